@@ -11,8 +11,18 @@ profile / tangential / planform / flowline / max / min curvature, TPI, TRI; Flor
 the reference defaults), inputs and outputs resident in HBM.  With N > 1 the raster is row-block partitioned
 (strong scaling: total work fixed) and every step includes the RCCL halo exchange.  Rank 0 prints ONE JSON line.
 
-Extra objects on that line: "roofline" (algorithmic bytes / HIP-event kernel time vs the 8 TB/s HBM peak) and
-"cpu_baseline" (the NumPy oracle = port of the reference's SciPy engine, timed on a bounded sample on this box).
+A plain run does only what the headline needs: set-up (input raster, plane placement), warm-up, the K timed steps, the
+--dump-outputs files if asked for, and the JSON line.  Everything else runs only with --full (the --no-* options then trim it):
+"roofline" (algorithmic bytes / HIP-event kernel time vs the 8 TB/s HBM peak, clock and sysfs samples during the timed steps),
+the spot check of the timed planes, the A/B leg on the other plane placement, "device_state", "cpu_baseline" (the NumPy
+oracle = port of the reference's SciPy engine, timed on a bounded sample on this box), "secondary" (C4 row blocks, the
+variogram / Nuth-Kaab / terrain-set / public-function legs) and "end_to_end".
+
+  python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR
+
+writes the 11 attribute planes of the last timed step as DIR/<attribute>.npy (float32; the interior pixels, whose windows lie
+inside the raster, at a fixed, seeded sample when there are more than DUMP_SAMPLES of them), so that two builds can be compared
+output for output.
 """
 from __future__ import annotations
 
@@ -34,6 +44,8 @@ C3_SIZE = int(os.environ.get("XDEM_BENCH_C3_SIZE", "20000"))  # test knobs of th
 C5_RUNS = int(os.environ.get("XDEM_BENCH_C5_RUNS", "100"))
 HBM_PEAK_GBPS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s spec peak (about 6.3 TB/s achievable)
 BYTES_PER_PIXEL = 4 + 4 * len(FULL)  # 4 B read + 4 B per attribute written = 48 B
+DUMP_SAMPLES = 1 << 20   # --dump-outputs: pixels per attribute plane (11 planes x 4 MiB of float32)
+DUMP_SEED = 20251016
 
 
 def _cpu_terrain_tile(args):
@@ -841,6 +853,46 @@ def end_to_end_calls(ctx, dev) -> dict:
     return out
 
 
+def dump_positions(n: int, depth: int):
+    """Global (rows, cols) of the pixels --dump-outputs writes, in row-major order: the interior of the n x n raster -- every pixel
+    whose window lies inside it; the `depth` outer rows and columns are NaN by definition of the attributes, nothing a build computes
+    -- whole when it holds at most DUMP_SAMPLES pixels, otherwise the positions DUMP_SEED draws from it (duplicates dropped), the
+    same in every run of the same --size.  Second value: the 2-D shape of the whole interior, or None for a sample."""
+    import numpy as np
+
+    m = n - 2 * depth
+    if m * m <= DUMP_SAMPLES:
+        flat, shape = np.arange(m * m, dtype=np.int64), (m, m)
+    else:
+        flat, shape = np.unique(np.random.default_rng(DUMP_SEED).integers(0, m * m, DUMP_SAMPLES, dtype=np.int64)), None
+    return (flat // m + depth, flat % m + depth), shape
+
+
+def dump_outputs(dirname: str, out, block, n: int, depth: int, rank: int, world: int) -> None:
+    """--dump-outputs: the (n_attr, rows, n) planes of this rank's row block, as the caller of the timed path receives them after
+    its last step, written by rank 0 as <dirname>/<attribute>.npy (float32) at the positions of dump_positions()."""
+    import numpy as np
+    import torch
+
+    (rows, cols), shape = dump_positions(n, depth)
+    lo, hi = np.searchsorted(rows, [block.r0, block.r1])
+    r = torch.from_numpy(rows[lo:hi] - block.r0).to(out.device)
+    c = torch.from_numpy(cols[lo:hi]).to(out.device)
+    vals = out[:, r, c].cpu().numpy()
+    parts = [vals]
+    if world > 1:   # row blocks in rank order: their concatenation is in global row-major order
+        import torch.distributed as dist
+
+        parts = [None] * world
+        dist.all_gather_object(parts, vals)
+    if rank != 0:
+        return
+    vals = np.concatenate(parts, axis=1)
+    os.makedirs(dirname, exist_ok=True)
+    for i, name in enumerate(FULL):
+        np.save(os.path.join(dirname, f"{name}.npy"), vals[i].reshape(shape) if shape else vals[i])
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -852,7 +904,15 @@ def main() -> None:
     ap.add_argument("--no-overlap", action="store_true", help="wait for the halo before launching anything")
     ap.add_argument("--c5a", action="store_true", help="also run the variogram at C5 reading A (5e13 pairs: about two minutes)")
     ap.add_argument("--no-end-to-end", action="store_true", help="skip the host-buffer (PCIe-inclusive) C2 figure")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement and check beyond the headline (roofline, spot check, plane A/B, device state, "
+                         "CPU baselines, secondary legs, end-to-end figures); the --no-* options trim this set")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the attribute planes of the last timed step as DIR/<attribute>.npy (float32; the raster's "
+                         f"interior, at a fixed, seeded sample of {DUMP_SAMPLES} pixels per plane when it is larger)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit(f"--steps {args.steps} --warmup {args.warmup}: at least one timed step, no negative warm-up")
 
     import torch
     import torch.distributed as dist
@@ -922,14 +982,17 @@ def main() -> None:
         if world > 1:  # communicator set-up (RCCL creates its point-to-point channels lazily) is not a step: do it up front
             xdist.RowBlock.wait_all(block.exchange())
             barrier()
-        sampler = GpuSampler(local_rank).start()   # clock / power / temperature while the warm-up and the timed steps run
-        # HIP events around every step ON THE LAUNCH STREAM (the library launches on torch's current stream here), recorded
-        # inside the timed region and read after it: the same launches under both clocks
-        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(steps)]
-        # the shader clock UNDER the launch: one sleeping wave per timed step on a side stream (xdemhip_clock_probe: ticks of the
-        # shader-clock counter against the constant 100 MHz one; ~7 ms each, inside its step) -- nothing the timed stream waits for
-        side = torch.cuda.Stream(device=dev)
-        ticks = torch.zeros((steps, 2), dtype=torch.int64, device=dev)
+        # --full instruments the timed steps; a plain run times them by the wall clock alone
+        instrument = args.full
+        if instrument:
+            sampler = GpuSampler(local_rank).start()   # clock / power / temperature while the warm-up and the timed steps run
+            # HIP events around every step ON THE LAUNCH STREAM (the library launches on torch's current stream here), recorded
+            # inside the timed region and read after it: the same launches under both clocks
+            ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(steps)]
+            # the shader clock UNDER the launch: one sleeping wave per timed step on a side stream (xdemhip_clock_probe: ticks of the
+            # shader-clock counter against the constant 100 MHz one; ~7 ms each, inside its step) -- nothing the timed stream waits for
+            side = torch.cuda.Stream(device=dev)
+            ticks = torch.zeros((steps, 2), dtype=torch.int64, device=dev)
         # (events, side stream and probe buffer exist BEFORE the warm-up: between the warm-up's last launch and the first timed one
         # there is only the contract's barrier + synchronize -- session r06aq: with the set-up in that gap the GPU sat idle long enough
         # to leave its clock state, and the first timed step took 14-15 ms against 12.7-12.8 ms for the rest, kernel_ms_series)
@@ -937,16 +1000,23 @@ def main() -> None:
             step()
         barrier()
         t0 = time.perf_counter()
-        for i, (a_, b_) in enumerate(ev):
-            a_.record()
+        for i in range(steps):
+            if instrument:
+                ev[i][0].record()
             step()
-            b_.record()
-            try:
-                ctx.clock_probe(side, ticks[i], sleeps=1600)
-            except Exception:
-                pass
+            if instrument:
+                ev[i][1].record()
+                try:
+                    ctx.clock_probe(side, ticks[i], sleeps=1600)
+                except Exception:
+                    pass
         barrier()
         t1 = time.perf_counter()
+        t = torch.tensor([t1 - t0], device="cpu" if share else dev, dtype=torch.float64)
+        if world > 1:
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        if not instrument:
+            return float(t.item()), block, out, None, {"planes": chosen}
         sampler.stop()
         tk = ticks.cpu().numpy().astype("float64")
         mhz = [100.0 * c / w for c, w in tk if w > 0]
@@ -954,9 +1024,6 @@ def main() -> None:
                                       "max_GHz": round(max(mhz) / 1e3, 4), "probes": len(mhz),
                                       "source": "xdemhip_clock_probe: one sleeping wave per timed step next to the launch, s_memtime "
                                                 "(shader clock) / s_memrealtime (100 MHz)"}
-        t = torch.tensor([t1 - t0], device="cpu" if share else dev, dtype=torch.float64)
-        if world > 1:
-            dist.all_reduce(t, op=dist.ReduceOp.MAX)
         step_ms = [a_.elapsed_time(b_) for a_, b_ in ev]
         state = sampler.summary(t0, t1)
         state["shader_clock_under_load"] = clock
@@ -969,7 +1036,9 @@ def main() -> None:
 
     n = args.size
     elapsed, block, out, step_ms, gpu_state = partitioned_run(n, args.steps, args.warmup)
-    kernel_ms = sum(step_ms) / len(step_ms)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, block, n, depth, rank, world)
+    # (the checks and legs from here on run with --full only; a plain run goes straight to the JSON line)
     # A/B of the plane backing inside the same process (one GPU): the same launches on planes a CALLER would bring -- an ordinary
     # allocation (torch.empty = hipMalloc), which on some boxes is one physically contiguous block -- after the library's
     # scattered backing above.  Every driver run is thereby a data point of "is >= 0.70 the kernel's or the allocator's"
@@ -981,7 +1050,7 @@ def main() -> None:
     lo = max(depth, (block.rows // 2) & ~31)
     hi = min(lo + 64, block.rows - depth)
     spot = None
-    if hi - lo >= 8:
+    if args.full and hi - lo >= 8:
         crop = terrain.terrain_attributes_device(block.interior[lo - depth:hi + depth], FULL, halo_top=depth, halo_bottom=depth, **kw)
         torch.cuda.synchronize(dev)
         same = bool(torch.equal(torch.nan_to_num(crop, nan=-7.0e33), torch.nan_to_num(out[:, lo:hi], nan=-7.0e33)))
@@ -995,7 +1064,7 @@ def main() -> None:
         del crop
     ab = None
     gpu_state2 = None
-    if world == 1 and os.environ.get("XDEM_BENCH_AB", "1") == "1" and os.environ.get("XDEM_BENCH_PLANES", "auto") == "auto":
+    if args.full and world == 1 and os.environ.get("XDEM_BENCH_AB", "1") == "1" and os.environ.get("XDEM_BENCH_PLANES", "auto") == "auto":
         del out
         import gc
 
@@ -1017,12 +1086,14 @@ def main() -> None:
     # launch stream around each step; one step = the streaming kernel over the raster interior + the tile kernel over its frame
     # of edge tiles, plus the halo exchange when the raster is partitioned).  By construction kernel_ms <= ms_per_step.
     px_launch = block.rows * n
-    achieved = BYTES_PER_PIXEL * px_launch / (kernel_ms * 1e-3) / 1e9
+    if args.full:
+        kernel_ms = sum(step_ms) / len(step_ms)
+        achieved = BYTES_PER_PIXEL * px_launch / (kernel_ms * 1e-3) / 1e9
 
     # C4 (BASELINE.json configs[3]): 65536^2 over the row blocks of all ranks with the halo exchange -- run by every rank whenever
     # the job has more than one, reported under "secondary" (the headline stays the metric's 40000^2 raster)
     c4 = None
-    if world > 1 and not args.no_secondary and n != C4_SIZE:
+    if args.full and world > 1 and not args.no_secondary and n != C4_SIZE:
         del out, block
         torch.cuda.empty_cache()
         c4_steps = max(2, min(args.steps, 5))
@@ -1055,30 +1126,31 @@ def main() -> None:
                        "partition": f"{world} row block(s), halo depth {depth}" +
                                     (", shared-GPU gloo test mode" if share else (", RCCL send/recv" if world > 1 else "")),
                        "bytes_per_pixel": BYTES_PER_PIXEL},
-            "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBPS, 4),
-                         "traffic": (lambda t: None if t is None else round(t[0] / (kernel_ms * 1e-3) / 1e9, 1))(
-                             measured_traffic_bytes(px_launch) if world == 1 else None),
-                         "traffic_bytes_per_launch": (lambda t: None if t is None else t[0])(
-                             measured_traffic_bytes(px_launch) if world == 1 else None),
-                         "traffic_source": (lambda t: None if t is None else
-                                            f"profiles/{t[1]}: rocprofv3 --pmc passes of this command (2 x FETCH_SIZE + WRITE_SIZE), "
-                                            "a committed profile, not re-measured in this run")(
-                             measured_traffic_bytes(px_launch) if world == 1 else None),
-                         "kernel": "terrain_strip_kernel<Florinsky,curv,win,lean tail> (raster interior, 98.6 % of the pixels) + "
-                                   "terrain_tile_kernel (frame of edge tiles)",
-                         "kernel_ms_source": "mean HIP-event time of the timed steps themselves (events on the launch stream)",
-                         "kernel_ms": round(kernel_ms, 4), "kernel_ms_min": round(min(step_ms), 4),
-                         "kernel_ms_max": round(max(step_ms), 4), "kernel_ms_series": [round(x, 3) for x in step_ms],
-                         "pixels_per_launch": px_launch, "output_spot_check": spot,
-                         # what the GPU was doing WHILE the timed steps ran (sysfs samples: see GpuSampler)
-                         "issue": issue_bound("headline: full 11, Florinsky, geometric curvatures", float(px_launch), kernel_ms, achieved / HBM_PEAK_GBPS, isa_cycles()),
-                         "clock_GHz": (lambda c: None if not c else c["mean_GHz"])((gpu_state or {}).get("shader_clock_under_load")),
-                         "clock_GHz_caller_planes": (lambda c: None if not c else c["mean_GHz"])((gpu_state2 or {}).get("shader_clock_under_load")),
-                         "power_W": (lambda c: None if not c else c["mean"])(None if (gpu_state or {}).get("sysfs_note") else (gpu_state or {}).get("power_W")),
-                         "gpu_state_during_timed_steps": gpu_state},
         }
-        res["roofline"]["planes"] = gpu_state.get("planes")   # which placement the timed planes have, and the calibration that chose it
+        if args.full:
+            res["roofline"] = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                               "frac": round(achieved / HBM_PEAK_GBPS, 4),
+                               "traffic": (lambda t: None if t is None else round(t[0] / (kernel_ms * 1e-3) / 1e9, 1))(
+                                   measured_traffic_bytes(px_launch) if world == 1 else None),
+                               "traffic_bytes_per_launch": (lambda t: None if t is None else t[0])(
+                                   measured_traffic_bytes(px_launch) if world == 1 else None),
+                               "traffic_source": (lambda t: None if t is None else
+                                                  f"profiles/{t[1]}: rocprofv3 --pmc passes of this command (2 x FETCH_SIZE + WRITE_SIZE), "
+                                                  "a committed profile, not re-measured in this run")(
+                                   measured_traffic_bytes(px_launch) if world == 1 else None),
+                               "kernel": "terrain_strip_kernel<Florinsky,curv,win,lean tail> (raster interior, 98.6 % of the pixels) + "
+                                         "terrain_tile_kernel (frame of edge tiles)",
+                               "kernel_ms_source": "mean HIP-event time of the timed steps themselves (events on the launch stream)",
+                               "kernel_ms": round(kernel_ms, 4), "kernel_ms_min": round(min(step_ms), 4),
+                               "kernel_ms_max": round(max(step_ms), 4), "kernel_ms_series": [round(x, 3) for x in step_ms],
+                               "pixels_per_launch": px_launch, "output_spot_check": spot,
+                               # what the GPU was doing WHILE the timed steps ran (sysfs samples: see GpuSampler)
+                               "issue": issue_bound("headline: full 11, Florinsky, geometric curvatures", float(px_launch), kernel_ms, achieved / HBM_PEAK_GBPS, isa_cycles()),
+                               "clock_GHz": (lambda c: None if not c else c["mean_GHz"])((gpu_state or {}).get("shader_clock_under_load")),
+                               "clock_GHz_caller_planes": (lambda c: None if not c else c["mean_GHz"])((gpu_state2 or {}).get("shader_clock_under_load")),
+                               "power_W": (lambda c: None if not c else c["mean"])(None if (gpu_state or {}).get("sysfs_note") else (gpu_state or {}).get("power_W")),
+                               "gpu_state_during_timed_steps": gpu_state}
+            res["roofline"]["planes"] = gpu_state.get("planes")   # which placement the timed planes have, and the calibration that chose it
         if ab is not None:
             # frac_caller_planes = the ORDINARY allocation (what a caller of the C-ABI brings), frac_scattered_planes = the library's pieces:
             # one of the two is the headline's own `frac`, the other the A/B leg's
@@ -1090,14 +1162,15 @@ def main() -> None:
             res["roofline"]["other_planes"] = ab
         res["config"]["rccl_ranks"] = world if world == 1 else dist.get_world_size()
         res["config"]["visible_gpus"] = torch.cuda.device_count()
-        res["device_state"] = device_state()
-        if not args.no_cpu_baseline and world == 1:
+        if args.full:
+            res["device_state"] = device_state()
+        if args.full and not args.no_cpu_baseline and world == 1:
             res["cpu_baseline"] = cpu_baseline()
         if c4 is not None:
             res["secondary"] = {"c4_terrain_row_blocks": c4}
     sec = None
     failed = []
-    if not args.no_secondary:   # every rank runs the secondary legs (they shard over the ranks); rank 0 reports
+    if args.full and not args.no_secondary:   # every rank runs the secondary legs (they shard over the ranks); rank 0 reports
         sets = None
         if world == 1:
             try:
@@ -1138,7 +1211,7 @@ def main() -> None:
             res.setdefault("secondary", {}).update(sec)
             if not args.no_cpu_baseline and world == 1 and "error" not in sec:
                 res["secondary"]["cpu_baseline"] = secondary_cpu_baselines()
-        if world == 1 and not args.no_end_to_end and not args.no_secondary:
+        if args.full and world == 1 and not args.no_end_to_end and not args.no_secondary:
             try:
                 res["end_to_end"] = end_to_end_host_path(ctx)
             except Exception as e:

@@ -321,7 +321,7 @@ def test_bench_two_ranks_reports_c4(tmp_path):
     env = dict(os.environ, XDEM_BENCH_SHARE_GPU="1", XDEM_BENCH_C4_SIZE="4096", XDEM_BENCH_C3_SIZE="3000", XDEM_BENCH_C5_RUNS="6",
                MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--size", "3000"]
+           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--size", "3000", "--full"]
     p = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=280)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -358,7 +358,7 @@ def test_bench_two_ranks_over_rccl_one_gpu_each(tmp_path):
                HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("XDEM_BENCH_SHARE_GPU", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--size", "8192"]
+           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--size", "8192", "--full"]
     p = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=560)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

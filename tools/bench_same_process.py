@@ -2,7 +2,7 @@
 """The bench line and the rocprofv3 kernel trace OF THE SAME PROCESS, side by side.
 
   cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -o bench -- \
-        python $REPO/bench.py --steps K --warmup W --no-cpu-baseline --no-secondary --no-end-to-end > <dir>/bench.log
+        python $REPO/bench.py --steps K --warmup W --full --no-cpu-baseline --no-secondary --no-end-to-end > <dir>/bench.log
   python tools/bench_same_process.py <dir> profiles/<tag>_bench_same_process.json
 
 bench.py launches, in this order: W warm-up + K timed steps on the library's scattered planes, then (XDEM_BENCH_AB, default on)

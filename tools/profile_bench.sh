@@ -12,10 +12,11 @@ TAG=${1:-r01}
 SIZE=${2:-40000}
 OUT=$GRAFT_REPO_ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
+BENCH=$(cd "$(dirname "$0")/.." && pwd)/bench.py
 cd /tmp && export TMPDIR=/tmp
-CMD="python $GRAFT_REPO_ROOT/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-secondary --no-end-to-end --size $SIZE"
+CMD="python $BENCH --steps 5 --warmup 2 --full --no-cpu-baseline --no-secondary --no-end-to-end --size $SIZE"
 # the stats pass also runs the secondary workloads (variogram C5-B, Nuth-Kaab C3) so their kernels show up in the summary
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- python $GRAFT_REPO_ROOT/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-end-to-end --size $SIZE > $OUT/stats.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- python $BENCH --steps 5 --warmup 2 --full --no-cpu-baseline --no-end-to-end --size $SIZE > $OUT/stats.log 2>&1
 timeout 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/fetch -o bench -- $CMD > $OUT/fetch.log 2>&1
 timeout 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/write -o bench -- $CMD > $OUT/write.log 2>&1
 timeout 600 rocprofv3 --pmc GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $OUT/grbm -o bench -- $CMD > $OUT/grbm.log 2>&1
