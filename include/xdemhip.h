@@ -337,6 +337,48 @@ void xdemhip_nk_destroy(xdemhip_nk_plan* plan);
 int xdemhip_binned_median(xdemhip_ctx* ctx, const void* x, const void* y, int dtype, int64_t n, int n_bins, double* edges,
                           int64_t* counts, double* medians);
 
+/* ---- bias corrections: Deramp and VerticalShift (elevation difference of two rasters on one grid) ----------------------------
+ * Replaces the array work of
+ *   Deramp._fit_rst_rst -> _bin_or_and_fit_nd("fit")   xdem/coreg/biascorr.py:195, 621-745; base.py:978-985
+ *       curve_fit(polynomial_2d, (xx, yy), ref - tba, p0=ones((order+1)^2)) over the valid pixels: here the least-squares moments
+ *   Deramp._apply_rst                                    biascorr.py:262-311 (+ the cast of base.py:491): xdemhip_poly2d_apply
+ *   vertical_shift(..., vshift_reduc_func=np.median)     xdem/coreg/affine.py:721-770: xdemhip_dh_median
+ * A dh plan holds ref, tba (H x W, `dtype`) and an optional inlier mask (0 / 1 bytes), in `memspace` like xdemhip_nk_create:
+ *
+ *  xdemhip_dh_create        valid = inlier & isfinite(ref) & isfinite(tba) (base.py:652-663); *n_valid = its count.
+ *  xdemhip_dh_subsample     the random subsample (base.py:577-617): the caller draws `k` distinct RANKS among the valid pixels in
+ *                           raster order (xdem_amd.coreg.subsample_ranks), the plan keeps those pixels -- flatnonzero(valid)[ranks] --
+ *                           as its selection for every later call; *n_drawn = their number.  Same tile count -> scan -> rank scheme
+ *                           as xdemhip_nk_subsample.
+ *  xdemhip_dh_poly_moments  least-squares sums of the tensor-product polynomial sum c[i, j] x^i y^j (xdem/fit.py:127-149; x = column,
+ *                           y = row_offset + row) over the selected pixels, in normalised coordinates u = (x - cx) / sx, v = (y - cy) / sy,
+ *                           cx = sx = (W_global - 1) / 2, cy = sy = (H_global - 1) / 2 (a half-width of 0 counts as 1):
+ *                             m_out[a * (2 order + 1) + b] = sum u^a v^b      (a, b <= 2 order)
+ *                             r_out[i * (order + 1) + j]   = sum dh u^i v^j   (i, j <= order)
+ *                           dh = ref - tba rounded in the input dtype, all sums float64, partials added in a fixed order (the same bits
+ *                           every call); *count = the number of selected pixels.  order 0..5.  A plan over raster rows
+ *                           [row_offset, row_offset + H) of an H_global x W grid returns sums that add up over row blocks.
+ *  xdemhip_dh_median        np.median(dh) over the selected pixels, exact, in the value dtype (radix selection; mean of the two middle
+ *                           values in the value dtype for an even count), and the count.
+ *  xdemhip_dh_values        dh (plan dtype) and the column / row index (int64) of every selected pixel, in raster order (any output may
+ *                           be NULL; each holds *count elements -- n_valid, or n_drawn after a subsample): what a host callable receives.
+ * Every entry returns XDEMHIP_EINVAL ("no valid points") where nothing is selected. */
+typedef struct xdemhip_dh_plan xdemhip_dh_plan;
+int xdemhip_dh_create(xdemhip_ctx* ctx, const void* ref, const void* tba, const uint8_t* inlier_mask_or_null, int dtype, int64_t H, int64_t W,
+                      int memspace, xdemhip_dh_plan** out_plan, int64_t* n_valid);
+int xdemhip_dh_subsample(xdemhip_dh_plan* plan, const int64_t* ranks, int64_t k, int memspace, int64_t* n_drawn);
+int xdemhip_dh_poly_moments(xdemhip_dh_plan* plan, int order, int64_t row_offset, int64_t H_global, int64_t W_global, double* m_out,
+                            double* r_out, int64_t* count);
+int xdemhip_dh_median(xdemhip_dh_plan* plan, double* median, int64_t* count);
+int xdemhip_dh_values(xdemhip_dh_plan* plan, void* dh_out, int64_t* col_out, int64_t* row_out, int memspace, int64_t* count);
+void xdemhip_dh_destroy(xdemhip_dh_plan* plan);
+/* out = cast(double(elev) + P(x, y)), P = np.polynomial.polynomial.polyval2d(x, y, c) with c[i, j] = coeffs[i * (order + 1) + j]
+ * (the reference's fit_params reshaped), x = column, y = row_offset + row, evaluated in NumPy's order bit for bit: Horner in x for
+ * every j (polyval, tensor form), then Horner in y (polyval, tensor=False), no fused multiply-add.  out has the dtype of elev: float32
+ * elev -> float32(elev + P) (the reference's final cast), float64 -> elev + P.  Non-finite elev stays non-finite.  order 0..5. */
+int xdemhip_poly2d_apply(xdemhip_ctx* ctx, const void* elev, int dtype, int64_t H, int64_t W, int64_t row_offset, const double* coeffs,
+                         int order, void* out, int memspace);
+
 /* "Next" row f4: the dense step of the patches method -- mean_filter_nan(img, kernel_size, kernel_shape)
  * (xdem/spatialstats.py:2597-2655: two scipy.ndimage.convolve calls with a ones / circular uint8 kernel, mode="constant",
  * cval=nan).  kernel_shape 0 = square, 1 = circular (_create_circular_mask, spatialstats.py:880-904).  Outputs are float64

@@ -173,6 +173,17 @@ def lib() -> ctypes.CDLL:
                                    ctypes.c_int, c_dp, c_dp, c_i64p]
         L.xdemhip_interp_grid_linear.argtypes = [c_ctx, ctypes.c_int, c_dp, c_ip, c_dp, ctypes.POINTER(ctypes.c_void_p), c_ip,
                                                  ctypes.c_int64, ctypes.c_double, c_dp, ctypes.c_int]
+        L.xdemhip_dh_create.argtypes = [c_ctx, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
+                                        ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), c_i64p]
+        L.xdemhip_dh_subsample.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, c_i64p]
+        L.xdemhip_dh_poly_moments.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, c_dp, c_dp,
+                                              c_i64p]
+        L.xdemhip_dh_median.argtypes = [ctypes.c_void_p, c_dp, c_i64p]
+        L.xdemhip_dh_values.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, c_i64p]
+        L.xdemhip_dh_destroy.argtypes = [ctypes.c_void_p]
+        L.xdemhip_dh_destroy.restype = None
+        L.xdemhip_poly2d_apply.argtypes = [c_ctx, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, c_dp,
+                                           ctypes.c_int, ctypes.c_void_p, ctypes.c_int]
         _lib = L
         return L
 

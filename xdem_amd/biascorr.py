@@ -1,0 +1,583 @@
+"""Deramp, VerticalShift and coregistration pipelines on MI355X -- host-side mirrors of ``xdem.coreg.Deramp``
+(``xdem/coreg/biascorr.py:621-745``), ``xdem.coreg.VerticalShift`` (``affine.py:721-770, 2013-2075``) and
+``xdem.coreg.CoregPipeline`` (``base.py:2008-2019, 2880-3190``) for two rasters on one grid.  Re-exported by ``xdem_amd.coreg``.
+
+Every pass over the grids runs in ``csrc/biascorr.hip`` through a dh plan (``xdemhip_dh_*``):
+
+* ``Deramp`` with the defaults ``fit_func=polynomial_2d`` and ``fit_optimizer=scipy.optimize.curve_fit`` takes the least-squares
+  moments of the polynomial over the valid (or drawn) pixels on the device, in normalised coordinates, and solves the
+  (order+1)^2 system in float64 here: the optimum ``curve_fit`` converges to from upstream's ``p0 = ones`` (the model is linear in
+  its parameters).  The coefficients are mapped back to raw pixel monomials, so ``fit_params`` has the reference's layout, and
+  ``fit_perr`` is curve_fit's ``absolute_sigma=True`` error.  Any other ``fit_func`` / ``fit_optimizer`` receives dh and the pixel
+  coordinates from the device and runs on the host exactly as upstream calls it (``base.py:978-985``); ``apply`` with a custom
+  ``fit_func`` evaluates it on the host too -- that route is slow and exists for compatibility.
+* ``VerticalShift`` with ``np.median`` / ``np.nanmedian`` selects the exact median of dh on the device; any other callable gets dh.
+* ``CoregPipeline`` chains the steps' public ``fit`` / ``apply`` as upstream does; rasters go back to the host between steps.
+
+Output dtype of ``apply`` = input dtype (float32 in, float32 out -- upstream's final cast; float64 in: ``elev + corr`` in float64).
+"""
+from __future__ import annotations
+
+import copy as _copy
+import ctypes
+import inspect
+import logging
+import math
+import warnings
+from typing import Any, Callable
+
+import numpy as np
+import scipy.optimize
+
+from . import _lib
+
+_NO_VALID = ("There is no valid points common to the input and auxiliary data (bias variables, or "
+             "derivatives required for this method, for example slope, aspect, etc).")
+MAX_DEVICE_ORDER = 5
+
+
+def polynomial_2d(xx, *params):
+    """N-order 2-D polynomial ``np.polynomial.polynomial.polyval2d(xx[0], xx[1], c)`` with ``c`` the (order+1)^2 params reshaped to
+    a square (xdem/fit.py:127-149)."""
+    poly_order = np.sqrt(len(params))
+    if not poly_order.is_integer():
+        raise ValueError("The parameters of the 2D polynomial should have a length equal to order^2, "
+                         "see np.polyval2d for more details.")
+    c = np.array(params).reshape((int(poly_order), int(poly_order)))
+    return np.polynomial.polynomial.polyval2d(xx[0], xx[1], c)
+
+
+def _host_array(a):
+    if a is None:
+        return None
+    return np.asarray(a.filled(np.nan) if isinstance(a, np.ma.MaskedArray) else a)
+
+
+# ---- the device plan --------------------------------------------------------------------------------------------------------
+class DhPlan:
+    """Device-resident elevation difference of two rasters (``xdemhip_dh_plan``): valid mask, optional random subsample, and the
+    reductions Deramp / VerticalShift need.  ``ref`` / ``tba``: 2-D NumPy arrays, or contiguous CUDA tensors of one dtype (kept alive by
+    the plan, never copied)."""
+
+    def __init__(self, ref, tba, inlier_mask=None, ctx: _lib.Context | None = None):
+        self.ctx = ctx or _lib.default_context()
+        self.handle = None
+        self.drawn = False
+        self.ctx.adopt(self)
+        h, nv = ctypes.c_void_p(), ctypes.c_int64()
+        L = self.ctx._L
+        if hasattr(ref, "is_cuda"):
+            import torch
+
+            if not (ref.is_cuda and tba.is_cuda and ref.is_contiguous() and tba.is_contiguous() and ref.dtype == tba.dtype
+                    and ref.shape == tba.shape and ref.dim() == 2 and ref.dtype in (torch.float32, torch.float64)):
+                raise ValueError("device inputs must be contiguous 2D float32 / float64 CUDA tensors of the same shape and dtype")
+            self.dtype = np.dtype(np.float32 if ref.dtype == torch.float32 else np.float64)
+            self.shape = tuple(ref.shape)
+            inl = None
+            if inlier_mask is not None:
+                inl = inlier_mask if hasattr(inlier_mask, "is_cuda") else torch.from_numpy(np.ascontiguousarray(inlier_mask, dtype=np.uint8))
+                inl = inl.to(device=ref.device, dtype=torch.uint8).contiguous()
+            self._keep = (ref, tba, inl)
+            torch.cuda.current_stream(ref.device).synchronize()
+            rc = L.xdemhip_dh_create(self.ctx.handle, ref.data_ptr(), tba.data_ptr(), inl.data_ptr() if inl is not None else None,
+                                     _lib.F32 if self.dtype == np.float32 else _lib.F64, self.shape[0], self.shape[1], _lib.DEVICE,
+                                     ctypes.byref(h), ctypes.byref(nv))
+        else:
+            ref, tba = np.ascontiguousarray(_host_array(ref)), np.ascontiguousarray(_host_array(tba))
+            if ref.shape != tba.shape or ref.ndim != 2:
+                raise ValueError("ref and tba must be 2D arrays of the same shape")
+            if ref.dtype != tba.dtype or ref.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+                dt = np.float64 if np.float64 in (ref.dtype, tba.dtype) else np.float32
+                ref, tba = ref.astype(dt), tba.astype(dt)
+            self.dtype = ref.dtype
+            self.shape = ref.shape
+            inl = None if inlier_mask is None else np.ascontiguousarray(_host_array(inlier_mask), dtype=np.uint8)
+            if inl is not None and inl.shape != ref.shape:
+                raise ValueError("inlier_mask must have the shape of the rasters")
+            rc = L.xdemhip_dh_create(self.ctx.handle, ref.ctypes.data, tba.ctypes.data, inl.ctypes.data if inl is not None else None,
+                                     _lib.F32 if self.dtype == np.float32 else _lib.F64, ref.shape[0], ref.shape[1], _lib.HOST,
+                                     ctypes.byref(h), ctypes.byref(nv))
+        self.ctx.check(rc)
+        self.handle = h
+        self.n_valid = int(nv.value)
+        self.n_selected = self.n_valid
+
+    def subsample(self, ranks: np.ndarray) -> int:
+        """Keep the valid pixels whose rank (position among the valid pixels in raster order) is listed: ``flatnonzero(valid)[ranks]``,
+        formed on the device (``xdemhip_dh_subsample``).  Returns their number."""
+        ranks = np.ascontiguousarray(ranks, dtype=np.int64)
+        k = ctypes.c_int64()
+        self.ctx.check(self.ctx._L.xdemhip_dh_subsample(self.handle, ranks.ctypes.data, int(ranks.size), _lib.HOST, ctypes.byref(k)))
+        self.drawn = True
+        self.n_selected = int(k.value)
+        return self.n_selected
+
+    def poly_moments(self, order: int, row_offset: int = 0, H_global: int | None = None, W_global: int | None = None):
+        """(M, R, count): M[a, b] = sum u^a v^b (a, b <= 2 order), R[i, j] = sum dh u^i v^j (i, j <= order) over the selected pixels, in
+        the normalised coordinates of ``poly_norm`` (``xdemhip_dh_poly_moments``)."""
+        order = int(order)
+        H_global = self.shape[0] if H_global is None else int(H_global)
+        W_global = self.shape[1] if W_global is None else int(W_global)
+        m = np.empty((2 * order + 1, 2 * order + 1), dtype=np.float64)
+        r = np.empty((order + 1, order + 1), dtype=np.float64)
+        cnt = ctypes.c_int64()
+        dp = ctypes.POINTER(ctypes.c_double)
+        self.ctx.check(self.ctx._L.xdemhip_dh_poly_moments(self.handle, order, int(row_offset), H_global, W_global, m.ctypes.data_as(dp),
+                                                           r.ctypes.data_as(dp), ctypes.byref(cnt)))
+        return m, r, int(cnt.value)
+
+    def median(self) -> tuple[float, int]:
+        """Exact ``np.median(dh)`` over the selected pixels in the value dtype, and their number (``xdemhip_dh_median``)."""
+        med, cnt = ctypes.c_double(), ctypes.c_int64()
+        self.ctx.check(self.ctx._L.xdemhip_dh_median(self.handle, ctypes.byref(med), ctypes.byref(cnt)))
+        return med.value, int(cnt.value)
+
+    def values(self, coords: bool = True):
+        """dh of the selected pixels (plan dtype, raster order) and -- with ``coords`` -- their column and row indexes (int64)."""
+        k = self.n_selected
+        dh = np.empty(k, dtype=self.dtype)
+        col = np.empty(k, dtype=np.int64) if coords else None
+        row = np.empty(k, dtype=np.int64) if coords else None
+        cnt = ctypes.c_int64()
+        self.ctx.check(self.ctx._L.xdemhip_dh_values(self.handle, dh.ctypes.data, col.ctypes.data if coords else None,
+                                                     row.ctypes.data if coords else None, _lib.HOST, ctypes.byref(cnt)))
+        if int(cnt.value) != k:
+            raise _lib.XdemHipError(f"xdemhip_dh_values returned {cnt.value} values, expected {k}")
+        return (dh, col, row) if coords else dh
+
+    def close(self) -> None:
+        if getattr(self, "handle", None):
+            if getattr(self.ctx, "handle", None):
+                self.ctx._L.xdemhip_dh_destroy(self.handle)
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _draw(plan: DhPlan, subsample, random_state) -> int:
+    """The random subsample of upstream's ``_get_subsample_on_valid_mask`` (base.py:577-617; geoutils' draw restated by
+    ``xdem_amd.coreg.subsample_ranks``) applied to the plan; returns the number of pixels the fit uses."""
+    from .coreg import subsample_ranks
+
+    if plan.n_valid == 0:
+        raise ValueError(_NO_VALID)
+    if subsample == 1:
+        return plan.n_valid
+    ranks = subsample_ranks(plan.n_valid, subsample, random_state)
+    if ranks.size == plan.n_valid:   # every valid pixel drawn: the whole-raster route covers the same set
+        return plan.n_valid
+    return plan.subsample(ranks)
+
+
+# ---- polynomial algebra on the host --------------------------------------------------------------------------------------------
+def poly_norm(n_global: int) -> tuple[float, float]:
+    """(centre, half-width) of the normalised coordinate of an axis of n_global pixels: u = (x - centre) / half-width (include/xdemhip.h)."""
+    half = 0.5 * (n_global - 1)
+    return half, (half if half > 0 else 1.0)
+
+
+def _axis_transform(K: int, centre: float, scale: float) -> np.ndarray:
+    """T[m, i] = C(i, m) (-centre)^(i - m) / scale^i: raw-monomial coefficients of u^i, u = (x - centre) / scale."""
+    T = np.zeros((K, K), dtype=np.float64)
+    for i in range(K):
+        for m in range(i + 1):
+            T[m, i] = math.comb(i, m) * (-centre) ** (i - m) / scale ** i
+    return T
+
+
+def coeff_transform(order: int, shape: tuple[int, int]) -> np.ndarray:
+    """The (K^2 x K^2) map from coefficients b[i, j] of u^i v^j to coefficients c[m, n] of x^m y^n (K = order + 1, both raveled in C
+    order, the layout of polynomial_2d's params), for a grid of ``shape`` = (H, W)."""
+    K = order + 1
+    cx, sx = poly_norm(shape[1])
+    cy, sy = poly_norm(shape[0])
+    return np.kron(_axis_transform(K, cx, sx), _axis_transform(K, cy, sy))
+
+
+def solve_moments(M: np.ndarray, R: np.ndarray, order: int, shape: tuple[int, int]):
+    """Least-squares polynomial from the device moments: the Gram matrix G[(i,j),(k,l)] = M[i+k, j+l] and right-hand side R[i, j] in
+    normalised coordinates, solved in float64 (minimum-norm where G is rank-deficient, e.g. all points on one row), mapped back to raw
+    pixel monomials.  Returns (fit_params, fit_perr): perr = sqrt(diag(T G^-1 T^T)), curve_fit's ``absolute_sigma=True`` error."""
+    K = order + 1
+    idx = [(i, j) for i in range(K) for j in range(K)]
+    G = np.array([[M[i + k, j + l] for (k, l) in idx] for (i, j) in idx], dtype=np.float64)
+    rhs = np.array([R[i, j] for (i, j) in idx], dtype=np.float64)
+    if np.linalg.matrix_rank(G) == G.shape[0]:
+        b = np.linalg.solve(G, rhs)
+        Ginv = np.linalg.inv(G)
+    else:
+        b = np.linalg.lstsq(G, rhs, rcond=None)[0]
+        Ginv = np.linalg.pinv(G)
+    T = coeff_transform(order, shape)
+    params = T @ b
+    cov = T @ Ginv @ T.T
+    return params, np.sqrt(np.abs(np.diag(cov)))
+
+
+def poly2d_apply(elev, params, row_offset: int = 0, ctx: _lib.Context | None = None, out=None):
+    """``elev + polyval2d(xx, yy, c)`` on the device, NumPy's evaluation order bit for bit (``xdemhip_poly2d_apply``); float32 elev gives
+    the float32 cast of the float64 sum, float64 elev the float64 sum.  ``elev``: a 2-D NumPy array, or a contiguous 2-D float32 /
+    float64 CUDA tensor -- then the result (``out`` if given: a contiguous CUDA tensor of the same shape, dtype and device) is written on
+    the current torch stream, ordered after the work that produced ``elev`` and before whatever the caller queues next, without a host
+    synchronisation (the context's stream is set to that stream, as ``terrain_attributes_device`` does)."""
+    params = np.ascontiguousarray(params, dtype=np.float64).ravel()
+    K = int(round(math.sqrt(params.size)))
+    if K * K != params.size:
+        raise ValueError("The parameters of the 2D polynomial should have a length equal to order^2, see np.polyval2d for more details.")
+    if K - 1 > MAX_DEVICE_ORDER:
+        raise NotImplementedError(f"poly_order > {MAX_DEVICE_ORDER} is not supported on the device")
+    dp = ctypes.POINTER(ctypes.c_double)
+    if hasattr(elev, "is_cuda"):
+        import torch
+
+        if not (elev.is_cuda and elev.dim() == 2 and elev.is_contiguous() and elev.dtype in (torch.float32, torch.float64)):
+            raise ValueError("device elev must be a contiguous 2D float32 / float64 CUDA tensor")
+        if out is None:
+            out = torch.empty_like(elev, memory_format=torch.contiguous_format)
+        elif not (hasattr(out, "is_cuda") and out.is_cuda and out.is_contiguous() and out.shape == elev.shape and out.dtype == elev.dtype
+                  and out.device == elev.device):
+            raise ValueError("out must be a contiguous CUDA tensor of elev's shape, dtype and device")
+        ctx = ctx or _lib.default_context(elev.device.index)
+        with ctx.call_lock:
+            ctx.set_stream(torch.cuda.current_stream(elev.device).cuda_stream)
+            ctx.check(ctx._L.xdemhip_poly2d_apply(ctx.handle, elev.data_ptr(), _lib.F32 if elev.dtype == torch.float32 else _lib.F64,
+                                                  elev.shape[0], elev.shape[1], int(row_offset), params.ctypes.data_as(dp), K - 1,
+                                                  out.data_ptr(), _lib.DEVICE))
+        return out
+    ctx = ctx or _lib.default_context()
+    arr = np.ascontiguousarray(_host_array(elev))
+    if arr.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+        arr = arr.astype(np.float32)
+    res = np.empty_like(arr)
+    ctx.check(ctx._L.xdemhip_poly2d_apply(ctx.handle, arr.ctypes.data, _lib.F32 if arr.dtype == np.float32 else _lib.F64, arr.shape[0],
+                                          arr.shape[1], int(row_offset), params.ctypes.data_as(dp), K - 1, res.ctypes.data, _lib.HOST))
+    return res
+
+
+# ---- shared plumbing of the three classes --------------------------------------------------------------------------------------
+class _Step:
+    """What Deramp, VerticalShift and CoregPipeline share with ``xdem.coreg.Coreg``: copy, ``+``, fit_and_apply."""
+
+    def copy(self):
+        """Identical, independent copy (base.py:1999-2006)."""
+        new = self.__new__(type(self))
+        new.__dict__ = {k: _copy.deepcopy(v) for k, v in self.__dict__.items()}
+        return new
+
+    def __add__(self, other) -> "CoregPipeline":
+        return _pipeline_add(self, other)
+
+    def fit_and_apply(self, reference_elev, to_be_aligned_elev, inlier_mask=None, bias_vars=None, weights=None, subsample=None,
+                      transform=None, crs=None, area_or_point=None, z_name: str = "z", resample: bool = True,
+                      resampling: str = "bilinear", random_state=None, fit_kwargs=None, apply_kwargs=None):
+        """``Coreg.fit_and_apply`` (base.py:2482-2590): fit, then apply to the to-be-aligned elevations."""
+        fit_kwargs = dict(fit_kwargs or {})
+        apply_kwargs = dict(apply_kwargs or {})
+        self.fit(reference_elev, to_be_aligned_elev, inlier_mask=inlier_mask, bias_vars=bias_vars, weights=weights, subsample=subsample,
+                 transform=transform, crs=crs, area_or_point=area_or_point, z_name=z_name, random_state=random_state, **fit_kwargs)
+        if "resolution" in fit_kwargs:
+            apply_kwargs.setdefault("resolution", fit_kwargs["resolution"])
+        return self.apply(to_be_aligned_elev, bias_vars=bias_vars, resample=resample, resampling=resampling, transform=transform, crs=crs,
+                          z_name=z_name, **apply_kwargs)
+
+
+def _is_step(obj) -> bool:
+    from .coreg import NuthKaab
+
+    return isinstance(obj, (NuthKaab, _Step))
+
+
+def _pipeline_add(a, b) -> "CoregPipeline":
+    """``Coreg.__add__`` (base.py:2008-2019): a two-step pipeline; an ``initial_shift`` of either step is dropped."""
+    if not _is_step(b):
+        raise ValueError(f"Incompatible add type: {type(b)}. Expected 'Coreg' subclass")
+    for m in (a, b):
+        if "affine" in m.meta["inputs"] and "initial_shift" in m.meta["inputs"]["affine"]:
+            del m.meta["inputs"]["affine"]["initial_shift"]
+    return CoregPipeline([a, b])
+
+
+def _with_transform(out, transform):
+    return out if transform is None else (out, transform)
+
+
+def _check_weights(weights) -> None:
+    if weights is not None:
+        raise NotImplementedError("Weights have not yet been implemented")
+
+
+# ---- Deramp ---------------------------------------------------------------------------------------------------------------------
+class Deramp(_Step):
+    """Correct a 2-D polynomial along the pixel coordinates (tilts, domes).  Constructor of ``xdem.coreg.Deramp``
+    (biascorr.py:630-640); only ``fit_or_bin="fit"`` is implemented here.  The parameters land in
+    ``meta["outputs"]["fitorbin"]["fit_params"]`` in the reference's layout: ``fit_func((xx, yy), *fit_params)`` is the surface."""
+
+    def __init__(self, poly_order: int = 2, fit_or_bin: str = "fit", fit_func: Callable[..., Any] = polynomial_2d,
+                 fit_optimizer: Callable[..., Any] = scipy.optimize.curve_fit, bin_sizes=10, bin_statistic=np.nanmedian,
+                 bin_apply_method: str = "linear", subsample: float | int = 5e5) -> None:
+        if fit_or_bin not in ["fit", "bin", "bin_and_fit"]:
+            raise ValueError(f"Argument `fit_or_bin` must be 'bin_and_fit', 'fit' or 'bin', got {fit_or_bin}.")
+        if fit_or_bin != "fit":
+            raise NotImplementedError(f"fit_or_bin={fit_or_bin!r}: only \"fit\" is implemented for Deramp here.")
+        if not callable(fit_func):
+            raise TypeError(f"Argument `fit_func` must be a function (callable), got {type(fit_func)}.")
+        if not callable(fit_optimizer):
+            raise TypeError(f"Argument `fit_optimizer` must be a function (callable), got {type(fit_optimizer)}.")
+        self.meta: dict[str, Any] = {
+            "inputs": {
+                "fitorbin": {"fit_or_bin": fit_or_bin, "fit_func": fit_func, "fit_optimizer": fit_optimizer, "bin_sizes": bin_sizes,
+                             "bin_statistic": bin_statistic, "bin_apply_method": bin_apply_method, "bias_var_names": ["xx", "yy"]},
+                "random": {"subsample": subsample, "random_state": None},
+                "specific": {"poly_order": int(poly_order)},
+            },
+            "outputs": {},
+        }
+        self._needs_vars = False
+
+    def _device_route(self) -> bool:
+        fb = self.meta["inputs"]["fitorbin"]
+        return fb["fit_func"] is polynomial_2d and fb["fit_optimizer"] is scipy.optimize.curve_fit
+
+    def fit(self, reference_elev, to_be_aligned_elev, inlier_mask=None, bias_vars=None, weights=None, subsample=None, transform=None,
+            crs=None, area_or_point=None, z_name=None, random_state=None, resolution=None, **kwargs: Any) -> "Deramp":
+        """Estimate the polynomial of dh = reference - to_be_aligned over the valid (and drawn) pixels (``Coreg.fit`` with
+        ``_fit_rst_rst``, biascorr.py:663-695).  ``transform`` / ``resolution`` are accepted for call compatibility (pixel
+        coordinates need neither)."""
+        _check_weights(weights)
+        if bias_vars is not None:
+            raise NotImplementedError("bias_vars is not used by Deramp (its variables are the pixel coordinates).")
+        if subsample is not None:
+            self.meta["inputs"]["random"]["subsample"] = subsample
+        if random_state is not None:
+            self.meta["inputs"]["random"]["random_state"] = random_state
+        order = self.meta["inputs"]["specific"]["poly_order"]
+        n_params = (order + 1) ** 2
+        if self._device_route() and order > MAX_DEVICE_ORDER:
+            raise NotImplementedError(f"Deramp: poly_order 0..{MAX_DEVICE_ORDER} on the device, got {order}")
+        with DhPlan(reference_elev, to_be_aligned_elev, inlier_mask) as plan:
+            n = _draw(plan, self.meta["inputs"]["random"]["subsample"], self.meta["inputs"]["random"]["random_state"])
+            if n < n_params:   # (what curve_fit raises for fewer points than parameters)
+                raise TypeError(f"Improper input: func input vector length N={n_params} must not exceed func output vector length M={n}")
+            logging.debug("Estimating a 2D polynomial of order %d on %d points.", order, n)
+            if self._device_route():
+                M, R, _ = plan.poly_moments(order)
+                params, perr = solve_moments(M, R, order, plan.shape)
+            else:
+                dh, col, row = plan.values()
+                fb = self.meta["inputs"]["fitorbin"]
+                results = fb["fit_optimizer"](f=fb["fit_func"], xdata=np.array([col, row]).squeeze(), ydata=dh, sigma=None,
+                                              absolute_sigma=True, p0=np.ones(n_params), **kwargs)
+                params = results[0]
+                perr = np.sqrt(np.diag(results[1])) if fb["fit_optimizer"] is scipy.optimize.curve_fit else None
+        self.meta["outputs"]["fitorbin"] = {"fit_params": np.asarray(params)}
+        if perr is not None:
+            self.meta["outputs"]["fitorbin"]["fit_perr"] = perr
+        self.meta["outputs"]["random"] = {"subsample_final": int(n)}
+        return self
+
+    def apply(self, elev, resolution=None, resample: bool = True, *, bias_vars=None, resampling: str = "bilinear", transform=None, crs=None,
+              z_name: str = "z"):
+        """``elev + fit_func((xx, yy), *fit_params)`` (biascorr.py:262-311, 740-745) in the input dtype; with ``transform=`` the call
+        returns ``(array, transform)`` like upstream's array interface."""
+        if "fitorbin" not in self.meta["outputs"]:
+            raise AssertionError(".fit() does not seem to have been called yet")
+        if bias_vars is not None:
+            raise NotImplementedError("bias_vars is not used by Deramp (its variables are the pixel coordinates).")
+        params = self.meta["outputs"]["fitorbin"]["fit_params"]
+        fit_func = self.meta["inputs"]["fitorbin"]["fit_func"]
+        if fit_func is polynomial_2d:
+            out = poly2d_apply(elev, params)
+        else:   # a custom surface: evaluated on the host, as upstream does
+            arr = np.asarray(_host_array(elev))
+            if arr.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+                arr = arr.astype(np.float32)
+            xx, yy = np.meshgrid(np.arange(0, arr.shape[1]), np.arange(0, arr.shape[0]))
+            out = (arr + fit_func((xx, yy), *params)).astype(arr.dtype)
+        return _with_transform(out, transform)
+
+    @property
+    def is_affine(self) -> bool:
+        return False
+
+    def to_matrix(self):
+        raise NotImplementedError("Deramp is not an affine transformation: it has no matrix.")
+
+
+# ---- VerticalShift --------------------------------------------------------------------------------------------------------------
+class VerticalShift(_Step):
+    """Shift the to-be-aligned DEM by a central tendency of dh (``xdem.coreg.VerticalShift``, affine.py:2013-2075).
+    ``np.median`` / ``np.nanmedian`` are exact selections on the device; any other callable receives dh (value dtype, raster order)."""
+
+    def __init__(self, vshift_reduc_func: Callable[[np.ndarray], Any] = np.median, subsample: float | int = 1.0, initial_shift=None) -> None:
+        if initial_shift is not None:
+            raise NotImplementedError("VerticalShift(initial_shift=...) is not implemented here.")
+        if not callable(vshift_reduc_func):
+            raise TypeError("vshift_reduc_func must be a callable")
+        self.meta: dict[str, Any] = {
+            "inputs": {"affine": {"vshift_reduc_func": vshift_reduc_func}, "random": {"subsample": subsample, "random_state": None}},
+            "outputs": {},
+        }
+        self._needs_vars = False
+
+    def fit(self, reference_elev, to_be_aligned_elev, inlier_mask=None, bias_vars=None, weights=None, subsample=None, transform=None,
+            crs=None, area_or_point=None, z_name=None, random_state=None, resolution=None, **kwargs: Any) -> "VerticalShift":
+        """``vertical_shift`` (affine.py:721-770): ``float(vshift_reduc_func(ref - tba))`` over the valid (and drawn) pixels."""
+        _check_weights(weights)
+        if bias_vars is not None:
+            raise NotImplementedError("bias_vars is not used by VerticalShift.")
+        if subsample is not None:
+            self.meta["inputs"]["random"]["subsample"] = subsample
+        if random_state is not None:
+            self.meta["inputs"]["random"]["random_state"] = random_state
+        func = self.meta["inputs"]["affine"]["vshift_reduc_func"]
+        logging.info("Running vertical shift coregistration")
+        with DhPlan(reference_elev, to_be_aligned_elev, inlier_mask) as plan:
+            n = _draw(plan, self.meta["inputs"]["random"]["subsample"], self.meta["inputs"]["random"]["random_state"])
+            if func is np.median or func is np.nanmedian:
+                vshift = float(plan.median()[0])
+            else:
+                vshift = float(func(plan.values(coords=False)))
+        self.meta["outputs"]["affine"] = {"shift_z": vshift}
+        self.meta["outputs"]["random"] = {"subsample_final": int(n)}
+        return self
+
+    def apply(self, elev, resolution=None, resample: bool = True, *, bias_vars=None, resampling: str = "bilinear", transform=None, crs=None,
+              z_name: str = "z"):
+        """``elev + shift_z`` in the input dtype (``apply_translation(..., resample=False)``); with ``transform=`` the call returns
+        ``(array, transform)``: a vertical shift leaves the geotransform as it is."""
+        from . import coreg
+
+        if "affine" not in self.meta["outputs"]:
+            raise AssertionError(".fit() does not seem to have been called yet")
+        if bias_vars is not None:
+            raise NotImplementedError("bias_vars is not used by VerticalShift.")
+        res = resolution if resolution is not None else 1.0
+        out = coreg.apply_translation(elev, 0.0, 0.0, self.meta["outputs"]["affine"]["shift_z"], res, resample=False)
+        return _with_transform(out, transform)
+
+    @property
+    def is_affine(self) -> bool:
+        return True
+
+    def to_translations(self) -> tuple[float, float, float]:
+        m = self.to_matrix()
+        return (float(m[0, 3]), float(m[1, 3]), float(m[2, 3]))
+
+    def to_rotations(self) -> tuple[float, float, float]:
+        return (0.0, 0.0, 0.0)
+
+    def to_matrix(self) -> np.ndarray:
+        """4x4 matrix of the vertical shift (affine.py:2098-2104)."""
+        m = np.diag(np.ones(4, dtype=float))
+        m[2, 3] += self.meta["outputs"]["affine"]["shift_z"]
+        return m
+
+
+# ---- CoregPipeline --------------------------------------------------------------------------------------------------------------
+class CoregPipeline(_Step):
+    """A sequential set of co-registration steps (``xdem.coreg.CoregPipeline``, base.py:2880-3190)."""
+
+    def __init__(self, pipeline: list) -> None:
+        self.pipeline = list(pipeline)
+        self.meta: dict[str, Any] = {"inputs": {}, "outputs": {}}
+        self._fit_called = False
+        self._needs_vars = any(getattr(c, "_needs_vars", False) for c in self.pipeline)
+
+    def __repr__(self) -> str:
+        return f"Pipeline: {self.pipeline}"
+
+    def __iter__(self):
+        yield from self.pipeline
+
+    def copy(self) -> "CoregPipeline":
+        """Identical, independent copy: every step copied (base.py:2916-2923)."""
+        new = self.__new__(type(self))
+        new.__dict__ = {k: _copy.deepcopy(v) for k, v in self.__dict__.items() if k != "pipeline"}
+        new.pipeline = [step.copy() for step in self.pipeline]
+        return new
+
+    def __add__(self, other) -> "CoregPipeline":
+        """Append a step or the steps of a list / pipeline (base.py:3166-3180); an ``initial_shift`` of any step is dropped."""
+        other = [other] if _is_step(other) else list(other)
+        steps = self.pipeline + other
+        for m in steps:
+            if "affine" in m.meta["inputs"] and "initial_shift" in m.meta["inputs"]["affine"]:
+                del m.meta["inputs"]["affine"]["initial_shift"]
+        return CoregPipeline(steps)
+
+    def fit(self, reference_elev, to_be_aligned_elev, inlier_mask=None, bias_vars=None, weights=None, subsample=None, transform=None,
+            crs=None, area_or_point=None, z_name=None, random_state=None, **kwargs: Any) -> "CoregPipeline":
+        """Fit every step on the output of the previous step's ``apply`` (base.py:2967-3050); the last step is not applied.
+        ``resolution=`` (keyword) reaches every step's fit and apply, like ``transform``."""
+        if bias_vars is not None:
+            raise NotImplementedError("bias_vars: no step of this package takes bias variables.")
+        argspec = [inspect.getfullargspec(c.__class__) for c in self.pipeline]
+        sub_meta = [c.meta["inputs"]["random"]["subsample"] for c in self.pipeline]
+        sub_is_default = [argspec[i].defaults[argspec[i].args.index("subsample") - 1] == sub_meta[i] for i in range(len(argspec))]
+        if subsample is not None and not all(sub_is_default):
+            warnings.warn(
+                "Subsample argument passed to fit() will override non-default subsample values defined for"
+                " individual steps of the pipeline. To silence this warning: only define 'subsample' in "
+                "either fit(subsample=...) or instantiation e.g., VerticalShift(subsample=...)."
+            )
+            warnings.filterwarnings("ignore", message="Subsample argument passed to*", category=UserWarning)
+        extra = {"resolution": kwargs.pop("resolution")} if "resolution" in kwargs else {}
+        tba_mod = to_be_aligned_elev
+        out_transform = transform
+        for i, step in enumerate(self.pipeline):
+            logging.debug("Running pipeline step: %d / %d", i + 1, len(self.pipeline))
+            step.fit(reference_elev=reference_elev, to_be_aligned_elev=tba_mod, inlier_mask=inlier_mask, transform=out_transform, crs=crs,
+                     z_name=z_name, weights=weights, subsample=subsample, random_state=random_state, **extra, **kwargs)
+            if i != len(self.pipeline) - 1:
+                res = step.apply(elev=tba_mod, transform=out_transform, crs=crs, z_name=z_name, **extra)
+                if out_transform is None:
+                    tba_mod = res
+                else:
+                    tba_mod, out_transform = res
+        self._fit_called = True
+        return self
+
+    def apply(self, elev, bias_vars=None, resample: bool = True, resampling: str = "bilinear", transform=None, crs=None, z_name=None,
+              **kwargs: Any):
+        """Apply the steps in order (base.py:3106-3150).  With ``transform=`` returns ``(array, transform)``, else the array."""
+        if not self._fit_called:
+            raise AssertionError(".fit() does not seem to have been called yet")
+        if bias_vars is not None:
+            raise NotImplementedError("bias_vars: no step of this package takes bias variables.")
+        elev_mod = elev
+        out_transform = transform
+        for step in self.pipeline:
+            res = step.apply(elev=elev_mod, transform=out_transform, crs=crs, z_name=z_name, resample=resample, resampling=resampling,
+                             **kwargs)
+            if out_transform is None:
+                elev_mod = res
+            else:
+                elev_mod, out_transform = res
+        return _with_transform(elev_mod, out_transform)
+
+    @property
+    def is_affine(self) -> bool:
+        return all(c.is_affine for c in self.pipeline)
+
+    def to_matrix(self) -> np.ndarray:
+        """Product of the steps' 4x4 matrices (base.py:3187-3199); a non-affine step raises."""
+        total = np.eye(4)
+        for c in self.pipeline:
+            total = c.to_matrix() @ total
+        return total
+
+    def to_translations(self) -> tuple[float, float, float]:
+        m = self.to_matrix()
+        return (float(m[0, 3]), float(m[1, 3]), float(m[2, 3]))

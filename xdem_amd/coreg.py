@@ -612,6 +612,12 @@ class NuthKaab:
         return self.apply(to_be_aligned_elev, resolution, resample, bias_vars=bias_vars, resampling=resampling, transform=transform,
                           crs=crs, z_name=z_name, **apply_kwargs)
 
+    def __add__(self, other):
+        """``NuthKaab() + other``: a two-step ``CoregPipeline`` (base.py:2008-2019)."""
+        from .biascorr import _pipeline_add
+
+        return _pipeline_add(self, other)
+
     def copy(self) -> "NuthKaab":
         """Identical, independent copy (base.py:1999-2006)."""
         import copy as _copy
@@ -640,3 +646,7 @@ class NuthKaab:
         m[1, 3] += self.meta["outputs"]["affine"]["shift_y"]
         m[2, 3] += self.meta["outputs"]["affine"]["shift_z"]
         return m
+
+
+# Deramp, VerticalShift and pipelines of steps (xdem_amd/biascorr.py), importable from here as upstream's xdem.coreg offers them
+from .biascorr import CoregPipeline, Deramp, VerticalShift, polynomial_2d  # noqa: E402,F401

@@ -126,15 +126,16 @@ class DEM:
                       **kwargs) -> "DEM":
         """Align this DEM to ``reference_elev`` (same grid) with ``coreg_method`` (upstream requires one and names Nuth and
         Kaab as the default in its docstring: ``None`` means ``NuthKaab(subsample=1)`` here).  ``random_state`` seeds the
-        subsampling; ``resample`` (keyword, default True) as upstream; ``bias_vars`` belongs to bias-correction methods, which
-        are not part of this package."""
+        subsampling; ``resample`` (keyword, default True) as upstream.  ``coreg_method``: ``NuthKaab``, ``Deramp``,
+        ``VerticalShift`` or a ``CoregPipeline`` of them; ``bias_vars`` belongs to bias corrections with explicit variables, which are
+        not part of this package."""
         resample = kwargs.pop("resample", True)
         if bias_vars is not None:
             raise NotImplementedError("bias_vars is only used by bias-correction methods (not part of xdem_amd).")
         if random_state is not None:
             kwargs["random_state"] = random_state
         method = coreg_method if coreg_method is not None else _coreg.NuthKaab(subsample=1)
-        if not isinstance(method, _coreg.NuthKaab):
+        if not isinstance(method, (_coreg.NuthKaab, _coreg.Deramp, _coreg.VerticalShift, _coreg.CoregPipeline)):
             raise ValueError("Argument `coreg_method` must be an xdem_amd.coreg instance (e.g. xdem_amd.coreg.NuthKaab()).")
         if reference_elev.shape != self.shape or reference_elev.transform != self.transform:
             raise NotImplementedError("reference and to-be-aligned DEM must share one grid (reprojection is geoutils' job).")
