@@ -348,8 +348,8 @@ int xdemhip_binned_median(xdemhip_ctx* ctx, const void* x, const void* y, int dt
  *  xdemhip_dh_create        valid = inlier & isfinite(ref) & isfinite(tba) (base.py:652-663); *n_valid = its count.
  *  xdemhip_dh_subsample     the random subsample (base.py:577-617): the caller draws `k` distinct RANKS among the valid pixels in
  *                           raster order (xdem_amd.coreg.subsample_ranks), the plan keeps those pixels -- flatnonzero(valid)[ranks] --
- *                           as its selection for every later call; *n_drawn = their number.  Same tile count -> scan -> rank scheme
- *                           as xdemhip_nk_subsample.
+ *                           as its selection for every later call; *n_drawn = their number.  The same tile count -> scan -> rank
+ *                           selection as xdemhip_nk_subsample (one implementation: xdem_amd/csrc/rank_select.h).
  *  xdemhip_dh_poly_moments  least-squares sums of the tensor-product polynomial sum c[i, j] x^i y^j (xdem/fit.py:127-149; x = column,
  *                           y = row_offset + row) over the selected pixels, in normalised coordinates u = (x - cx) / sx, v = (y - cy) / sy,
  *                           cx = sx = (W_global - 1) / 2, cy = sy = (H_global - 1) / 2 (a half-width of 0 counts as 1):

@@ -210,3 +210,53 @@ def test_poly2d_apply_device_tensors():
                     torch.empty_like(t).t().contiguous().t(), np.empty(t.shape, dtype=np.float32)):
         with pytest.raises(ValueError):
             poly2d_apply(t, params, out=bad_out)
+
+
+@pytest.mark.parametrize("shape", [(333, 517), (2101, 2011)])
+def test_nk_and_dh_plans_select_the_same_pixels(shape):
+    """The two subsample entry points share one rank selection: given the same ranks over the same valid pixels, the NK plan's inlier
+    mask and the dh plan's pixel list name the same pixels -- flatnonzero(valid)[ranks], a repeated rank counted once.  333 x 517 is
+    not a multiple of 16 or 4096 pixels; 2101 x 2011 has more than 1024 tiles of 4096, so the tile scan carries over pieces."""
+    from xdem_amd import coreg
+    from xdem_amd.biascorr import DhPlan
+
+    rng = np.random.default_rng(3)
+    ref = (100 + np.cumsum(rng.normal(size=shape), axis=1)).astype(np.float32)
+    tba = (ref + rng.normal(scale=0.1, size=shape)).astype(np.float32)
+    ref[rng.random(shape) < 0.05] = np.nan
+    with coreg.NKPlan(ref, tba, None) as nk0:
+        valid = nk0.aux()[2]   # (the NK rule is the stricter one: as inlier mask it makes both plans' valid pixels the same)
+    ranks = coreg.subsample_ranks(int(valid.sum()), 0.3, 11)
+    ranks = np.concatenate([ranks, ranks[:50], ranks[-7:]])
+    want = np.zeros(valid.size, dtype=bool)
+    want[np.flatnonzero(valid)[ranks]] = True
+    want = want.reshape(shape)
+    with coreg.NKPlan(ref, tba, valid) as nk, DhPlan(ref, tba, valid) as dh:
+        assert nk.n_valid == dh.n_valid == int(valid.sum())
+        assert nk.subsample(ranks) == dh.subsample(ranks) == int(want.sum())
+        _, col, row = dh.values()
+        got = np.zeros(shape, dtype=bool)
+        got[row, col] = True
+        assert np.array_equal(nk.aux()[2], want) and np.array_equal(got, want)
+        assert np.all(np.diff(row * shape[1] + col) > 0)   # (raster order)
+
+
+def test_nk_plan_takes_any_device_mask_and_refuses_other_dtypes():
+    """NKPlan and DhPlan share one input front: a device inlier mask of any integer / bool dtype is converted to uint8, and a CUDA
+    dtype other than float32 / float64 is a ValueError."""
+    import torch
+
+    from xdem_amd import coreg
+
+    rng = np.random.default_rng(5)
+    ref = torch.from_numpy((100 + np.cumsum(rng.normal(size=(64, 80)), axis=1)).astype(np.float32)).cuda()
+    tba = ref + 0.5
+    mask = np.ones((64, 80), dtype=bool)
+    mask[10:20, 30:50] = False
+    with coreg.NKPlan(ref.cpu().numpy(), tba.cpu().numpy(), mask.astype(np.uint8)) as host:
+        want = host.aux()[2]
+    for m in (torch.from_numpy(mask).cuda(), torch.from_numpy(mask.astype(np.int32)).cuda()):
+        with coreg.NKPlan(ref, tba, m) as plan:
+            assert np.array_equal(plan.aux()[2], want)
+    with pytest.raises(ValueError, match="float32 / float64"):
+        coreg.NKPlan(ref.half(), tba.half(), None)

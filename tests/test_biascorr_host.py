@@ -306,3 +306,65 @@ def test_coregister_3d_accepts_the_new_methods(monkeypatch):
     for m in (coreg.Deramp(), coreg.VerticalShift(), coreg.CoregPipeline([coreg.Deramp()])):
         out = a.coregister_3d(b, m, resample=False)
         assert np.all(out.data == 1.0) and seen[-2] == ("fit", type(m).__name__, (2.0, 2.0)) and seen[-1][2] is False
+
+
+@pytest.mark.parametrize("first", ["biascorr", "coreg"])
+def test_coreg_and_biascorr_import_in_either_order(first):
+    """coreg and biascorr share xdem_amd._coregbase and import each other nowhere lazily: either may be imported first."""
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    second = "coreg" if first == "biascorr" else "biascorr"
+    code = (f"import xdem_amd.{first}, xdem_amd.{second}\n"
+            "from xdem_amd import biascorr, coreg\n"
+            "assert coreg.CoregPipeline is biascorr.CoregPipeline and coreg.Deramp is biascorr.Deramp\n"
+            "assert isinstance(coreg.NuthKaab() + coreg.VerticalShift(), biascorr.CoregPipeline)\n")
+    env = dict(os.environ, PYTHONPATH=os.pathsep.join(p for p in (root, os.environ.get("PYTHONPATH")) if p))
+    subprocess.run([sys.executable, "-c", code], cwd=root, env=env, check=True, timeout=300)
+
+
+def test_nuthkaab_is_a_step(monkeypatch):
+    """NuthKaab shares _Step with the other methods: ``+`` gives a two-step pipeline, and fit_and_apply hands
+    ``fit_kwargs={"resolution": ...}`` on to apply."""
+    from xdem_amd import coreg
+    from xdem_amd._coregbase import _Step
+
+    assert isinstance(coreg.NuthKaab(), _Step)
+    pipe = coreg.NuthKaab() + coreg.Deramp()
+    assert isinstance(pipe, coreg.CoregPipeline) and [type(s) for s in pipe] == [coreg.NuthKaab, coreg.Deramp]
+    with pytest.raises(ValueError, match="Incompatible add type"):
+        coreg.NuthKaab() + 1
+    seen = {}
+    monkeypatch.setattr(coreg, "nuth_kaab", lambda ref, tba, inlier, res, **kw: ((1.0, 2.0, 3.0), 7))
+
+    def fake_translation(elev, sx, sy, sz, res, resample=True, ctx=None):
+        seen["apply"] = (sx, sy, sz, res, resample)
+        return elev + sz
+
+    monkeypatch.setattr(coreg, "apply_translation", fake_translation)
+    out = coreg.NuthKaab().fit_and_apply(np.zeros((3, 4), np.float32), np.ones((3, 4), np.float32), fit_kwargs={"resolution": (2.0, 4.0)})
+    assert seen["apply"] == (-1.0, -2.0, 3.0, (2.0, 4.0), True) and np.all(out == 4.0)
+
+
+def test_nuth_kaab_closes_the_plan_when_the_draw_fails(monkeypatch):
+    from xdem_amd import coreg
+
+    closed = []
+
+    class _NKPlan:
+        n_valid = 100
+
+        def __init__(self, *args, **kwargs):
+            pass
+
+        def subsample(self, ranks):
+            raise RuntimeError("draw failed")
+
+        def close(self):
+            closed.append(True)
+
+    monkeypatch.setattr(coreg, "NKPlan", _NKPlan)
+    with pytest.raises(RuntimeError, match="draw failed"):
+        coreg.nuth_kaab(np.zeros((10, 10)), np.zeros((10, 10)), None, (1.0, 1.0), subsample=0.5, random_state=0)
+    assert closed == [True]

@@ -1,0 +1,288 @@
+"""What ``xdem_amd.coreg`` (NuthKaab) and ``xdem_amd.biascorr`` (Deramp, VerticalShift) share: the random subsample of the valid
+pixels, the raster-pair front of their device plans, the plans' lifetime, ``apply_translation``, and the steps' common base with the
+pipeline they form (``xdem.coreg.CoregPipeline``, base.py:2008-2019, 2880-3190).  Both modules re-export what their users import."""
+from __future__ import annotations
+
+import copy as _copy
+import inspect
+import logging
+import warnings
+from typing import Any, NamedTuple
+
+import numpy as np
+
+from . import _lib
+
+NO_VALID = ("There is no valid points common to the input and auxiliary data (bias variables, or "
+            "derivatives required for this method, for example slope, aspect, etc).")
+
+
+# ---- the random subsample ---------------------------------------------------------------------------------------------------------
+def subsample_valid_mask(valid_mask: np.ndarray, subsample: float | int, random_state=None) -> np.ndarray:
+    """Boolean mask of a random subsample of the valid pixels (``_get_subsample_on_valid_mask``, xdem/coreg/base.py:577-617).
+    The draw itself is geoutils' ``subsample_array`` (un-vendored, absent here); its published rule is restated --
+    ``rng = default_rng(random_state)``, ``n = int(subsample * n_valid)`` for 0 < subsample <= 1 else ``int(subsample)``,
+    capped at n_valid, ``rng.choice(flat valid indices, n, replace=False)`` -- **parity unpinned**."""
+    n_valid = int(np.count_nonzero(valid_mask))
+    if subsample == 1 and n_valid > 0:
+        return valid_mask
+    ranks = subsample_ranks(n_valid, subsample, random_state)
+    valids = np.flatnonzero(valid_mask.ravel())
+    out = np.zeros(valid_mask.size, dtype=bool)
+    out[valids[ranks]] = True
+    return out.reshape(valid_mask.shape)
+
+
+def subsample_ranks(n_valid: int, subsample: float | int, random_state=None) -> np.ndarray:
+    """The draw of ``subsample_valid_mask`` as RANKS among the valid pixels: ``rng.choice(valids, n, replace=False)`` is
+    ``valids[rng.choice(len(valids), n, replace=False)]`` -- NumPy draws the positions from the population SIZE and indexes the array
+    with them (same generator stream, same order; CPU test) -- so the ranks need only the count of valid pixels, not the mask:
+    the device turns them into pixels (``NKPlan.subsample``) and the mask stays where it is."""
+    if n_valid == 0:
+        raise ValueError(NO_VALID)
+    if subsample <= 0:
+        raise ValueError("`subsample` must be > 0")
+    npoints = int(subsample * n_valid) if subsample <= 1 else int(subsample)
+    npoints = min(npoints, n_valid)
+    rng = np.random.default_rng(random_state)
+    return rng.choice(n_valid, npoints, replace=False)
+
+
+def draw(plan, subsample, random_state) -> int:
+    """The random subsample of upstream's ``_get_subsample_on_valid_mask`` (base.py:577-617; geoutils' draw restated by
+    ``subsample_ranks``) applied to a device plan (``NKPlan`` / ``DhPlan``); returns the number of pixels the fit uses."""
+    if plan.n_valid == 0:
+        raise ValueError(NO_VALID)
+    if subsample == 1:
+        return plan.n_valid
+    ranks = subsample_ranks(plan.n_valid, subsample, random_state)
+    if ranks.size == plan.n_valid:   # every valid pixel drawn: the whole-raster route covers the same set
+        return plan.n_valid
+    return plan.subsample(ranks)
+
+
+# ---- the device plans' front and lifetime -------------------------------------------------------------------------------------------
+class RasterPair(NamedTuple):
+    ref: int                 # pointers for the library's create call
+    tba: int
+    inlier: int | None
+    dtype: np.dtype
+    code: int                # _lib.F32 / _lib.F64
+    shape: tuple
+    memspace: int            # _lib.HOST / _lib.DEVICE
+    keep: tuple              # the arrays the pointers point into: alive at least until the create call returns
+
+
+def raster_pair(ref, tba, inlier_mask) -> RasterPair:
+    """Two rasters on one grid and an optional inlier mask, as a plan's create call takes them.  ``ref`` / ``tba``: 2-D arrays
+    (promoted to float64 if either is float64, else to float32, when their dtypes differ or are not float), or contiguous 2-D float32 /
+    float64 CUDA tensors of one dtype, never copied (the plan keeps them alive; the current torch stream is synchronised).  The mask
+    goes as uint8: next to device rasters a host mask is uploaded and a device mask converted, on the rasters' device."""
+    if hasattr(ref, "is_cuda"):
+        import torch
+
+        if not (ref.is_cuda and tba.is_cuda and ref.is_contiguous() and tba.is_contiguous() and ref.dtype == tba.dtype
+                and ref.shape == tba.shape and ref.dim() == 2 and ref.dtype in (torch.float32, torch.float64)):
+            raise ValueError("device inputs must be contiguous 2D float32 / float64 CUDA tensors of the same shape and dtype")
+        inl = None
+        if inlier_mask is not None:
+            inl = inlier_mask if hasattr(inlier_mask, "is_cuda") else torch.from_numpy(np.ascontiguousarray(inlier_mask, dtype=np.uint8))
+            inl = inl.to(device=ref.device, dtype=torch.uint8).contiguous()
+        torch.cuda.current_stream(ref.device).synchronize()
+        dtype = np.dtype(np.float32 if ref.dtype == torch.float32 else np.float64)
+        return RasterPair(ref.data_ptr(), tba.data_ptr(), inl.data_ptr() if inl is not None else None, dtype,
+                          _lib.F32 if dtype == np.float32 else _lib.F64, tuple(ref.shape), _lib.DEVICE, (ref, tba, inl))
+    ref, tba = np.ascontiguousarray(ref), np.ascontiguousarray(tba)
+    if ref.shape != tba.shape or ref.ndim != 2:
+        raise ValueError("ref and tba must be 2D arrays of the same shape")
+    if ref.dtype != tba.dtype or ref.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+        dt = np.float64 if np.float64 in (ref.dtype, tba.dtype) else np.float32
+        ref, tba = ref.astype(dt), tba.astype(dt)
+    inl = None if inlier_mask is None else np.ascontiguousarray(inlier_mask, dtype=np.uint8)
+    return RasterPair(ref.ctypes.data, tba.ctypes.data, inl.ctypes.data if inl is not None else None, ref.dtype,
+                      _lib.F32 if ref.dtype == np.float32 else _lib.F64, ref.shape, _lib.HOST, (ref, tba, inl))
+
+
+class _Plan:
+    """Lifetime of a device plan: ``close`` (also on leaving a ``with`` block, and at collection) calls the library's ``_DESTROY``."""
+
+    _DESTROY = ""
+
+    def close(self) -> None:
+        if getattr(self, "handle", None):
+            if getattr(self.ctx, "handle", None):   # (a context that is already gone took its plans with it)
+                getattr(self.ctx._L, self._DESTROY)(self.handle)
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def apply_translation(elev: np.ndarray, shift_x: float, shift_y: float, shift_z: float, resolution, resample: bool = True,
+                      ctx: _lib.Context | None = None) -> np.ndarray:
+    """Apply a pure translation to a DEM array (``Coreg.apply`` for ``shift_x / shift_y / shift_z``): with
+    ``resample=True`` the shifted DEM is bilinearly resampled onto its original grid
+    (``_apply_matrix_rst`` case 2 + ``_reproject_horizontal_shift_samecrs``, xdem/coreg/base.py:1522-1570, 1615-1655):
+    ``out(r, c) = elev(r + shift_y / res_y, c - shift_x / res_x) + shift_z``.  Without resampling only ``shift_z`` is
+    added (the reference then just moves the geotransform)."""
+    arr = np.ascontiguousarray(elev.filled(np.nan) if isinstance(elev, np.ma.MaskedArray) else elev)
+    if arr.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+        arr = arr.astype(np.float32)
+    from .spatialstats import _count_finite   # (np.isfinite over the raster on the library's host threads: 7 ms against 0.1 s at 20000^2)
+
+    if _count_finite(arr)[0] == 0:
+        raise ValueError("Input DEM has all nans.")
+    if not resample:
+        return arr + arr.dtype.type(shift_z)
+    res = (float(resolution), float(resolution)) if np.isscalar(resolution) else (float(resolution[0]), float(resolution[1]))
+    ctx = ctx or _lib.default_context()
+    out = np.empty_like(arr)
+    ctx.check(ctx._L.xdemhip_shift_bilinear(ctx.handle, arr.ctypes.data, _lib.F32 if arr.dtype == np.float32 else _lib.F64,
+                                            arr.shape[0], arr.shape[1], float(shift_y) / res[1], -float(shift_x) / res[0],
+                                            float(shift_z), out.ctypes.data, _lib.HOST))
+    return out
+
+
+# ---- the coregistration steps --------------------------------------------------------------------------------------------------
+class _Step:
+    """What NuthKaab, Deramp, VerticalShift and CoregPipeline share with ``xdem.coreg.Coreg``: copy, ``+``, fit_and_apply."""
+
+    def copy(self):
+        """Identical, independent copy (base.py:1999-2006)."""
+        new = self.__new__(type(self))
+        new.__dict__ = {k: _copy.deepcopy(v) for k, v in self.__dict__.items()}
+        return new
+
+    def __add__(self, other) -> "CoregPipeline":
+        """``Coreg.__add__`` (base.py:2008-2019): a two-step pipeline; an ``initial_shift`` of either step is dropped."""
+        if not isinstance(other, _Step):
+            raise ValueError(f"Incompatible add type: {type(other)}. Expected 'Coreg' subclass")
+        for m in (self, other):
+            if "affine" in m.meta["inputs"] and "initial_shift" in m.meta["inputs"]["affine"]:
+                del m.meta["inputs"]["affine"]["initial_shift"]
+        return CoregPipeline([self, other])
+
+    def fit_and_apply(self, reference_elev, to_be_aligned_elev, inlier_mask=None, bias_vars=None, weights=None, subsample=None,
+                      transform=None, crs=None, area_or_point=None, z_name: str = "z", resample: bool = True,
+                      resampling: str = "bilinear", random_state=None, fit_kwargs=None, apply_kwargs=None):
+        """``Coreg.fit_and_apply`` (base.py:2482-2590): fit, then apply to the to-be-aligned elevations."""
+        fit_kwargs = dict(fit_kwargs or {})
+        apply_kwargs = dict(apply_kwargs or {})
+        self.fit(reference_elev, to_be_aligned_elev, inlier_mask=inlier_mask, bias_vars=bias_vars, weights=weights, subsample=subsample,
+                 transform=transform, crs=crs, area_or_point=area_or_point, z_name=z_name, random_state=random_state, **fit_kwargs)
+        if "resolution" in fit_kwargs:
+            apply_kwargs.setdefault("resolution", fit_kwargs["resolution"])
+        return self.apply(to_be_aligned_elev, bias_vars=bias_vars, resample=resample, resampling=resampling, transform=transform, crs=crs,
+                          z_name=z_name, **apply_kwargs)
+
+
+def _with_transform(out, transform):
+    return out if transform is None else (out, transform)
+
+
+# ---- CoregPipeline --------------------------------------------------------------------------------------------------------------
+class CoregPipeline(_Step):
+    """A sequential set of co-registration steps (``xdem.coreg.CoregPipeline``, base.py:2880-3190)."""
+
+    def __init__(self, pipeline: list) -> None:
+        self.pipeline = list(pipeline)
+        self.meta: dict[str, Any] = {"inputs": {}, "outputs": {}}
+        self._fit_called = False
+        self._needs_vars = any(getattr(c, "_needs_vars", False) for c in self.pipeline)
+
+    def __repr__(self) -> str:
+        return f"Pipeline: {self.pipeline}"
+
+    def __iter__(self):
+        yield from self.pipeline
+
+    def copy(self) -> "CoregPipeline":
+        """Identical, independent copy: every step copied (base.py:2916-2923)."""
+        new = self.__new__(type(self))
+        new.__dict__ = {k: _copy.deepcopy(v) for k, v in self.__dict__.items() if k != "pipeline"}
+        new.pipeline = [step.copy() for step in self.pipeline]
+        return new
+
+    def __add__(self, other) -> "CoregPipeline":
+        """Append a step or the steps of a list / pipeline (base.py:3166-3180); an ``initial_shift`` of any step is dropped."""
+        other = [other] if isinstance(other, _Step) else list(other)
+        steps = self.pipeline + other
+        for m in steps:
+            if "affine" in m.meta["inputs"] and "initial_shift" in m.meta["inputs"]["affine"]:
+                del m.meta["inputs"]["affine"]["initial_shift"]
+        return CoregPipeline(steps)
+
+    def fit(self, reference_elev, to_be_aligned_elev, inlier_mask=None, bias_vars=None, weights=None, subsample=None, transform=None,
+            crs=None, area_or_point=None, z_name=None, random_state=None, **kwargs: Any) -> "CoregPipeline":
+        """Fit every step on the output of the previous step's ``apply`` (base.py:2967-3050); the last step is not applied.
+        ``resolution=`` (keyword) reaches every step's fit and apply, like ``transform``."""
+        if bias_vars is not None:
+            raise NotImplementedError("bias_vars: no step of this package takes bias variables.")
+        argspec = [inspect.getfullargspec(c.__class__) for c in self.pipeline]
+        sub_meta = [c.meta["inputs"]["random"]["subsample"] for c in self.pipeline]
+        sub_is_default = [argspec[i].defaults[argspec[i].args.index("subsample") - 1] == sub_meta[i] for i in range(len(argspec))]
+        if subsample is not None and not all(sub_is_default):
+            warnings.warn(
+                "Subsample argument passed to fit() will override non-default subsample values defined for"
+                " individual steps of the pipeline. To silence this warning: only define 'subsample' in "
+                "either fit(subsample=...) or instantiation e.g., VerticalShift(subsample=...)."
+            )
+            warnings.filterwarnings("ignore", message="Subsample argument passed to*", category=UserWarning)
+        extra = {"resolution": kwargs.pop("resolution")} if "resolution" in kwargs else {}
+        tba_mod = to_be_aligned_elev
+        out_transform = transform
+        for i, step in enumerate(self.pipeline):
+            logging.debug("Running pipeline step: %d / %d", i + 1, len(self.pipeline))
+            step.fit(reference_elev=reference_elev, to_be_aligned_elev=tba_mod, inlier_mask=inlier_mask, transform=out_transform, crs=crs,
+                     z_name=z_name, weights=weights, subsample=subsample, random_state=random_state, **extra, **kwargs)
+            if i != len(self.pipeline) - 1:
+                res = step.apply(elev=tba_mod, transform=out_transform, crs=crs, z_name=z_name, **extra)
+                if out_transform is None:
+                    tba_mod = res
+                else:
+                    tba_mod, out_transform = res
+        self._fit_called = True
+        return self
+
+    def apply(self, elev, bias_vars=None, resample: bool = True, resampling: str = "bilinear", transform=None, crs=None, z_name=None,
+              **kwargs: Any):
+        """Apply the steps in order (base.py:3106-3150).  With ``transform=`` returns ``(array, transform)``, else the array."""
+        if not self._fit_called:
+            raise AssertionError(".fit() does not seem to have been called yet")
+        if bias_vars is not None:
+            raise NotImplementedError("bias_vars: no step of this package takes bias variables.")
+        elev_mod = elev
+        out_transform = transform
+        for step in self.pipeline:
+            res = step.apply(elev=elev_mod, transform=out_transform, crs=crs, z_name=z_name, resample=resample, resampling=resampling,
+                             **kwargs)
+            if out_transform is None:
+                elev_mod = res
+            else:
+                elev_mod, out_transform = res
+        return _with_transform(elev_mod, out_transform)
+
+    @property
+    def is_affine(self) -> bool:
+        return all(c.is_affine for c in self.pipeline)
+
+    def to_matrix(self) -> np.ndarray:
+        """Product of the steps' 4x4 matrices (base.py:3187-3199); a non-affine step raises."""
+        total = np.eye(4)
+        for c in self.pipeline:
+            total = c.to_matrix() @ total
+        return total
+
+    def to_translations(self) -> tuple[float, float, float]:
+        m = self.to_matrix()
+        return (float(m[0, 3]), float(m[1, 3]), float(m[2, 3]))

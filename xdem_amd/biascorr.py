@@ -12,27 +12,24 @@ Every pass over the grids runs in ``csrc/biascorr.hip`` through a dh plan (``xde
   coordinates from the device and runs on the host exactly as upstream calls it (``base.py:978-985``); ``apply`` with a custom
   ``fit_func`` evaluates it on the host too -- that route is slow and exists for compatibility.
 * ``VerticalShift`` with ``np.median`` / ``np.nanmedian`` selects the exact median of dh on the device; any other callable gets dh.
-* ``CoregPipeline`` chains the steps' public ``fit`` / ``apply`` as upstream does; rasters go back to the host between steps.
+* ``CoregPipeline`` (``xdem_amd._coregbase``, shared with NuthKaab) chains the steps' public ``fit`` / ``apply`` as upstream does; rasters
+  go back to the host between steps.
 
 Output dtype of ``apply`` = input dtype (float32 in, float32 out -- upstream's final cast; float64 in: ``elev + corr`` in float64).
 """
 from __future__ import annotations
 
-import copy as _copy
 import ctypes
-import inspect
 import logging
 import math
-import warnings
 from typing import Any, Callable
 
 import numpy as np
 import scipy.optimize
 
 from . import _lib
+from ._coregbase import CoregPipeline, _Plan, _Step, _with_transform, apply_translation, draw, raster_pair  # noqa: F401
 
-_NO_VALID = ("There is no valid points common to the input and auxiliary data (bias variables, or "
-             "derivatives required for this method, for example slope, aspect, etc).")
 MAX_DEVICE_ORDER = 5
 
 
@@ -54,10 +51,12 @@ def _host_array(a):
 
 
 # ---- the device plan --------------------------------------------------------------------------------------------------------
-class DhPlan:
+class DhPlan(_Plan):
     """Device-resident elevation difference of two rasters (``xdemhip_dh_plan``): valid mask, optional random subsample, and the
     reductions Deramp / VerticalShift need.  ``ref`` / ``tba``: 2-D NumPy arrays, or contiguous CUDA tensors of one dtype (kept alive by
     the plan, never copied)."""
+
+    _DESTROY = "xdemhip_dh_destroy"
 
     def __init__(self, ref, tba, inlier_mask=None, ctx: _lib.Context | None = None):
         self.ctx = ctx or _lib.default_context()
@@ -65,40 +64,16 @@ class DhPlan:
         self.drawn = False
         self.ctx.adopt(self)
         h, nv = ctypes.c_void_p(), ctypes.c_int64()
-        L = self.ctx._L
-        if hasattr(ref, "is_cuda"):
-            import torch
-
-            if not (ref.is_cuda and tba.is_cuda and ref.is_contiguous() and tba.is_contiguous() and ref.dtype == tba.dtype
-                    and ref.shape == tba.shape and ref.dim() == 2 and ref.dtype in (torch.float32, torch.float64)):
-                raise ValueError("device inputs must be contiguous 2D float32 / float64 CUDA tensors of the same shape and dtype")
-            self.dtype = np.dtype(np.float32 if ref.dtype == torch.float32 else np.float64)
-            self.shape = tuple(ref.shape)
-            inl = None
-            if inlier_mask is not None:
-                inl = inlier_mask if hasattr(inlier_mask, "is_cuda") else torch.from_numpy(np.ascontiguousarray(inlier_mask, dtype=np.uint8))
-                inl = inl.to(device=ref.device, dtype=torch.uint8).contiguous()
-            self._keep = (ref, tba, inl)
-            torch.cuda.current_stream(ref.device).synchronize()
-            rc = L.xdemhip_dh_create(self.ctx.handle, ref.data_ptr(), tba.data_ptr(), inl.data_ptr() if inl is not None else None,
-                                     _lib.F32 if self.dtype == np.float32 else _lib.F64, self.shape[0], self.shape[1], _lib.DEVICE,
-                                     ctypes.byref(h), ctypes.byref(nv))
-        else:
-            ref, tba = np.ascontiguousarray(_host_array(ref)), np.ascontiguousarray(_host_array(tba))
-            if ref.shape != tba.shape or ref.ndim != 2:
-                raise ValueError("ref and tba must be 2D arrays of the same shape")
-            if ref.dtype != tba.dtype or ref.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
-                dt = np.float64 if np.float64 in (ref.dtype, tba.dtype) else np.float32
-                ref, tba = ref.astype(dt), tba.astype(dt)
-            self.dtype = ref.dtype
-            self.shape = ref.shape
-            inl = None if inlier_mask is None else np.ascontiguousarray(_host_array(inlier_mask), dtype=np.uint8)
-            if inl is not None and inl.shape != ref.shape:
-                raise ValueError("inlier_mask must have the shape of the rasters")
-            rc = L.xdemhip_dh_create(self.ctx.handle, ref.ctypes.data, tba.ctypes.data, inl.ctypes.data if inl is not None else None,
-                                     _lib.F32 if self.dtype == np.float32 else _lib.F64, ref.shape[0], ref.shape[1], _lib.HOST,
-                                     ctypes.byref(h), ctypes.byref(nv))
-        self.ctx.check(rc)
+        if not hasattr(ref, "is_cuda"):
+            ref, tba, inlier_mask = _host_array(ref), _host_array(tba), _host_array(inlier_mask)
+        p = raster_pair(ref, tba, inlier_mask)
+        if p.memspace == _lib.HOST and p.keep[2] is not None and p.keep[2].shape != p.shape:
+            raise ValueError("inlier_mask must have the shape of the rasters")
+        self.dtype, self.shape = p.dtype, p.shape
+        if p.memspace == _lib.DEVICE:
+            self._keep = p.keep
+        self.ctx.check(self.ctx._L.xdemhip_dh_create(self.ctx.handle, p.ref, p.tba, p.inlier, p.code, p.shape[0], p.shape[1], p.memspace,
+                                                     ctypes.byref(h), ctypes.byref(nv)))
         self.handle = h
         self.n_valid = int(nv.value)
         self.n_selected = self.n_valid
@@ -145,40 +120,6 @@ class DhPlan:
         if int(cnt.value) != k:
             raise _lib.XdemHipError(f"xdemhip_dh_values returned {cnt.value} values, expected {k}")
         return (dh, col, row) if coords else dh
-
-    def close(self) -> None:
-        if getattr(self, "handle", None):
-            if getattr(self.ctx, "handle", None):
-                self.ctx._L.xdemhip_dh_destroy(self.handle)
-            self.handle = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def __del__(self):  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-def _draw(plan: DhPlan, subsample, random_state) -> int:
-    """The random subsample of upstream's ``_get_subsample_on_valid_mask`` (base.py:577-617; geoutils' draw restated by
-    ``xdem_amd.coreg.subsample_ranks``) applied to the plan; returns the number of pixels the fit uses."""
-    from .coreg import subsample_ranks
-
-    if plan.n_valid == 0:
-        raise ValueError(_NO_VALID)
-    if subsample == 1:
-        return plan.n_valid
-    ranks = subsample_ranks(plan.n_valid, subsample, random_state)
-    if ranks.size == plan.n_valid:   # every valid pixel drawn: the whole-raster route covers the same set
-        return plan.n_valid
-    return plan.subsample(ranks)
 
 
 # ---- polynomial algebra on the host --------------------------------------------------------------------------------------------
@@ -266,53 +207,6 @@ def poly2d_apply(elev, params, row_offset: int = 0, ctx: _lib.Context | None = N
     return res
 
 
-# ---- shared plumbing of the three classes --------------------------------------------------------------------------------------
-class _Step:
-    """What Deramp, VerticalShift and CoregPipeline share with ``xdem.coreg.Coreg``: copy, ``+``, fit_and_apply."""
-
-    def copy(self):
-        """Identical, independent copy (base.py:1999-2006)."""
-        new = self.__new__(type(self))
-        new.__dict__ = {k: _copy.deepcopy(v) for k, v in self.__dict__.items()}
-        return new
-
-    def __add__(self, other) -> "CoregPipeline":
-        return _pipeline_add(self, other)
-
-    def fit_and_apply(self, reference_elev, to_be_aligned_elev, inlier_mask=None, bias_vars=None, weights=None, subsample=None,
-                      transform=None, crs=None, area_or_point=None, z_name: str = "z", resample: bool = True,
-                      resampling: str = "bilinear", random_state=None, fit_kwargs=None, apply_kwargs=None):
-        """``Coreg.fit_and_apply`` (base.py:2482-2590): fit, then apply to the to-be-aligned elevations."""
-        fit_kwargs = dict(fit_kwargs or {})
-        apply_kwargs = dict(apply_kwargs or {})
-        self.fit(reference_elev, to_be_aligned_elev, inlier_mask=inlier_mask, bias_vars=bias_vars, weights=weights, subsample=subsample,
-                 transform=transform, crs=crs, area_or_point=area_or_point, z_name=z_name, random_state=random_state, **fit_kwargs)
-        if "resolution" in fit_kwargs:
-            apply_kwargs.setdefault("resolution", fit_kwargs["resolution"])
-        return self.apply(to_be_aligned_elev, bias_vars=bias_vars, resample=resample, resampling=resampling, transform=transform, crs=crs,
-                          z_name=z_name, **apply_kwargs)
-
-
-def _is_step(obj) -> bool:
-    from .coreg import NuthKaab
-
-    return isinstance(obj, (NuthKaab, _Step))
-
-
-def _pipeline_add(a, b) -> "CoregPipeline":
-    """``Coreg.__add__`` (base.py:2008-2019): a two-step pipeline; an ``initial_shift`` of either step is dropped."""
-    if not _is_step(b):
-        raise ValueError(f"Incompatible add type: {type(b)}. Expected 'Coreg' subclass")
-    for m in (a, b):
-        if "affine" in m.meta["inputs"] and "initial_shift" in m.meta["inputs"]["affine"]:
-            del m.meta["inputs"]["affine"]["initial_shift"]
-    return CoregPipeline([a, b])
-
-
-def _with_transform(out, transform):
-    return out if transform is None else (out, transform)
-
-
 def _check_weights(weights) -> None:
     if weights is not None:
         raise NotImplementedError("Weights have not yet been implemented")
@@ -367,7 +261,7 @@ class Deramp(_Step):
         if self._device_route() and order > MAX_DEVICE_ORDER:
             raise NotImplementedError(f"Deramp: poly_order 0..{MAX_DEVICE_ORDER} on the device, got {order}")
         with DhPlan(reference_elev, to_be_aligned_elev, inlier_mask) as plan:
-            n = _draw(plan, self.meta["inputs"]["random"]["subsample"], self.meta["inputs"]["random"]["random_state"])
+            n = draw(plan, self.meta["inputs"]["random"]["subsample"], self.meta["inputs"]["random"]["random_state"])
             if n < n_params:   # (what curve_fit raises for fewer points than parameters)
                 raise TypeError(f"Improper input: func input vector length N={n_params} must not exceed func output vector length M={n}")
             logging.debug("Estimating a 2D polynomial of order %d on %d points.", order, n)
@@ -444,7 +338,7 @@ class VerticalShift(_Step):
         func = self.meta["inputs"]["affine"]["vshift_reduc_func"]
         logging.info("Running vertical shift coregistration")
         with DhPlan(reference_elev, to_be_aligned_elev, inlier_mask) as plan:
-            n = _draw(plan, self.meta["inputs"]["random"]["subsample"], self.meta["inputs"]["random"]["random_state"])
+            n = draw(plan, self.meta["inputs"]["random"]["subsample"], self.meta["inputs"]["random"]["random_state"])
             if func is np.median or func is np.nanmedian:
                 vshift = float(plan.median()[0])
             else:
@@ -457,14 +351,12 @@ class VerticalShift(_Step):
               z_name: str = "z"):
         """``elev + shift_z`` in the input dtype (``apply_translation(..., resample=False)``); with ``transform=`` the call returns
         ``(array, transform)``: a vertical shift leaves the geotransform as it is."""
-        from . import coreg
-
         if "affine" not in self.meta["outputs"]:
             raise AssertionError(".fit() does not seem to have been called yet")
         if bias_vars is not None:
             raise NotImplementedError("bias_vars is not used by VerticalShift.")
         res = resolution if resolution is not None else 1.0
-        out = coreg.apply_translation(elev, 0.0, 0.0, self.meta["outputs"]["affine"]["shift_z"], res, resample=False)
+        out = apply_translation(elev, 0.0, 0.0, self.meta["outputs"]["affine"]["shift_z"], res, resample=False)
         return _with_transform(out, transform)
 
     @property
@@ -483,101 +375,3 @@ class VerticalShift(_Step):
         m = np.diag(np.ones(4, dtype=float))
         m[2, 3] += self.meta["outputs"]["affine"]["shift_z"]
         return m
-
-
-# ---- CoregPipeline --------------------------------------------------------------------------------------------------------------
-class CoregPipeline(_Step):
-    """A sequential set of co-registration steps (``xdem.coreg.CoregPipeline``, base.py:2880-3190)."""
-
-    def __init__(self, pipeline: list) -> None:
-        self.pipeline = list(pipeline)
-        self.meta: dict[str, Any] = {"inputs": {}, "outputs": {}}
-        self._fit_called = False
-        self._needs_vars = any(getattr(c, "_needs_vars", False) for c in self.pipeline)
-
-    def __repr__(self) -> str:
-        return f"Pipeline: {self.pipeline}"
-
-    def __iter__(self):
-        yield from self.pipeline
-
-    def copy(self) -> "CoregPipeline":
-        """Identical, independent copy: every step copied (base.py:2916-2923)."""
-        new = self.__new__(type(self))
-        new.__dict__ = {k: _copy.deepcopy(v) for k, v in self.__dict__.items() if k != "pipeline"}
-        new.pipeline = [step.copy() for step in self.pipeline]
-        return new
-
-    def __add__(self, other) -> "CoregPipeline":
-        """Append a step or the steps of a list / pipeline (base.py:3166-3180); an ``initial_shift`` of any step is dropped."""
-        other = [other] if _is_step(other) else list(other)
-        steps = self.pipeline + other
-        for m in steps:
-            if "affine" in m.meta["inputs"] and "initial_shift" in m.meta["inputs"]["affine"]:
-                del m.meta["inputs"]["affine"]["initial_shift"]
-        return CoregPipeline(steps)
-
-    def fit(self, reference_elev, to_be_aligned_elev, inlier_mask=None, bias_vars=None, weights=None, subsample=None, transform=None,
-            crs=None, area_or_point=None, z_name=None, random_state=None, **kwargs: Any) -> "CoregPipeline":
-        """Fit every step on the output of the previous step's ``apply`` (base.py:2967-3050); the last step is not applied.
-        ``resolution=`` (keyword) reaches every step's fit and apply, like ``transform``."""
-        if bias_vars is not None:
-            raise NotImplementedError("bias_vars: no step of this package takes bias variables.")
-        argspec = [inspect.getfullargspec(c.__class__) for c in self.pipeline]
-        sub_meta = [c.meta["inputs"]["random"]["subsample"] for c in self.pipeline]
-        sub_is_default = [argspec[i].defaults[argspec[i].args.index("subsample") - 1] == sub_meta[i] for i in range(len(argspec))]
-        if subsample is not None and not all(sub_is_default):
-            warnings.warn(
-                "Subsample argument passed to fit() will override non-default subsample values defined for"
-                " individual steps of the pipeline. To silence this warning: only define 'subsample' in "
-                "either fit(subsample=...) or instantiation e.g., VerticalShift(subsample=...)."
-            )
-            warnings.filterwarnings("ignore", message="Subsample argument passed to*", category=UserWarning)
-        extra = {"resolution": kwargs.pop("resolution")} if "resolution" in kwargs else {}
-        tba_mod = to_be_aligned_elev
-        out_transform = transform
-        for i, step in enumerate(self.pipeline):
-            logging.debug("Running pipeline step: %d / %d", i + 1, len(self.pipeline))
-            step.fit(reference_elev=reference_elev, to_be_aligned_elev=tba_mod, inlier_mask=inlier_mask, transform=out_transform, crs=crs,
-                     z_name=z_name, weights=weights, subsample=subsample, random_state=random_state, **extra, **kwargs)
-            if i != len(self.pipeline) - 1:
-                res = step.apply(elev=tba_mod, transform=out_transform, crs=crs, z_name=z_name, **extra)
-                if out_transform is None:
-                    tba_mod = res
-                else:
-                    tba_mod, out_transform = res
-        self._fit_called = True
-        return self
-
-    def apply(self, elev, bias_vars=None, resample: bool = True, resampling: str = "bilinear", transform=None, crs=None, z_name=None,
-              **kwargs: Any):
-        """Apply the steps in order (base.py:3106-3150).  With ``transform=`` returns ``(array, transform)``, else the array."""
-        if not self._fit_called:
-            raise AssertionError(".fit() does not seem to have been called yet")
-        if bias_vars is not None:
-            raise NotImplementedError("bias_vars: no step of this package takes bias variables.")
-        elev_mod = elev
-        out_transform = transform
-        for step in self.pipeline:
-            res = step.apply(elev=elev_mod, transform=out_transform, crs=crs, z_name=z_name, resample=resample, resampling=resampling,
-                             **kwargs)
-            if out_transform is None:
-                elev_mod = res
-            else:
-                elev_mod, out_transform = res
-        return _with_transform(elev_mod, out_transform)
-
-    @property
-    def is_affine(self) -> bool:
-        return all(c.is_affine for c in self.pipeline)
-
-    def to_matrix(self) -> np.ndarray:
-        """Product of the steps' 4x4 matrices (base.py:3187-3199); a non-affine step raises."""
-        total = np.eye(4)
-        for c in self.pipeline:
-            total = c.to_matrix() @ total
-        return total
-
-    def to_translations(self) -> tuple[float, float, float]:
-        m = self.to_matrix()
-        return (float(m[0, 3]), float(m[1, 3]), float(m[2, 3]))

@@ -24,6 +24,9 @@ from typing import Any, Callable
 import numpy as np
 
 from . import _lib
+from ._coregbase import NO_VALID, CoregPipeline, _Plan, _Step, apply_translation, draw, raster_pair  # noqa: F401
+from ._coregbase import subsample_ranks, subsample_valid_mask  # noqa: F401
+from .biascorr import Deramp, VerticalShift, polynomial_2d  # noqa: F401  (upstream's xdem.coreg offers them here)
 
 
 def _nuth_kaab_fit_func(xx, *params):
@@ -50,8 +53,10 @@ class HaloTooSmall(_lib.XdemHipError):
     deeper halo (``xdem_amd.dist.nuth_kaab_row_blocks`` does)."""
 
 
-class NKPlan:
+class NKPlan(_Plan):
     """Device-resident state of one fit (``xdemhip_nk_plan``)."""
+
+    _DESTROY = "xdemhip_nk_destroy"
 
     def __init__(self, ref: np.ndarray, tba: np.ndarray, inlier_mask: np.ndarray | None, ctx: _lib.Context | None = None,
                  group=None, block: tuple[int, int, int, int, int] | None = None):
@@ -82,58 +87,25 @@ class NKPlan:
             raise
 
     def _create(self, ref, tba, inlier_mask, group, block) -> None:
-        h = ctypes.c_void_p()
-        nv = ctypes.c_int64()
-        L = self.ctx._L
+        h, nv = ctypes.c_void_p(), ctypes.c_int64()
         if block is not None:
             if group is not None:
                 self.ctx.set_allreduce(group)  # (the creation pass already counts the valid pixels globally)
             H, rb, re_, ht, hb = (int(v) for v in block)
-
-            def create(rp, tp, ip, dt, nrows, W, space):
-                if nrows != (re_ - rb) + ht + hb:
-                    raise ValueError(f"block arrays hold {nrows} rows, expected {(re_ - rb) + ht + hb}")
-                return L.xdemhip_nk_create_block(self.ctx.handle, rp, tp, ip, dt, H, W, rb, re_, ht, hb, space, ctypes.byref(h),
-                                                 ctypes.byref(nv))
+        p = raster_pair(ref, tba, inlier_mask)
+        self.dtype, self.shape = p.dtype, p.shape
+        if p.memspace == _lib.DEVICE:
+            self._keep = p.keep
+        L = self.ctx._L
+        if block is not None:
+            if p.shape[0] != (re_ - rb) + ht + hb:
+                raise ValueError(f"block arrays hold {p.shape[0]} rows, expected {(re_ - rb) + ht + hb}")
+            rc = L.xdemhip_nk_create_block(self.ctx.handle, p.ref, p.tba, p.inlier, p.code, H, p.shape[1], rb, re_, ht, hb, p.memspace,
+                                           ctypes.byref(h), ctypes.byref(nv))
         else:
-            def create(rp, tp, ip, dt, nrows, W, space):
-                return L.xdemhip_nk_create(self.ctx.handle, rp, tp, ip, dt, nrows, W, space, ctypes.byref(h), ctypes.byref(nv))
-        if hasattr(ref, "is_cuda"):
-            # device-resident rasters (torch CUDA/HIP tensors, same dtype, contiguous): no host copies; the caller keeps them alive
-            if not (ref.is_cuda and tba.is_cuda and ref.is_contiguous() and tba.is_contiguous() and ref.dtype == tba.dtype
-                    and ref.shape == tba.shape and ref.dim() == 2):
-                raise ValueError("device inputs must be contiguous 2D CUDA tensors of the same shape and dtype")
-            import torch
-
-            self.dtype = np.dtype({torch.float32: np.float32, torch.float64: np.float64}[ref.dtype])
-            self.shape = tuple(ref.shape)
-            if inlier_mask is not None and not hasattr(inlier_mask, "is_cuda"):
-                # (a host mask next to device rasters, e.g. the random subsample drawn by nuth_kaab)
-                inlier_mask = torch.from_numpy(np.ascontiguousarray(inlier_mask, dtype=np.uint8)).to(ref.device)
-            self._keep = (ref, tba, inlier_mask)
-            inl_ptr = None
-            if inlier_mask is not None:
-                if not (inlier_mask.is_cuda and inlier_mask.dtype == torch.uint8 and inlier_mask.is_contiguous()):
-                    raise ValueError("device inlier mask must be a contiguous uint8 CUDA tensor")
-                inl_ptr = inlier_mask.data_ptr()
-            torch.cuda.current_stream(ref.device).synchronize()
-            self.ctx.check(create(ref.data_ptr(), tba.data_ptr(), inl_ptr, _lib.F32 if self.dtype == np.float32 else _lib.F64,
-                                  self.shape[0], self.shape[1], _lib.DEVICE))
-        else:
-            ref = np.ascontiguousarray(ref)
-            tba = np.ascontiguousarray(tba)
-            if ref.shape != tba.shape or ref.ndim != 2:
-                raise ValueError("ref and tba must be 2D arrays of the same shape")
-            if ref.dtype != tba.dtype or ref.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
-                dt = np.float64 if np.float64 in (ref.dtype, tba.dtype) else np.float32
-                ref, tba = ref.astype(dt), tba.astype(dt)
-            self.dtype = ref.dtype
-            self.shape = ref.shape
-            inl = None
-            if inlier_mask is not None:
-                inl = np.ascontiguousarray(inlier_mask, dtype=np.uint8)
-            self.ctx.check(create(ref.ctypes.data, tba.ctypes.data, inl.ctypes.data if inl is not None else None,
-                                  _lib.F32 if self.dtype == np.float32 else _lib.F64, ref.shape[0], ref.shape[1], _lib.HOST))
+            rc = L.xdemhip_nk_create(self.ctx.handle, p.ref, p.tba, p.inlier, p.code, p.shape[0], p.shape[1], p.memspace, ctypes.byref(h),
+                                     ctypes.byref(nv))
+        self.ctx.check(rc)
         self.handle = h
         self.n_valid = int(nv.value)
         self.group = group
@@ -272,18 +244,10 @@ class NKPlan:
         return self.n_valid
 
     def close(self) -> None:
-        if getattr(self, "handle", None):
-            if getattr(self.ctx, "handle", None):   # (a context that is already gone took its plans with it)
-                self.ctx._L.xdemhip_nk_destroy(self.handle)
-                if getattr(self, "group", None) is not None:
-                    self.ctx.set_allreduce(None)
-            self.handle = None
-
-    def __del__(self):  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
+        hooked = getattr(self, "handle", None) and getattr(self.ctx, "handle", None) and getattr(self, "group", None) is not None
+        super().close()
+        if hooked:   # (the plan's reduction hook leaves the context with it)
+            self.ctx.set_allreduce(None)
 
 
 def binned_median(x: np.ndarray, y: np.ndarray, n_bins: int = 72, ctx: _lib.Context | None = None):
@@ -344,39 +308,6 @@ def _check_unbinned_optimizer(fit_optimizer, bin_before_fit: bool) -> None:
         )
 
 
-def subsample_valid_mask(valid_mask: np.ndarray, subsample: float | int, random_state=None) -> np.ndarray:
-    """Boolean mask of a random subsample of the valid pixels (``_get_subsample_on_valid_mask``, xdem/coreg/base.py:577-617).
-    The draw itself is geoutils' ``subsample_array`` (un-vendored, absent here); its published rule is restated --
-    ``rng = default_rng(random_state)``, ``n = int(subsample * n_valid)`` for 0 < subsample <= 1 else ``int(subsample)``,
-    capped at n_valid, ``rng.choice(flat valid indices, n, replace=False)`` -- **parity unpinned**."""
-    n_valid = int(np.count_nonzero(valid_mask))
-    if subsample == 1 and n_valid > 0:
-        return valid_mask
-    ranks = subsample_ranks(n_valid, subsample, random_state)
-    valids = np.flatnonzero(valid_mask.ravel())
-    out = np.zeros(valid_mask.size, dtype=bool)
-    out[valids[ranks]] = True
-    return out.reshape(valid_mask.shape)
-
-
-def subsample_ranks(n_valid: int, subsample: float | int, random_state=None) -> np.ndarray:
-    """The draw of ``subsample_valid_mask`` as RANKS among the valid pixels: ``rng.choice(valids, n, replace=False)`` is
-    ``valids[rng.choice(len(valids), n, replace=False)]`` -- NumPy draws the positions from the population SIZE and indexes the array
-    with them (same generator stream, same order; CPU test) -- so the ranks need only the count of valid pixels, not the mask:
-    the device turns them into pixels (``NKPlan.subsample``) and the mask stays where it is."""
-    if n_valid == 0:
-        raise ValueError(
-            "There is no valid points common to the input and auxiliary data (bias variables, or "
-            "derivatives required for this method, for example slope, aspect, etc)."
-        )
-    if subsample <= 0:
-        raise ValueError("`subsample` must be > 0")
-    npoints = int(subsample * n_valid) if subsample <= 1 else int(subsample)
-    npoints = min(npoints, n_valid)
-    rng = np.random.default_rng(random_state)
-    return rng.choice(n_valid, npoints, replace=False)
-
-
 def _iterate(plan: "NKPlan", res, tolerance, max_iterations, bin_sizes, fit_optimizer, bin_before_fit: bool, initial_offsets=(0.0, 0.0)):
     """``_iterate_method`` (affine.py:102-147) around one plan: stop when i > 1 and the horizontal step falls below the tolerance."""
     offsets = (float(initial_offsets[0]), float(initial_offsets[1]), 0.0)
@@ -428,12 +359,8 @@ def nuth_kaab(ref_elev: np.ndarray, tba_elev: np.ndarray, inlier_mask: np.ndarra
     fit_optimizer = fit_optimizer or scipy.optimize.curve_fit
     logging.info("Running Nuth and Kääb (2011) coregistration")
     plan = NKPlan(ref_elev, tba_elev, inlier_mask, ctx, group)
-    if subsample != 1 and plan.n_valid > 0 and group is None and not _HOST_DRAW:
-        # valid = inlier & finite ref / tba / slope / aspect (base.py:650-661), as the aux pass just established it; the draw needs its
-        # COUNT only (subsample_ranks), the plan turns the drawn ranks into pixels on the device: no mask back to the host, no second
-        # plan (20000^2 host arrays, default subsample: 0.95 s -> profiles/r06_nk_end_to_end.txt)
-        plan.subsample(subsample_ranks(plan.n_valid, subsample, random_state))
-    elif subsample != 1 and plan.n_valid > 0:
+    device_draw = group is None and not _HOST_DRAW
+    if subsample != 1 and plan.n_valid > 0 and not device_draw:
         # partitioned fits (and the test switch _HOST_DRAW): the mask travels, the draw indexes it on the host, a second plan takes it
         valid = plan.aux()[2]
         plan.close()
@@ -441,11 +368,13 @@ def nuth_kaab(ref_elev: np.ndarray, tba_elev: np.ndarray, inlier_mask: np.ndarra
             random_state = _shared_seed(random_state, group)
         plan = NKPlan(ref_elev, tba_elev, subsample_valid_mask(valid, subsample, random_state), ctx, group)
     try:
-        if plan.n_valid == 0:
-            raise ValueError(
-                "There is no valid points common to the input and auxiliary data (bias variables, or "
-                "derivatives required for this method, for example slope, aspect, etc)."
-            )
+        if device_draw:
+            # valid = inlier & finite ref / tba / slope / aspect (base.py:650-661), as the aux pass just established it; the draw needs
+            # its COUNT only (subsample_ranks), the plan turns the drawn ranks into pixels on the device: no mask back to the host, no
+            # second plan (20000^2 host arrays, default subsample: 0.95 s -> profiles/r06_nk_end_to_end.txt)
+            draw(plan, subsample, random_state)
+        elif plan.n_valid == 0:
+            raise ValueError(NO_VALID)
         plan.set_statistic(bin_statistic)
         if not isinstance(bin_sizes, (int, np.integer)):
             plan.set_bin_edges(bin_sizes)
@@ -455,32 +384,7 @@ def nuth_kaab(ref_elev: np.ndarray, tba_elev: np.ndarray, inlier_mask: np.ndarra
         plan.close()
 
 
-def apply_translation(elev: np.ndarray, shift_x: float, shift_y: float, shift_z: float, resolution, resample: bool = True,
-                      ctx: _lib.Context | None = None) -> np.ndarray:
-    """Apply a pure translation to a DEM array (``Coreg.apply`` for ``shift_x / shift_y / shift_z``): with
-    ``resample=True`` the shifted DEM is bilinearly resampled onto its original grid
-    (``_apply_matrix_rst`` case 2 + ``_reproject_horizontal_shift_samecrs``, xdem/coreg/base.py:1522-1570, 1615-1655):
-    ``out(r, c) = elev(r + shift_y / res_y, c - shift_x / res_x) + shift_z``.  Without resampling only ``shift_z`` is
-    added (the reference then just moves the geotransform)."""
-    arr = np.ascontiguousarray(elev.filled(np.nan) if isinstance(elev, np.ma.MaskedArray) else elev)
-    if arr.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
-        arr = arr.astype(np.float32)
-    from .spatialstats import _count_finite   # (np.isfinite over the raster on the library's host threads: 7 ms against 0.1 s at 20000^2)
-
-    if _count_finite(arr)[0] == 0:
-        raise ValueError("Input DEM has all nans.")
-    if not resample:
-        return arr + arr.dtype.type(shift_z)
-    res = (float(resolution), float(resolution)) if np.isscalar(resolution) else (float(resolution[0]), float(resolution[1]))
-    ctx = ctx or _lib.default_context()
-    out = np.empty_like(arr)
-    ctx.check(ctx._L.xdemhip_shift_bilinear(ctx.handle, arr.ctypes.data, _lib.F32 if arr.dtype == np.float32 else _lib.F64,
-                                            arr.shape[0], arr.shape[1], float(shift_y) / res[1], -float(shift_x) / res[0],
-                                            float(shift_z), out.ctypes.data, _lib.HOST))
-    return out
-
-
-class NuthKaab:
+class NuthKaab(_Step):
     """Nuth and Kaab (2011) coregistration: horizontal and vertical translations by iterative slope/aspect alignment.
 
     Constructor mirrors ``xdem.coreg.NuthKaab.__init__`` (xdem/coreg/affine.py:2397-2456).  ``fit`` takes the two DEMs
@@ -600,32 +504,6 @@ class NuthKaab:
         shifted = (t[0], t[1], t[2] + a["shift_x"], t[3], t[4], t[5] + a["shift_y"])
         return out, (type(transform)(*shifted) if hasattr(transform, "a") else shifted)
 
-    def fit_and_apply(self, reference_elev, to_be_aligned_elev, inlier_mask=None, bias_vars=None, weights=None, subsample=None,
-                      transform=None, crs=None, area_or_point=None, z_name: str = "z", resample: bool = True,
-                      resampling: str = "bilinear", random_state=None, fit_kwargs=None, apply_kwargs=None):
-        """``Coreg.fit_and_apply`` (base.py:2482-2590): fit, then apply to the to-be-aligned elevations."""
-        fit_kwargs = dict(fit_kwargs or {})
-        apply_kwargs = dict(apply_kwargs or {})
-        self.fit(reference_elev, to_be_aligned_elev, inlier_mask=inlier_mask, bias_vars=bias_vars, weights=weights, subsample=subsample,
-                 transform=transform, crs=crs, area_or_point=area_or_point, z_name=z_name, random_state=random_state, **fit_kwargs)
-        resolution = apply_kwargs.pop("resolution", fit_kwargs.get("resolution"))
-        return self.apply(to_be_aligned_elev, resolution, resample, bias_vars=bias_vars, resampling=resampling, transform=transform,
-                          crs=crs, z_name=z_name, **apply_kwargs)
-
-    def __add__(self, other):
-        """``NuthKaab() + other``: a two-step ``CoregPipeline`` (base.py:2008-2019)."""
-        from .biascorr import _pipeline_add
-
-        return _pipeline_add(self, other)
-
-    def copy(self) -> "NuthKaab":
-        """Identical, independent copy (base.py:1999-2006)."""
-        import copy as _copy
-
-        new = self.__new__(type(self))
-        new.__dict__ = {k: _copy.deepcopy(v) for k, v in self.__dict__.items()}
-        return new
-
     @property
     def is_affine(self) -> bool:
         return True
@@ -647,6 +525,3 @@ class NuthKaab:
         m[2, 3] += self.meta["outputs"]["affine"]["shift_z"]
         return m
 
-
-# Deramp, VerticalShift and pipelines of steps (xdem_amd/biascorr.py), importable from here as upstream's xdem.coreg offers them
-from .biascorr import CoregPipeline, Deramp, VerticalShift, polynomial_2d  # noqa: E402,F401

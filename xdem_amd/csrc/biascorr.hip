@@ -2,7 +2,7 @@
 //
 // Replaces, for raster-raster input (xdem/coreg):
 //   valid = inlier & isfinite(ref) & isfinite(tba)                      base.py:652-663       -> dh_valid_kernel (counts once per plan)
-//   random subsample of the valid pixels                                base.py:577-617       -> dh_sel_kernel (ranks -> pixels)
+//   random subsample of the valid pixels                                base.py:577-617       -> rank_select.h (ranks -> pixels)
 //   curve_fit(polynomial_2d, (xx, yy), ref - tba) over the valid pixels biascorr.py:195, 621-745, base.py:978-985
 //                                                                                             -> least-squares moments (dh_moments_*)
 //   np.median(ref - tba) over the valid pixels                          affine.py:721-770     -> radix selection (select_run.h)
@@ -22,6 +22,7 @@
 #include "common.h"
 #include "select.h"
 #include "select_run.h"
+#include "rank_select.h"
 
 struct xdemhip_dh_plan {
     xdemhip_ctx* ctx = nullptr;
@@ -43,7 +44,6 @@ struct xdemhip_dh_plan {
 namespace xd {
 namespace {
 
-constexpr int DH_TILE = 4096;        // pixels per tile of the count / compaction passes (256 threads x 16)
 constexpr int DH_MAX_ORDER = 5;
 
 template <typename T> __device__ __forceinline__ bool dh_finite(T v) { return t_finite<T>(v); }
@@ -74,7 +74,7 @@ __global__ __launch_bounds__(256) void dh_valid_kernel(const T* __restrict__ ref
     int c = 0;
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-        const int64_t p0 = (int64_t)blockIdx.x * DH_TILE + g * 1024 + (int64_t)threadIdx.x * 4;
+        const int64_t p0 = (int64_t)blockIdx.x * RANK_TILE + g * 1024 + (int64_t)threadIdx.x * 4;
         if (VEC && p0 + 4 <= n) {
             T a[4], b[4];
             load4<T>(ref + p0, a);
@@ -104,92 +104,6 @@ __global__ __launch_bounds__(256) void dh_valid_kernel(const T* __restrict__ ref
         __syncthreads();
     }
     if (threadIdx.x == 0) tile_cnt[blockIdx.x] = (unsigned long long)s[0];
-}
-
-// exclusive scan over the tile counts, in place; total in *total (one workgroup, pieces of 1024 with a carry)
-__global__ __launch_bounds__(1024) void dh_scan_kernel(unsigned long long* tile_cnt, int64_t n_tiles, unsigned long long* total) {
-    __shared__ unsigned long long s[1024];
-    __shared__ unsigned long long carry;
-    if (threadIdx.x == 0) carry = 0ull;
-    __syncthreads();
-    for (int64_t b0 = 0; b0 < n_tiles; b0 += 1024) {
-        const int64_t k = b0 + threadIdx.x;
-        const unsigned long long v = k < n_tiles ? tile_cnt[k] : 0ull;
-        s[threadIdx.x] = v;
-        __syncthreads();
-        for (int off = 1; off < 1024; off <<= 1) {
-            const unsigned long long a = (int)threadIdx.x >= off ? s[threadIdx.x - off] : 0ull;
-            __syncthreads();
-            s[threadIdx.x] += a;
-            __syncthreads();
-        }
-        if (k < n_tiles) tile_cnt[k] = carry + s[threadIdx.x] - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) carry += s[1023];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *total = carry;
-}
-
-__global__ __launch_bounds__(256) void dh_mark_kernel(const int64_t* __restrict__ ranks, int64_t k, int64_t n_ranks, uint8_t* __restrict__ mark,
-                                                      unsigned long long* bad) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < k; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t r = ranks[i];
-        if (r < 0 || r >= n_ranks) atomicAdd(bad, 1ull);
-        else mark[r] = 1;
-    }
-}
-
-// Selection of a tile's pixels: valid, and -- with `mark` -- whose rank among the valid pixels is marked.  WRITE = false: the number
-// selected per tile into sel[tile]; WRITE = true: sel[] holds the scanned offsets and the flat indexes go to idx[] in raster order.
-template <bool WRITE>
-__global__ __launch_bounds__(256) void dh_sel_kernel(const uint8_t* __restrict__ valid, int64_t n, const unsigned long long* __restrict__ valid_off,
-                                                     const uint8_t* __restrict__ mark, unsigned long long* __restrict__ sel, int64_t* __restrict__ idx) {
-    const int64_t t0 = (int64_t)blockIdx.x * DH_TILE + (int64_t)threadIdx.x * 16;
-    uint8_t v[16];
-    int cv = 0;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        v[k] = (t0 + k < n) ? valid[t0 + k] : (uint8_t)0;
-        cv += v[k] ? 1 : 0;
-    }
-    __shared__ int s[256];
-    int rank_in_tile = 0;
-    if (mark) {
-        s[threadIdx.x] = cv;
-        __syncthreads();
-        for (int off = 1; off < 256; off <<= 1) {
-            const int a = (int)threadIdx.x >= off ? s[threadIdx.x - off] : 0;
-            __syncthreads();
-            s[threadIdx.x] += a;
-            __syncthreads();
-        }
-        rank_in_tile = s[threadIdx.x] - cv;
-        __syncthreads();
-        unsigned long long r = valid_off[blockIdx.x] + (unsigned long long)rank_in_tile;
-#pragma unroll
-        for (int k = 0; k < 16; ++k)
-            if (v[k]) { v[k] = mark[r]; ++r; }
-    }
-    int cs = 0;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) cs += v[k] ? 1 : 0;
-    s[threadIdx.x] = cs;
-    __syncthreads();
-    for (int off = 1; off < 256; off <<= 1) {
-        const int a = (int)threadIdx.x >= off ? s[threadIdx.x - off] : 0;
-        __syncthreads();
-        s[threadIdx.x] += a;
-        __syncthreads();
-    }
-    if (!WRITE) {
-        if (threadIdx.x == 255) sel[blockIdx.x] = (unsigned long long)s[255];
-        return;
-    }
-    unsigned long long o = sel[blockIdx.x] + (unsigned long long)(s[threadIdx.x] - cs);
-#pragma unroll
-    for (int k = 0; k < 16; ++k)
-        if (v[k]) idx[o++] = t0 + k;
 }
 
 // ---- moments, dense route ----------------------------------------------------------------------------------------------------
@@ -539,7 +453,7 @@ int ensure_mask(xdemhip_dh_plan* P) {
     }
     const int rc = launch_valid(P, true);
     if (rc) return rc;
-    hipLaunchKernelGGL(dh_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, P->tile_off, P->n_tiles, P->tile_off + P->n_tiles);
+    hipLaunchKernelGGL(rank_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, P->tile_off, P->n_tiles, P->tile_off + P->n_tiles);
     return hipGetLastError() == hipSuccess ? XDEMHIP_OK : xd_fail(ctx, XDEMHIP_EHIP, "dh_scan_kernel launch failed");
 }
 
@@ -553,8 +467,8 @@ int ensure_valid_idx(xdemhip_dh_plan* P) {
         P->idx = nullptr;
         return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed (valid pixel list)");
     }
-    hipLaunchKernelGGL((dh_sel_kernel<true>), dim3((unsigned)P->n_tiles), dim3(256), 0, ctx->stream, P->valid, P->H * P->W, P->tile_off,
-                       (const uint8_t*)nullptr, P->tile_off, P->idx);
+    hipLaunchKernelGGL((rank_select_kernel<RankOut::List>), dim3((unsigned)P->n_tiles), dim3(256), 0, ctx->stream, P->valid, P->H * P->W,
+                       (const unsigned long long*)nullptr, (const uint8_t*)nullptr, P->tile_off, P->idx, (uint8_t*)nullptr);
     if (hipGetLastError() != hipSuccess) return xd_fail(ctx, XDEMHIP_EHIP, "dh_sel_kernel launch failed");
     P->n_idx = P->n_valid;
     return XDEMHIP_OK;
@@ -648,7 +562,7 @@ int xdemhip_dh_create(xdemhip_ctx* ctx, const void* ref, const void* tba, const 
     const int64_t n = H * W;
     xdemhip_dh_plan* P = new xdemhip_dh_plan();
     P->ctx = ctx; P->dtype = dtype; P->H = H; P->W = W;
-    P->n_tiles = (n + DH_TILE - 1) / DH_TILE;
+    P->n_tiles = (n + RANK_TILE - 1) / RANK_TILE;
     auto fail = [&](int code) { xdemhip_dh_destroy(P); return code; };
     if (P->n_tiles > 0x7FFFFFFF) return fail(xd_fail(ctx, XDEMHIP_EINVAL, "xdemhip_dh_create: raster too large"));
     if (memspace == XDEMHIP_HOST) {
@@ -673,7 +587,7 @@ int xdemhip_dh_create(xdemhip_ctx* ctx, const void* ref, const void* tba, const 
     }
     // (counts only: the mask itself is built by the routes that read it)
     { const int rc_ = launch_valid(P, false); if (rc_) return fail(rc_); }
-    hipLaunchKernelGGL(dh_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, P->tile_off, P->n_tiles, P->tile_off + P->n_tiles);
+    hipLaunchKernelGGL(rank_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, P->tile_off, P->n_tiles, P->tile_off + P->n_tiles);
     if (hipGetLastError() != hipSuccess) return fail(xd_fail(ctx, XDEMHIP_EHIP, "xdemhip_dh_create: kernel launch failed"));
     unsigned long long total = 0;
     { const int rc_ = xd_d2h(ctx, &total, P->tile_off + P->n_tiles, 8); if (rc_) return fail(rc_); }
@@ -692,51 +606,26 @@ int xdemhip_dh_subsample(xdemhip_dh_plan* P, const int64_t* ranks, int64_t k, in
     if (memspace != XDEMHIP_HOST && memspace != XDEMHIP_DEVICE) return xd_fail(ctx, XDEMHIP_EINVAL, "bad memspace");
     XD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     { const int rc_ = ensure_mask(P); if (rc_) return rc_; }
-    const int64_t n = P->H * P->W;
-    uint8_t* mark = nullptr;
-    unsigned long long* sel = nullptr;   // [n_tiles] counts -> offsets, [1] total, [1] ranks out of range
-    int64_t* d_ranks = nullptr;
+    RankSelect rs;
+    unsigned long long total = 0, bad = 0;
+    { const int rc_ = rs.run(ctx, "xdemhip_dh_subsample", ranks, k, memspace, P->n_valid, P->valid, P->H * P->W, P->tile_off, &total, &bad); if (rc_) return rc_; }
+    if (bad != 0) return xd_fail(ctx, XDEMHIP_EINVAL, "xdemhip_dh_subsample: a rank is outside [0, n_valid)");
+    if ((int64_t)total > k) return xd_fail(ctx, XDEMHIP_EINVAL, "xdemhip_dh_subsample: more pixels than ranks");
+    // (repeated ranks select one pixel: the list is as long as the distinct ranks)
     int64_t* idx = nullptr;
-    auto release = [&]() {
-        if (mark) (void)hipFree(mark);
-        if (sel) (void)hipFree(sel);
-        if (d_ranks) (void)hipFree(d_ranks);
-        if (idx) (void)hipFree(idx);
-    };
-    if (hipMalloc(reinterpret_cast<void**>(&mark), (size_t)P->n_valid) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&sel), (size_t)(P->n_tiles + 2) * 8) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&idx), (size_t)k * 8) != hipSuccess ||
-        (memspace == XDEMHIP_HOST && hipMalloc(reinterpret_cast<void**>(&d_ranks), (size_t)k * 8) != hipSuccess)) {
+    if (hipMalloc(reinterpret_cast<void**>(&idx), (size_t)k * 8) != hipSuccess) {
         (void)hipGetLastError();
-        release();
         return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed (xdemhip_dh_subsample)");
     }
-    auto fail = [&](int code, const char* msg) { release(); return xd_fail(ctx, code, msg); };
-    const int64_t* rk = ranks;
-    if (memspace == XDEMHIP_HOST) {
-        if (hipMemcpyAsync(d_ranks, ranks, (size_t)k * 8, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return fail(XDEMHIP_EHIP, "copy of the ranks failed");
-        rk = d_ranks;
-    }
-    if (hipMemsetAsync(mark, 0, (size_t)P->n_valid, ctx->stream) != hipSuccess || hipMemsetAsync(sel + P->n_tiles, 0, 16, ctx->stream) != hipSuccess)
-        return fail(XDEMHIP_EHIP, "hipMemsetAsync failed");
-    hipLaunchKernelGGL(dh_mark_kernel, dim3(grid_for(ctx, k, 256, 8)), dim3(256), 0, ctx->stream, rk, k, P->n_valid, mark, sel + P->n_tiles + 1);
-    hipLaunchKernelGGL((dh_sel_kernel<false>), dim3((unsigned)P->n_tiles), dim3(256), 0, ctx->stream, P->valid, n, P->tile_off, mark, sel, (int64_t*)nullptr);
-    hipLaunchKernelGGL(dh_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, sel, P->n_tiles, sel + P->n_tiles);
-    unsigned long long chk[2] = {0, 0};
-    { const int rc_ = xd_d2h(ctx, chk, sel + P->n_tiles, 16); if (rc_) { release(); return rc_; } }
-    { const int rc_ = xd_sync(ctx); if (rc_) { release(); return rc_; } }
-    if (chk[1] != 0) return fail(XDEMHIP_EINVAL, "xdemhip_dh_subsample: a rank is outside [0, n_valid)");
-    if ((int64_t)chk[0] > k) return fail(XDEMHIP_EINVAL, "xdemhip_dh_subsample: more pixels than ranks");
-    // (repeated ranks select one pixel: the list is as long as the distinct ranks)
-    hipLaunchKernelGGL((dh_sel_kernel<true>), dim3((unsigned)P->n_tiles), dim3(256), 0, ctx->stream, P->valid, n, P->tile_off, mark, sel, idx);
-    if (hipGetLastError() != hipSuccess) return fail(XDEMHIP_EHIP, "xdemhip_dh_subsample: kernel launch failed");
-    { const int rc_ = xd_sync(ctx); if (rc_) { release(); return rc_; } }
+    hipLaunchKernelGGL((rank_select_kernel<RankOut::List>), dim3((unsigned)P->n_tiles), dim3(256), 0, ctx->stream, P->valid, P->H * P->W, P->tile_off,
+                       rs.mark, rs.off, idx, (uint8_t*)nullptr);
+    int rc = hipGetLastError() == hipSuccess ? XDEMHIP_OK : xd_fail(ctx, XDEMHIP_EHIP, "xdemhip_dh_subsample: kernel launch failed");
+    if (rc == XDEMHIP_OK) rc = xd_sync(ctx);
+    if (rc) { (void)hipFree(idx); return rc; }
     if (P->idx) (void)hipFree(P->idx);
     P->idx = idx;
-    idx = nullptr;
-    P->n_idx = (int64_t)chk[0];
+    P->n_idx = (int64_t)total;
     P->drawn = true;
-    release();
     if (n_drawn) *n_drawn = P->n_idx;
     return XDEMHIP_OK;
 }

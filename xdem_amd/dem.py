@@ -15,6 +15,7 @@ from typing import Any
 import numpy as np
 
 from . import coreg as _coreg
+from ._coregbase import _Step
 from . import spatialstats as _ss
 from . import terrain
 
@@ -135,7 +136,7 @@ class DEM:
         if random_state is not None:
             kwargs["random_state"] = random_state
         method = coreg_method if coreg_method is not None else _coreg.NuthKaab(subsample=1)
-        if not isinstance(method, (_coreg.NuthKaab, _coreg.Deramp, _coreg.VerticalShift, _coreg.CoregPipeline)):
+        if not isinstance(method, _Step):
             raise ValueError("Argument `coreg_method` must be an xdem_amd.coreg instance (e.g. xdem_amd.coreg.NuthKaab()).")
         if reference_elev.shape != self.shape or reference_elev.transform != self.transform:
             raise NotImplementedError("reference and to-be-aligned DEM must share one grid (reprojection is geoutils' job).")

@@ -210,10 +210,7 @@ def nuth_kaab_row_blocks(ref_rows: torch.Tensor, tba_rows: torch.Tensor, total_r
                             block=(total_rows, r0, r1, rb.halo_top, rb.halo_bottom))
         try:
             if plan.n_valid == 0:
-                raise ValueError(
-                    "There is no valid points common to the input and auxiliary data (bias variables, or "
-                    "derivatives required for this method, for example slope, aspect, etc)."
-                )
+                raise ValueError(coreg.NO_VALID)
             plan.set_statistic(bin_statistic)
             if not isinstance(bin_sizes, (int, np.integer)):
                 plan.set_bin_edges(bin_sizes)
