@@ -11,6 +11,7 @@ Fixture families:
   terrain_T4     int32 DEM -> float32 outputs
   terrain_T5     window sizes 3/5/7 for TPI/TRI
   terrain_T9     rugosity + fractal roughness (incl. the known answers of test_window.py:21-89)
+  terrain_T10    texture shading (freq.py:63-148); T10b the same at length-1 axes and odd FFT lengths
   terrain_T11    the reference's own NUMBA-engine code (surfit.py:948-1088, 1270-1303; window.py:767-870, 980-1000) run
                  in the interpreter through the identity-njit shim of _refimport.py: T1 DEMs (f32 + f64, NaN and Inf
                  holes), a terrain-like DEM, three fits, both curvature methods, windowed indexes
@@ -341,6 +342,30 @@ def terrain_T10() -> None:
     np.savez_compressed(os.path.join(OUT, "terrain_T10_texture.npz"), **rec)
 
 
+def terrain_T10b() -> None:
+    """Texture shading at the shapes T10 leaves out: length-1 axes (FFT 1 x 1, 1 x 8, 8 x 1) and odd FFT lengths (1029 = 3 * 7^3
+    beside 4, 16 and 1029 beside 16), float32 / float64 DEMs with NaN holes, alpha 0.8 -- the reference's own _texture_shading_fft,
+    in a file of its own so that T10 stays as it is."""
+    import importlib
+
+    freq = importlib.import_module("xdem.terrain.freq")
+    rng = np.random.default_rng(29)
+    rec = {}
+    for shape in ((1, 1), (1, 7), (7, 1), (3, 1025), (1029, 9), (9, 1029)):
+        base = 800.0 + np.cumsum(np.cumsum(rng.normal(scale=0.3, size=shape), axis=0), axis=1)
+        if base.size > 1:
+            base[rng.uniform(size=shape) < 0.02] = np.nan
+            base.flat[base.size // 2] = np.nan
+        for dt in (np.float32, np.float64):
+            dem = base.astype(dt)
+            key = f"{shape[0]}x{shape[1]}|{np.dtype(dt).name}"
+            rec[f"dem|{key}"] = dem
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore")
+                rec[f"{key}|0.8"] = freq._texture_shading_fft(dem, 0.8)
+    np.savez_compressed(os.path.join(OUT, "terrain_T10b_texture_shapes.npz"), **rec)
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     which = sys.argv[1:] or ["terrain", "nk", "vario", "binning", "patches", "conv"]
@@ -352,6 +377,7 @@ if __name__ == "__main__":
         terrain_T4_T5()
         terrain_T9()
         terrain_T10()
+        terrain_T10b()
         terrain_T11_numba()
         terrain_T12_engine_boundary()
         print("terrain fixtures written")

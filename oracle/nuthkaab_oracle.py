@@ -62,23 +62,25 @@ def aux_vars(ref: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
     return slope_tan, aspect
 
 
-def bilinear_shifted(img: np.ndarray, dr: float, dc: float, nan_rule: int | None = None) -> np.ndarray:
+def bilinear_shifted(img: np.ndarray, dr: float, dc: float, nan_rule: int | None = None, row_offset: int = 0) -> np.ndarray:
     """bilinear(img)(row + dr, col + dc) on the full grid, float64 weights, result in img's dtype.  ``nan_rule`` = the
     switchable nodata convention of the kernel (geoutils' own rule is unpinned, see header): 0 "4tap" -- NaN if any of the
     four taps is non-finite or outside, zero weights included (except a zero-weight tap beyond the last row / column: nodes on
     the upper edge keep their value); 1 "weighted" -- taps with zero weight are ignored; 2
     "dilate3x3" -- NaN if the 3 x 3 neighbourhood of the nearest pixel holds a non-finite pixel or leaves the raster; 3
-    "dilate_cross" -- the same with the 4-connected cross."""
+    "dilate_cross" -- the same with the 4-connected cross.  ``row_offset``: ``img`` is a slab of a taller raster starting at
+    that row; tap positions are formed from the raster row (row_offset + row) + dr, as on the full raster, and taps that leave
+    the slab count as outside it (rows within three of a slab edge that is not a raster edge are then not the full raster's)."""
     if nan_rule is None:   # the decided convention (oracle/_conventions.py: the product's default, 0 unless a decision file says otherwise)
         nan_rule = _conventions.decided("nk_nan_rule")
     H, W = img.shape
-    rr = np.arange(H, dtype=np.float64)[:, None] + dr
+    rr = np.arange(row_offset, row_offset + H, dtype=np.float64)[:, None] + dr
     cc = np.arange(W, dtype=np.float64)[None, :] + dc
     r0 = np.floor(rr)
     c0 = np.floor(cc)
     fr = rr - r0
     fc = cc - c0
-    r0 = r0.astype(np.int64)
+    r0 = r0.astype(np.int64) - row_offset
     c0 = c0.astype(np.int64)
     # zero-weight taps: ignored by rule 1 everywhere; by the other rules only where the tap would leave the raster (a node
     # exactly on the upper edge is returned by every linear interpolator)
@@ -109,7 +111,7 @@ def bilinear_shifted(img: np.ndarray, dr: float, dc: float, nan_rule: int | None
                 for b in range(3):
                     if nan_rule == 2 or a == 1 or b == 1:  # rule 3: the 4-connected cross (SciPy's default dilation structure)
                         dil |= pad[a : a + H, b : b + W]
-            rn = np.floor(rr + 0.5).astype(np.int64)
+            rn = np.floor(rr + 0.5).astype(np.int64) - row_offset
             cn = np.floor(cc + 0.5).astype(np.int64)
             inside = np.broadcast_to((rn >= 0) & (rn < H), (H, W)) & np.broadcast_to((cn >= 0) & (cn < W), (H, W))
             near_bad = np.where(inside, dil[np.clip(rn, 0, H - 1), np.clip(cn, 0, W - 1)], True)

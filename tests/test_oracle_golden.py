@@ -212,6 +212,21 @@ def test_T10_texture_shading():
     assert np.all(z["flat|0.8"] == 0) and np.isnan(z["allnan|0.8"]).all()  # tests/test_terrain/test_freq.py:53-57
 
 
+def test_T10b_texture_shading_shapes():
+    """The oracle's texture shading at length-1 axes (FFT 1 x 1, 1 x 8, 8 x 1) and odd FFT lengths (1029) equals the reference's
+    own _texture_shading_fft (tests/golden/terrain_T10b_texture_shapes.npz) bit for bit, float32 and float64."""
+    z = _load("terrain_T10b_texture_shapes.npz")
+    n = 0
+    for key in z.files:
+        if key.startswith("dem|"):
+            continue
+        name, alpha = key.rsplit("|", 1)
+        got = to.texture_shading(z[f"dem|{name}"], float(alpha))
+        assert _same(got, z[key]), key
+        n += 1
+    assert n == 12
+
+
 def test_oracle_convolution_equals_scipy():
     """The restated convolution must reproduce scipy.ndimage.convolve (the reference's engine call) bit for bit."""
     scipy_ndimage = pytest.importorskip("scipy.ndimage")

@@ -63,8 +63,14 @@ static int64_t nextprod_fft(int64_t n) {
     }
 }
 
+// Fill statistics in a fixed order: each workgroup leaves its partial (waves reduced by shuffles, then its four waves in order)
+// and one workgroup adds the partials -- the same bits on every call (float64 atomics added them in arrival order: the fill of a
+// float64 DEM with holes changed in its last bit from call to call).
+struct TexStats { double sum; unsigned long long nn, fin; };   // sum and count of the non-NaN values, count of the finite ones
+
 template <typename T>
-__global__ __launch_bounds__(256) void tex_stats_kernel(const T* dem, int64_t n, double* sum, unsigned long long* counts /* [non-NaN, finite] */) {
+__global__ __launch_bounds__(256) void tex_stats_kernel(const T* dem, int64_t n, TexStats* part) {
+    __shared__ TexStats s_wave[4];
     double s = 0.0;
     unsigned long long c_nn = 0, c_fin = 0;
     for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (int64_t)gridDim.x * blockDim.x) {
@@ -73,7 +79,33 @@ __global__ __launch_bounds__(256) void tex_stats_kernel(const T* dem, int64_t n,
         if (fabs((double)v) <= 1.79769313486231570e308) ++c_fin;
     }
     for (int off = 32; off > 0; off >>= 1) { s += __shfl_down(s, off); c_nn += __shfl_down(c_nn, off); c_fin += __shfl_down(c_fin, off); }
-    if ((threadIdx.x & 63) == 0) { atomicAdd(sum, s); atomicAdd(&counts[0], c_nn); atomicAdd(&counts[1], c_fin); }
+    if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = TexStats{s, c_nn, c_fin};
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        TexStats t = s_wave[0];
+        for (int w = 1; w < 4; ++w) { t.sum += s_wave[w].sum; t.nn += s_wave[w].nn; t.fin += s_wave[w].fin; }
+        part[blockIdx.x] = t;
+    }
+}
+
+// lane l adds the partials of workgroups l, l + 256, ... in order, then a fixed tree over the lanes
+__global__ __launch_bounds__(256) void tex_stats_reduce_kernel(const TexStats* part, int nblocks, TexStats* out) {
+    __shared__ double s_sum[256];
+    __shared__ unsigned long long s_nn[256], s_fin[256];
+    double a = 0.0;
+    unsigned long long b = 0, c = 0;
+    for (int k = threadIdx.x; k < nblocks; k += 256) { a += part[k].sum; b += part[k].nn; c += part[k].fin; }
+    s_sum[threadIdx.x] = a; s_nn[threadIdx.x] = b; s_fin[threadIdx.x] = c;
+    __syncthreads();
+    for (int half = 128; half > 0; half >>= 1) {
+        if ((int)threadIdx.x < half) {
+            s_sum[threadIdx.x] += s_sum[threadIdx.x + half];
+            s_nn[threadIdx.x] += s_nn[threadIdx.x + half];
+            s_fin[threadIdx.x] += s_fin[threadIdx.x + half];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *out = TexStats{s_sum[0], s_nn[0], s_fin[0]};
 }
 
 // padded[r][c] = filled DEM at the symmetric reflection of (r - pad_r, c - pad_c)   (np.pad(mode="symmetric"))
@@ -136,23 +168,23 @@ static int texture_typed(xdemhip_ctx* ctx, const T* d_dem, int64_t H, int64_t W,
     FftApi& api = fft_api();
     if (!api.ok) return xd_fail(ctx, XDEMHIP_EUNSUPPORTED, "libhipfft.so could not be loaded (needed by texture shading only)");
     const int64_t n = H * W;
-    double* d_sum = nullptr;
+    TexStats* d_stats = nullptr;   // [g1] per-workgroup partials, then the total
     T *d_pad = nullptr, *d_spec = nullptr;
     fft_handle fwd = nullptr, inv = nullptr;
     auto cleanup = [&]() {
         if (fwd) api.destroy(fwd);
         if (inv) api.destroy(inv);
-        if (d_sum) (void)hipFree(d_sum);
+        if (d_stats) (void)hipFree(d_stats);
         if (d_pad) (void)hipFree(d_pad);
         if (d_spec) (void)hipFree(d_spec);
     };
-    if (hipMalloc(reinterpret_cast<void**>(&d_sum), 24) != hipSuccess) return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed");
-    (void)hipMemsetAsync(d_sum, 0, 24, ctx->stream);
     const int g1 = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
-    hipLaunchKernelGGL((tex_stats_kernel<T>), dim3(g1), dim3(256), 0, ctx->stream, d_dem, n, d_sum,
-                       reinterpret_cast<unsigned long long*>(d_sum + 1));
-    struct { double sum; unsigned long long nn, fin; } st;
-    hipError_t e = hipMemcpyAsync(&st, d_sum, 24, hipMemcpyDeviceToHost, ctx->stream);
+    if (hipMalloc(reinterpret_cast<void**>(&d_stats), (size_t)(g1 + 1) * sizeof(TexStats)) != hipSuccess)
+        return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed");
+    hipLaunchKernelGGL((tex_stats_kernel<T>), dim3(g1), dim3(256), 0, ctx->stream, d_dem, n, d_stats);
+    hipLaunchKernelGGL(tex_stats_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, d_stats, g1, d_stats + g1);
+    TexStats st;
+    hipError_t e = hipMemcpyAsync(&st, d_stats + g1, sizeof(TexStats), hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) { cleanup(); return xd_fail(ctx, XDEMHIP_EHIP, std::string("texture statistics failed: ") + hipGetErrorString(e)); }
     if (st.fin == 0) {  // no valid pixel: all NaN (freq.py:88-89)
