@@ -362,7 +362,18 @@ int xdemhip_binned_median(xdemhip_ctx* ctx, const void* x, const void* y, int dt
  *                           values in the value dtype for an even count), and the count.
  *  xdemhip_dh_values        dh (plan dtype) and the column / row index (int64) of every selected pixel, in raster order (any output may
  *                           be NULL; each holds *count elements -- n_valid, or n_drawn after a subsample): what a host callable receives.
- * Every entry returns XDEMHIP_EINVAL ("no valid points") where nothing is selected. */
+ *  xdemhip_dh_shift_nmad    the objective of DhMinimize (xdem/coreg/affine.py:617-674) at one trial shift: for every selected pixel (r, c)
+ *                           dh = ref[r, c] - bilinear(tba)(r - shift_y / res_y, c + shift_x / res_x), with the taps and the nodata rule of
+ *                           the Nuth-Kaab step (option "nk_nan_rule"; float64 weights, the interpolated value rounded to the raster
+ *                           dtype, the difference taken in it); pixels whose interpolated value is NaN drop out.  *count = the number
+ *                           left, *median = np.nanmedian(dh) (exact; mean of the two middle values in the value dtype for an even
+ *                           count), *nmad = (T)nfact * np.nanmedian(|dh - median|) rounded as xdemhip_nmad rounds it.  One pass over the
+ *                           rasters per call; both selections read the plan's staging copy of dh, and their results come back in one
+ *                           fetch.  The plan keeps the buffers from the first call on.  Single-process plans: a reduction hook on the
+ *                           context is suspended for the call.
+ *  xdemhip_dh_shift_values  the same dh of every selected pixel in raster order (plan dtype, NaN kept where the interpolation is NaN):
+ *                           what any other loss function receives; *count = the number of selected pixels, as xdemhip_dh_values.
+ * Every entry returns XDEMHIP_EINVAL ("no valid points") where nothing is selected (xdemhip_dh_shift_nmad: where nothing is left). */
 typedef struct xdemhip_dh_plan xdemhip_dh_plan;
 int xdemhip_dh_create(xdemhip_ctx* ctx, const void* ref, const void* tba, const uint8_t* inlier_mask_or_null, int dtype, int64_t H, int64_t W,
                       int memspace, xdemhip_dh_plan** out_plan, int64_t* n_valid);
@@ -371,6 +382,10 @@ int xdemhip_dh_poly_moments(xdemhip_dh_plan* plan, int order, int64_t row_offset
                             double* r_out, int64_t* count);
 int xdemhip_dh_median(xdemhip_dh_plan* plan, double* median, int64_t* count);
 int xdemhip_dh_values(xdemhip_dh_plan* plan, void* dh_out, int64_t* col_out, int64_t* row_out, int memspace, int64_t* count);
+int xdemhip_dh_shift_nmad(xdemhip_dh_plan* plan, double shift_x, double shift_y, double res_x, double res_y, double nfact, double* median,
+                          double* nmad, int64_t* count);
+int xdemhip_dh_shift_values(xdemhip_dh_plan* plan, double shift_x, double shift_y, double res_x, double res_y, void* dh_out, int memspace,
+                            int64_t* count);
 void xdemhip_dh_destroy(xdemhip_dh_plan* plan);
 /* out = cast(double(elev) + P(x, y)), P = np.polynomial.polynomial.polyval2d(x, y, c) with c[i, j] = coeffs[i * (order + 1) + j]
  * (the reference's fit_params reshaped), x = column, y = row_offset + row, evaluated in NumPy's order bit for bit: Horner in x for

@@ -180,6 +180,10 @@ def lib() -> ctypes.CDLL:
                                               c_i64p]
         L.xdemhip_dh_median.argtypes = [ctypes.c_void_p, c_dp, c_i64p]
         L.xdemhip_dh_values.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, c_i64p]
+        L.xdemhip_dh_shift_nmad.argtypes = [ctypes.c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                            c_dp, c_dp, c_i64p]
+        L.xdemhip_dh_shift_values.argtypes = [ctypes.c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                              ctypes.c_void_p, ctypes.c_int, c_i64p]
         L.xdemhip_dh_destroy.argtypes = [ctypes.c_void_p]
         L.xdemhip_dh_destroy.restype = None
         L.xdemhip_poly2d_apply.argtypes = [c_ctx, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, c_dp,

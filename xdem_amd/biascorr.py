@@ -59,16 +59,16 @@ class DhPlan(_Plan):
     _DESTROY = "xdemhip_dh_destroy"
 
     def __init__(self, ref, tba, inlier_mask=None, ctx: _lib.Context | None = None):
-        self.ctx = ctx or _lib.default_context()
         self.handle = None
         self.drawn = False
-        self.ctx.adopt(self)
-        h, nv = ctypes.c_void_p(), ctypes.c_int64()
         if not hasattr(ref, "is_cuda"):
             ref, tba, inlier_mask = _host_array(ref), _host_array(tba), _host_array(inlier_mask)
-        p = raster_pair(ref, tba, inlier_mask)
+        p = raster_pair(ref, tba, inlier_mask)   # (checked before a device is asked for: what is no raster pair is refused anywhere)
         if p.memspace == _lib.HOST and p.keep[2] is not None and p.keep[2].shape != p.shape:
             raise ValueError("inlier_mask must have the shape of the rasters")
+        self.ctx = ctx or _lib.default_context()
+        self.ctx.adopt(self)
+        h, nv = ctypes.c_void_p(), ctypes.c_int64()
         self.dtype, self.shape = p.dtype, p.shape
         if p.memspace == _lib.DEVICE:
             self._keep = p.keep
@@ -120,6 +120,30 @@ class DhPlan(_Plan):
         if int(cnt.value) != k:
             raise _lib.XdemHipError(f"xdemhip_dh_values returned {cnt.value} values, expected {k}")
         return (dh, col, row) if coords else dh
+
+    def shift_nmad(self, shift_x: float, shift_y: float, res, nfact: float = 1.4826) -> tuple[float, float, int]:
+        """(median, nmad, count) of dh = ref - bilinear(tba)(row - shift_y / res_y, col + shift_x / res_x) over the selected pixels, the
+        ones whose interpolated value is NaN dropped: ``np.nanmedian(dh)``, ``nfact * np.nanmedian(|dh - median|)`` in the value dtype
+        and ``np.isfinite(dh).sum()``, all exact (``xdemhip_dh_shift_nmad``: one pass over the rasters, two selections, one fetch).
+        Raises "no valid points" where no pixel is left."""
+        res = (float(res), float(res)) if np.isscalar(res) else (float(res[0]), float(res[1]))
+        med, nm, cnt = ctypes.c_double(), ctypes.c_double(), ctypes.c_int64()
+        self.ctx.check(self.ctx._L.xdemhip_dh_shift_nmad(self.handle, float(shift_x), float(shift_y), res[0], res[1], float(nfact),
+                                                         ctypes.byref(med), ctypes.byref(nm), ctypes.byref(cnt)))
+        return med.value, nm.value, int(cnt.value)
+
+    def shift_values(self, shift_x: float, shift_y: float, res) -> np.ndarray:
+        """The same dh of every selected pixel (plan dtype, raster order, NaN where the interpolated value is): what a host loss function
+        receives (``xdemhip_dh_shift_values``)."""
+        res = (float(res), float(res)) if np.isscalar(res) else (float(res[0]), float(res[1]))
+        k = self.n_selected
+        dh = np.empty(k, dtype=self.dtype)
+        cnt = ctypes.c_int64()
+        self.ctx.check(self.ctx._L.xdemhip_dh_shift_values(self.handle, float(shift_x), float(shift_y), res[0], res[1], dh.ctypes.data,
+                                                           _lib.HOST, ctypes.byref(cnt)))
+        if int(cnt.value) != k:
+            raise _lib.XdemHipError(f"xdemhip_dh_shift_values returned {cnt.value} values, expected {k}")
+        return dh
 
 
 # ---- polynomial algebra on the host --------------------------------------------------------------------------------------------

@@ -22,11 +22,13 @@ import warnings
 from typing import Any, Callable
 
 import numpy as np
+import scipy.optimize
 
 from . import _lib
 from ._coregbase import NO_VALID, CoregPipeline, _Plan, _Step, apply_translation, draw, raster_pair  # noqa: F401
 from ._coregbase import subsample_ranks, subsample_valid_mask  # noqa: F401
-from .biascorr import Deramp, VerticalShift, polynomial_2d  # noqa: F401  (upstream's xdem.coreg offers them here)
+from .biascorr import Deramp, DhPlan, VerticalShift, _check_weights, polynomial_2d  # noqa: F401  (upstream's xdem.coreg offers them here)
+from .spatialstats import nmad
 
 
 def _nuth_kaab_fit_func(xx, *params):
@@ -384,7 +386,78 @@ def nuth_kaab(ref_elev: np.ndarray, tba_elev: np.ndarray, inlier_mask: np.ndarra
         plan.close()
 
 
-class NuthKaab(_Step):
+def _check_initial_shift(initial_shift):
+    """The checks of ``AffineCoreg.__init__`` (affine.py:1813-1829): a tuple of two or three numbers; a vertical part is dropped."""
+    if not (isinstance(initial_shift, tuple) and len(initial_shift) in (2, 3)
+            and all(isinstance(val, (float, int)) for val in initial_shift)):
+        raise ValueError("Argument `initial_shift` must be a tuple of exactly two or three numerical values.")
+    if len(initial_shift) == 2:
+        initial_shift += (0,)
+    elif initial_shift[2] != 0:
+        initial_shift = (*initial_shift[:2], 0)
+        warnings.warn("Initial shift in altitude is currently work in progress.", category=UserWarning)
+    return initial_shift
+
+
+class _TranslationStep(_Step):
+    """What the steps that estimate a translation (NuthKaab, DhMinimize) share: the grid spacing of a call, ``apply`` through
+    ``apply_translation`` and the matrix of ``meta["outputs"]["affine"]``."""
+
+    @staticmethod
+    def _resolution(resolution, transform) -> tuple[float, float]:
+        """(x, y) pixel size from ``resolution`` (scalar or pair) or from an affine ``transform`` (object with ``.a`` / ``.e`` or
+        a 6-tuple ``(a, b, c, d, e, f)``), which is how the reference's array interface carries it."""
+        if resolution is None and transform is not None:
+            a, e = (transform.a, transform.e) if hasattr(transform, "a") else (transform[0], transform[4])
+            return (abs(float(a)), abs(float(e)))
+        if resolution is None:
+            raise ValueError("'transform' must be given if both DEMs are array-like.")  # (base.py:204; or pass resolution=)
+        return (float(resolution), float(resolution)) if np.isscalar(resolution) else (float(resolution[0]), float(resolution[1]))
+
+    def apply(self, elev: np.ndarray, resolution: float | tuple[float, float] | None = None, resample: bool = True, *,
+              bias_vars=None, resampling: str = "bilinear", transform=None, crs=None, z_name: str = "z"):
+        """Apply the estimated translation to a DEM array on the fit grid (``Coreg.apply``, translation case; upstream's
+        keywords are keyword-only here).  With ``transform=`` the call returns ``(array, transform)`` like upstream's array
+        interface -- for ``resample=False`` the shift goes into the returned transform and only the vertical shift into the
+        array; with ``resolution=`` it returns the array alone."""
+        if bias_vars is not None:
+            raise NotImplementedError(f"bias_vars is not used by {type(self).__name__}.")
+        if resampling != "bilinear":
+            raise NotImplementedError("the GPU resampler is bilinear (the reference default).")
+        a = self.meta["outputs"]["affine"]
+        res = self._resolution(resolution, transform)
+        out = apply_translation(elev, a["shift_x"], a["shift_y"], a["shift_z"], res, resample)
+        if transform is None:
+            return out
+        if resample:
+            return out, transform
+        t = (transform.a, transform.b, transform.c, transform.d, transform.e, transform.f) if hasattr(transform, "a") else tuple(transform)
+        shifted = (t[0], t[1], t[2] + a["shift_x"], t[3], t[4], t[5] + a["shift_y"])
+        return out, (type(transform)(*shifted) if hasattr(transform, "a") else shifted)
+
+    @property
+    def is_affine(self) -> bool:
+        return True
+
+    def to_translations(self) -> tuple[float, float, float]:
+        """(x, y, z) translations of the estimated transform (base.py: ``to_translations`` of affine methods)."""
+        m = self.to_matrix()
+        return (float(m[0, 3]), float(m[1, 3]), float(m[2, 3]))
+
+    def to_rotations(self) -> tuple[float, float, float]:
+        """Rotations of the estimated transform: none, the method estimates a pure translation."""
+        return (0.0, 0.0, 0.0)
+
+    def to_matrix(self) -> np.ndarray:
+        """4x4 translation matrix (affine.py:2532-2541)."""
+        m = np.diag(np.ones(4, dtype=float))
+        m[0, 3] += self.meta["outputs"]["affine"]["shift_x"]
+        m[1, 3] += self.meta["outputs"]["affine"]["shift_y"]
+        m[2, 3] += self.meta["outputs"]["affine"]["shift_z"]
+        return m
+
+
+class NuthKaab(_TranslationStep):
     """Nuth and Kaab (2011) coregistration: horizontal and vertical translations by iterative slope/aspect alignment.
 
     Constructor mirrors ``xdem.coreg.NuthKaab.__init__`` (xdem/coreg/affine.py:2397-2456).  ``fit`` takes the two DEMs
@@ -413,17 +486,7 @@ class NuthKaab(_Step):
                 raise NotImplementedError("explicit aspect-bin edges: at most 128 bins (one histogram sweep on the GPU); pass a "
                                           "number of bins (up to 1024) for a finer uniform binning.")
         if initial_shift is not None:
-            # same checks as AffineCoreg.__init__ (affine.py:1813-1829)
-            if not (isinstance(initial_shift, tuple) and len(initial_shift) in (2, 3)
-                    and all(isinstance(val, (float, int)) for val in initial_shift)):
-                raise ValueError("Argument `initial_shift` must be a tuple of exactly two or three numerical values.")
-            if len(initial_shift) == 2:
-                initial_shift += (0,)
-            elif initial_shift[2] != 0:
-                import warnings
-
-                initial_shift = (*initial_shift[:2], 0)
-                warnings.warn("Initial shift in altitude is currently work in progress.", category=UserWarning)
+            initial_shift = _check_initial_shift(initial_shift)
         self.vertical_shift = vertical_shift
         self.meta: dict[str, Any] = {
             "inputs": {
@@ -437,17 +500,6 @@ class NuthKaab(_Step):
             },
             "outputs": {},
         }
-
-    @staticmethod
-    def _resolution(resolution, transform) -> tuple[float, float]:
-        """(x, y) pixel size from ``resolution`` (scalar or pair) or from an affine ``transform`` (object with ``.a`` / ``.e`` or
-        a 6-tuple ``(a, b, c, d, e, f)``), which is how the reference's array interface carries it."""
-        if resolution is None and transform is not None:
-            a, e = (transform.a, transform.e) if hasattr(transform, "a") else (transform[0], transform[4])
-            return (abs(float(a)), abs(float(e)))
-        if resolution is None:
-            raise ValueError("'transform' must be given if both DEMs are array-like.")  # (base.py:204; or pass resolution=)
-        return (float(resolution), float(resolution)) if np.isscalar(resolution) else (float(resolution[0]), float(resolution[1]))
 
     def fit(self, reference_elev: np.ndarray, to_be_aligned_elev: np.ndarray, inlier_mask: np.ndarray | None = None,
             bias_vars=None, weights=None, subsample: int | float | None = None, transform=None, crs=None, area_or_point=None,
@@ -483,45 +535,78 @@ class NuthKaab(_Step):
         self.meta["outputs"]["random"] = {"subsample_final": n_final}
         return self
 
-    def apply(self, elev: np.ndarray, resolution: float | tuple[float, float] | None = None, resample: bool = True, *,
-              bias_vars=None, resampling: str = "bilinear", transform=None, crs=None, z_name: str = "z"):
-        """Apply the estimated translation to a DEM array on the fit grid (``Coreg.apply``, translation case; upstream's
-        keywords are keyword-only here).  With ``transform=`` the call returns ``(array, transform)`` like upstream's array
-        interface -- for ``resample=False`` the shift goes into the returned transform and only the vertical shift into the
-        array; with ``resolution=`` it returns the array alone."""
+
+class DhMinimize(_TranslationStep):
+    """Elevation difference minimization coregistration: the horizontal shift that minimises a dispersion of dh, then the median of dh
+    there as vertical shift.  Constructor of ``xdem.coreg.DhMinimize`` (xdem/coreg/affine.py:2667-2696); ``fit`` mirrors
+    ``_dh_minimize_fit`` (affine.py:636-674) around a dh plan: every evaluation of the objective is ``DhPlan.shift_nmad`` -- one pass over
+    the rasters and two exact selections on the device, the loss bit for bit what ``nmad`` returns for the same dh on the host, so the
+    minimiser takes the decisions it would take there.  A ``fit_loss_func`` other than ``xdem_amd.spatialstats.nmad`` receives the
+    flattened dh of the selected pixels (``DhPlan.shift_values``) as upstream hands it over."""
+
+    def __init__(self, fit_minimizer: Callable[..., Any] = scipy.optimize.minimize, fit_loss_func: Callable[[np.ndarray], Any] = nmad,
+                 subsample: int | float = 5e5, initial_shift=None) -> None:
+        if not callable(fit_minimizer):
+            raise TypeError(f"Argument `fit_minimizer` must be a function (callable), got {type(fit_minimizer)}.")
+        if not callable(fit_loss_func):
+            raise TypeError(f"Argument `fit_loss_func` must be a function (callable), got {type(fit_loss_func)}.")
+        if initial_shift is not None:
+            initial_shift = _check_initial_shift(initial_shift)
+        self.meta: dict[str, Any] = {
+            "inputs": {
+                "fitorbin": {"fit_or_bin": "fit", "fit_minimizer": fit_minimizer, "fit_loss_func": fit_loss_func},
+                "random": {"subsample": subsample, "random_state": None},
+                "affine": {**({"initial_shift": initial_shift} if initial_shift is not None else {})},
+            },
+            "outputs": {},
+        }
+        self._needs_vars = False
+
+    def fit(self, reference_elev, to_be_aligned_elev, inlier_mask=None, bias_vars=None, weights=None, subsample=None, transform=None,
+            crs=None, area_or_point=None, z_name=None, random_state=None, resolution=None, **kwargs: Any) -> "DhMinimize":
+        """Estimate the x/y/z offset between two DEMs given as arrays on the same grid (``Coreg.fit`` with ``_fit_rst_rst``,
+        affine.py:2698-2762).  ``kwargs`` go to ``fit_minimizer`` as upstream passes them; the number of objective evaluations lands in
+        ``meta["outputs"]["specific"]["n_evaluations"]``."""
+        _check_weights(weights)
         if bias_vars is not None:
-            raise NotImplementedError("bias_vars is not used by NuthKaab.")
-        if resampling != "bilinear":
-            raise NotImplementedError("the GPU resampler is bilinear (the reference default).")
-        a = self.meta["outputs"]["affine"]
+            raise NotImplementedError("bias_vars is not used by DhMinimize.")
+        if subsample is not None:
+            self.meta["inputs"]["random"]["subsample"] = subsample
+        if random_state is not None:
+            self.meta["inputs"]["random"]["random_state"] = random_state
         res = self._resolution(resolution, transform)
-        out = apply_translation(elev, a["shift_x"], a["shift_y"], a["shift_z"], res, resample)
-        if transform is None:
-            return out
-        if resample:
-            return out, transform
-        t = (transform.a, transform.b, transform.c, transform.d, transform.e, transform.f) if hasattr(transform, "a") else tuple(transform)
-        shifted = (t[0], t[1], t[2] + a["shift_x"], t[3], t[4], t[5] + a["shift_y"])
-        return out, (type(transform)(*shifted) if hasattr(transform, "a") else shifted)
+        fb = self.meta["inputs"]["fitorbin"]
+        loss_func, minimizer = fb["fit_loss_func"], fb["fit_minimizer"]
+        # initial_shift (base.py:2307-2313, 2358-2366): the search runs around (sx, sy), as NuthKaab starts its iteration there
+        init = self.meta["inputs"]["affine"].get("initial_shift") or (0.0, 0.0, 0.0)
+        logging.info("Running dh minimization coregistration.")
+        n_eval = 0
+        with DhPlan(reference_elev, to_be_aligned_elev, inlier_mask) as plan:
+            n = draw(plan, self.meta["inputs"]["random"]["subsample"], self.meta["inputs"]["random"]["random_state"])
 
-    @property
-    def is_affine(self) -> bool:
-        return True
+            def fit_func(coords_offsets):
+                nonlocal n_eval
+                n_eval += 1
+                sx, sy = float(coords_offsets[0]) - init[0], float(coords_offsets[1]) - init[1]
+                if loss_func is nmad:
+                    return plan.dtype.type(plan.shift_nmad(sx, sy, res)[1])
+                return loss_func(plan.shift_values(sx, sy, res))
 
-    def to_translations(self) -> tuple[float, float, float]:
-        """(x, y, z) translations of the estimated transform (base.py: ``to_translations`` of affine methods)."""
-        m = self.to_matrix()
-        return (float(m[0, 3]), float(m[1, 3]), float(m[2, 3]))
+            init_offsets = (0, 0)
+            if minimizer == scipy.optimize.minimize and "method" not in kwargs:
+                # Nelder-Mead has trouble when initialised with (0, 0): upstream starts it from (1, 1) (affine.py:660-665)
+                kwargs.update({"method": "Nelder-Mead"})
+                init_offsets = (1, 1)
+            results = minimizer(fit_func, init_offsets, **kwargs)
+            east, north = -results.x[0], -results.x[1]
+            vert = float(plan.shift_nmad(-east - init[0], -north - init[1], res)[0])   # np.nanmedian of dh at the optimum
+        self.meta["outputs"]["affine"] = {"shift_x": east + init[0], "shift_y": north + init[1], "shift_z": vert}
+        self.meta["outputs"]["random"] = {"subsample_final": int(n)}
+        self.meta["outputs"]["specific"] = {"n_evaluations": n_eval}
+        return self
 
-    def to_rotations(self) -> tuple[float, float, float]:
-        """Rotations of the estimated transform: none, Nuth and Kaab is a pure translation."""
-        return (0.0, 0.0, 0.0)
-
-    def to_matrix(self) -> np.ndarray:
-        """4x4 translation matrix (affine.py:2532-2541)."""
-        m = np.diag(np.ones(4, dtype=float))
-        m[0, 3] += self.meta["outputs"]["affine"]["shift_x"]
-        m[1, 3] += self.meta["outputs"]["affine"]["shift_y"]
-        m[2, 3] += self.meta["outputs"]["affine"]["shift_z"]
-        return m
-
+    def apply(self, elev, bias_vars=None, resample: bool = True, resampling: str = "bilinear", transform=None, crs=None, z_name=None,
+              resolution=None):
+        """``Coreg.apply`` with the reference's parameters in the reference's order (base.py: ``apply``), plus ``resolution=`` for arrays
+        without a transform; the translation itself is the shared one (``apply_translation``)."""
+        return super().apply(elev, resolution, resample, bias_vars=bias_vars, resampling=resampling, transform=transform, crs=crs, z_name=z_name)

@@ -7,6 +7,7 @@
 //                                                                                             -> least-squares moments (dh_moments_*)
 //   np.median(ref - tba) over the valid pixels                          affine.py:721-770     -> radix selection (select_run.h)
 //   elev + polyval2d(xx, yy, c), cast to the input dtype                biascorr.py:262-311, base.py:491 -> poly2d_apply_kernel
+//   nmad(ref - interp(tba)(shifted points)), DhMinimize's objective      affine.py:617-674     -> dh_shift_*_kernel + two selections
 // The (order+1)^2 least-squares system is solved on the host (xdem_amd/biascorr.py).
 //
 // The moments are taken in normalised coordinates u = (x - cx) / sx, v = (y - cy) / sy with cx = sx = (W_global - 1) / 2 and
@@ -23,6 +24,7 @@
 #include "select.h"
 #include "select_run.h"
 #include "rank_select.h"
+#include "nk_geom.h"
 
 struct xdemhip_dh_plan {
     xdemhip_ctx* ctx = nullptr;
@@ -39,6 +41,12 @@ struct xdemhip_dh_plan {
     int64_t* idx = nullptr;                   // selected pixels (flat indexes, raster order): the drawn ones, or all valid ones on demand
     int64_t n_idx = 0;
     bool drawn = false;                       // xdemhip_dh_subsample was called: the drawn pixels are the selection
+    // shifted-dh evaluations (xdemhip_dh_shift_nmad / _values): made at the first evaluation, kept until the plan goes
+    void* stage = nullptr;                    // dh of one evaluation: H * W values (dense route) or n_idx (list route)
+    int64_t stage_n = 0;
+    unsigned char* sel_scratch = nullptr;     // selection states, successor keys, histograms (scratch_size(1)), then the DhEvalOut block
+    xd::SelWorkspace sel_ws;                  // sample / candidate buffers of the bracketed selection (stage_n >= SEL_BRACKET_MIN_N)
+    int64_t sel_ws_n = 0;
 };
 
 namespace xd {
@@ -280,6 +288,177 @@ __global__ __launch_bounds__(256) void dh_gather_kernel(const T* __restrict__ re
     }
 }
 
+// ---- shifted dh and its NMAD: the objective of DhMinimize ---------------------------------------------------------------------
+// dh = ref[r, c] - bilinear(tba)(r + g.dr, c + g.dc) with the taps and the nodata rule of the Nuth-Kaab step (nk_geom.h), NaN where
+// the interpolated value is.  One pass writes dh of every selected pixel to the plan's staging buffer -- NaN for the others on the
+// dense route -- and, with HIST, counts the leading key digit of the values for the median's selection; the later digit passes and the
+// second selection (|dh - median|) read the staging buffer only.
+template <typename T>
+__device__ __forceinline__ T dh_shift_pixel(const T* __restrict__ tba, const NkGeom& g, int64_t r, int64_t c, T refv) {
+    const BiTap t = bi_locate(g, r, c);
+    const BiVals<T> tv = bi_load<T>(tba, t);
+    T val;
+    const bool ok = bi_value<T>(g, tba, t, tv.a00, tv.a01, tv.a10, tv.a11, val);
+    return ok ? t_sub(refv, val) : (T)NAN;   // (a difference that overflows stays +-inf, as in NumPy: nanmedian keeps it)
+}
+
+// leading-digit counters of a workgroup: DH_HIST_COPIES privatised tables (copy = lane % copies, an odd stride apart: float keys
+// share their sign and exponent bits, every lane of a wave would otherwise hit one counter), flushed with one global add per
+// non-empty counter
+constexpr int DH_HIST_COPIES = 16, DH_HIST_STRIDE = SEL_RADIX + 1;
+template <typename T> __device__ __forceinline__ void dh_hist_count(uint32_t* hc, T v) {
+    if (v == v) atomicAdd(&hc[(int)(key_of(v) >> (8 * (KeyT<T>::passes - 1)))], 1u);
+}
+__device__ __forceinline__ void dh_hist_flush(const uint32_t* h, uint64_t* __restrict__ hist) {
+    __syncthreads();
+    for (int k = threadIdx.x; k < SEL_RADIX; k += blockDim.x) {
+        unsigned long long c = 0;
+        for (int q = 0; q < DH_HIST_COPIES; ++q) c += h[q * DH_HIST_STRIDE + k];
+        if (c) atomicAdd(reinterpret_cast<unsigned long long*>(&hist[k]), c);
+    }
+}
+
+// dense route: the tiles of dh_valid_kernel (lane l of a tile: pixels g * 1024 + 4 l .. + 3, g = 0..3), 16-byte loads of ref and
+// stores of dh and a 4-byte load of the mask where the rasters allow (VEC), one pixel at a time in the last, partial group
+template <typename T, bool VEC, bool HIST>
+__global__ __launch_bounds__(256) void dh_shift_dense_kernel(const T* __restrict__ ref, const T* __restrict__ tba, const uint8_t* __restrict__ valid,
+                                                             NkGeom g, int64_t n, double invW, T* __restrict__ stage, uint64_t* __restrict__ hist) {
+    __shared__ uint32_t h[HIST ? DH_HIST_COPIES * DH_HIST_STRIDE : 1];
+    if (HIST) {
+        for (int k = threadIdx.x; k < DH_HIST_COPIES * DH_HIST_STRIDE; k += blockDim.x) h[k] = 0;
+        __syncthreads();
+    }
+    uint32_t* hc = h + (HIST ? (threadIdx.x % DH_HIST_COPIES) * DH_HIST_STRIDE : 0);
+#pragma unroll
+    for (int gq = 0; gq < 4; ++gq) {
+        const int64_t p0 = (int64_t)blockIdx.x * RANK_TILE + gq * 1024 + (int64_t)threadIdx.x * 4;
+        if (p0 >= n) continue;
+        const bool full = p0 + 4 <= n;
+        const int cnt = full ? 4 : (int)(n - p0);
+        T a[4];
+        uint32_t m4 = 0;
+        if (VEC && full) {
+            load4<T>(ref + p0, a);
+            m4 = *reinterpret_cast<const uint32_t*>(valid + p0);
+        } else {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                a[q] = q < cnt ? ref[p0 + q] : (T)NAN;
+                m4 |= (q < cnt && valid[p0 + q]) ? (1u << (8 * q)) : 0u;
+            }
+        }
+        int64_t r, c;
+        row_col(p0, g.W, invW, r, c);
+        T o[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            o[q] = (T)NAN;
+            if (q < cnt) {
+                if ((m4 >> (8 * q)) & 0xFFu) o[q] = dh_shift_pixel<T>(tba, g, r + g.roff, c, a[q]);
+                if (HIST) dh_hist_count<T>(hc, o[q]);
+                if (++c == g.W) { c = 0; ++r; }
+            }
+        }
+        if (VEC && full) store4<T>(stage + p0, o);
+        else
+            for (int q = 0; q < cnt; ++q) stage[p0 + q] = o[q];
+    }
+    if (HIST) dh_hist_flush(h, hist);
+}
+
+// list route: dh of the listed pixels (the drawn ones, or all valid ones for xdemhip_dh_shift_values), in list order
+template <typename T, bool HIST>
+__global__ __launch_bounds__(256) void dh_shift_list_kernel(const T* __restrict__ ref, const T* __restrict__ tba, const int64_t* __restrict__ idx,
+                                                            int64_t k, NkGeom g, double invW, T* __restrict__ out, uint64_t* __restrict__ hist) {
+    __shared__ uint32_t h[HIST ? DH_HIST_COPIES * DH_HIST_STRIDE : 1];
+    if (HIST) {
+        for (int q = threadIdx.x; q < DH_HIST_COPIES * DH_HIST_STRIDE; q += blockDim.x) h[q] = 0;
+        __syncthreads();
+    }
+    uint32_t* hc = h + (HIST ? (threadIdx.x % DH_HIST_COPIES) * DH_HIST_STRIDE : 0);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < k; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t q = idx[i];
+        int64_t r, c;
+        row_col(q, g.W, invW, r, c);
+        const T d = dh_shift_pixel<T>(tba, g, r + g.roff, c, ref[q]);
+        out[i] = d;
+        if (HIST) dh_hist_count<T>(hc, d);
+    }
+    if (HIST) dh_hist_flush(h, hist);
+}
+
+__device__ __forceinline__ float dh_abs(float v) { return fabsf(v); }
+__device__ __forceinline__ double dh_abs(double v) { return fabs(v); }
+
+// |dh - median| of the staging buffer as an element source of the bracketed selection (select_run.h): nothing is materialised
+template <typename T> struct AbsDevSource {
+    const T* vals;
+    const T* med;    // device slot the first selection's finish kernel wrote
+    T m;
+    struct Raw { T v; };
+    struct Acc {};
+    static size_t lds_bytes(int) { return 0; }
+    __device__ __forceinline__ void setup(unsigned char*, int) { m = *med; }
+    __device__ __forceinline__ void fetch(int64_t p, Raw& r) const { r.v = vals[p]; }
+    __device__ __forceinline__ void blank(Raw& r) const { r.v = (T)NAN; }
+    template <bool ACC> __device__ __forceinline__ bool eval(const Raw& r, int, T& v, uint16_t& b, Acc&) const {
+        v = dh_abs(t_sub(r.v, m));
+        b = 0;
+        return v == v;
+    }
+    __device__ __forceinline__ void finish(Acc&) const {}
+    static constexpr bool HAS_LEAN = false;
+};
+// the same in place, for the plain digit passes (they read an array)
+template <typename T>
+__global__ __launch_bounds__(256) void dh_absdev_kernel(T* __restrict__ stage, int64_t n, const T* __restrict__ med) {
+    const T m = *med;
+    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (int64_t)gridDim.x * blockDim.x) stage[p] = dh_abs(t_sub(stage[p], m));
+}
+
+// What one evaluation hands back (a block behind the selection scratch): filled by the two finish kernels, fetched once.
+struct DhEvalOut {
+    double median, mad;             // in the value dtype, widened
+    unsigned long long count, fail; // values that are not NaN; a bracket of either selection missed or a candidate buffer overflowed
+    double slot;                    // the median in the value dtype: what the second selection subtracts
+};
+// np.nanmedian from a finished selection, on the device (median_from's rule).  `small` = the workspace block of a bracketed selection
+// (select_bracketed_enqueue: flags, rebase shift, low key, counters), nullptr after the plain passes.
+template <typename T>
+__global__ void dh_sel_finish_kernel(const SelState<typename KeyT<T>::type>* st, const uint64_t* succ, const uint64_t* small, int nb_max, int which,
+                                     DhEvalOut* out) {
+    typedef typename KeyT<T>::type K;
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    SelState<K> s = st[0];
+    uint64_t sc = succ[0];
+    if (small) {
+        if (small[2] != 0 || small[3] != 0) out->fail = 1ull;
+        const int rbs = (int)(uint32_t)small[4];
+        const K klo = reinterpret_cast<const K*>(small + 8)[0];
+        const uint64_t* cnt = small + 8 + 3 * nb_max;
+        s.count = cnt[0];
+        s.n_le += cnt[1];
+        s.prefix = (K)((K)(s.prefix >> rbs) + klo);
+        if (sc != ~(uint64_t)0) sc = (uint64_t)(K)((K)((K)sc >> rbs) + klo);
+    }
+    T m = (T)NAN;
+    if (s.count) {
+        const T lo = val_of(s.prefix);
+        if (s.count & 1) m = lo;
+        else {
+            const T hi = (s.n_le > s.count / 2) ? lo : val_of((K)sc);
+            m = (T)((T)(lo + hi) / (T)2);
+        }
+    }
+    if (which == 0) {
+        out->median = (double)m;
+        out->count = s.count;
+        *reinterpret_cast<T*>(&out->slot) = m;
+    } else {
+        out->mad = (double)m;
+    }
+}
+
 // ---- apply: out = cast(double(elev) + polyval2d(x, y, c)) ---------------------------------------------------------------------
 // NumPy's evaluation order (numpy/polynomial/polynomial.py polyval / polyval2d), no contraction (-ffp-contract=off):
 //   t_j = c[K-1, j] + x * 0;  t_j = c[K-2, j] + t_j * x; ... ; t_j = c[0, j] + t_j * x      (polyval(x, c), tensor form)
@@ -511,6 +690,123 @@ int median_typed(xdemhip_dh_plan* P, double* median, int64_t* count) {
     return rc;
 }
 
+// ---- shifted-dh evaluations: buffers the plan keeps, and the sequence of one evaluation ---------------------------------------------
+int ensure_stage(xdemhip_dh_plan* P, int64_t n) {
+    if (P->stage && P->stage_n == n) return XDEMHIP_OK;
+    xdemhip_ctx* ctx = P->ctx;
+    if (P->stage) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(P->stage); P->stage = nullptr; P->stage_n = 0; }
+    const size_t es = P->dtype == XDEMHIP_F32 ? 4 : 8;
+    if (hipMalloc(&P->stage, (size_t)(n > 0 ? n : 1) * es) != hipSuccess) {
+        (void)hipGetLastError();
+        P->stage = nullptr;
+        return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed (dh staging buffer)");
+    }
+    P->stage_n = n;
+    return XDEMHIP_OK;
+}
+int ensure_selection(xdemhip_dh_plan* P, int64_t n) {
+    xdemhip_ctx* ctx = P->ctx;
+    if (!P->sel_scratch && hipMalloc(reinterpret_cast<void**>(&P->sel_scratch), scratch_size(1) + sizeof(DhEvalOut)) != hipSuccess) {
+        (void)hipGetLastError();
+        P->sel_scratch = nullptr;
+        return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed (dh selection scratch)");
+    }
+    if (P->sel_ws_n != n) {
+        (void)hipStreamSynchronize(ctx->stream);
+        sel_ws_free(P->sel_ws);
+        if (n >= SEL_BRACKET_MIN_N) (void)sel_ws_create(ctx, n, P->dtype == XDEMHIP_F32 ? 4 : 8, 1, P->sel_ws);  // (on failure: plain selection)
+        P->sel_ws_n = n;
+    }
+    return XDEMHIP_OK;
+}
+
+NkGeom dh_geom(const xdemhip_dh_plan* P, double shift_x, double shift_y, double res_x, double res_y) {
+    NkGeom g;
+    g.H = P->H; g.W = P->W; g.roff = 0; g.dr = -shift_y / res_y; g.dc = shift_x / res_x; g.rule = P->ctx->nk_nan_rule;
+    return g;
+}
+
+// dh of the plan's selection at a shift into the staging buffer (with_hist: + the leading digit's counts into `hist`)
+template <typename T>
+int launch_shift(xdemhip_dh_plan* P, const NkGeom& g, bool with_hist, uint64_t* hist) {
+    xdemhip_ctx* ctx = P->ctx;
+    const T* ref = static_cast<const T*>(P->ref);
+    const T* tba = static_cast<const T*>(P->tba);
+    T* stage = static_cast<T*>(P->stage);
+    const double invW = 1.0 / (double)P->W;
+    if (P->drawn) {
+        const dim3 grid(grid_for(ctx, P->n_idx, 256, 16)), b(256);
+        if (with_hist) hipLaunchKernelGGL((dh_shift_list_kernel<T, true>), grid, b, 0, ctx->stream, ref, tba, P->idx, P->n_idx, g, invW, stage, hist);
+        else hipLaunchKernelGGL((dh_shift_list_kernel<T, false>), grid, b, 0, ctx->stream, ref, tba, P->idx, P->n_idx, g, invW, stage, hist);
+    } else {
+        const int64_t n = P->H * P->W;
+        const bool vec = (uintptr_t)ref % 16 == 0 && (uintptr_t)stage % 16 == 0 && (uintptr_t)P->valid % 4 == 0;
+        const dim3 grid((unsigned)P->n_tiles), b(256);
+#define XD_DENSE(V, HH) hipLaunchKernelGGL((dh_shift_dense_kernel<T, V, HH>), grid, b, 0, ctx->stream, ref, tba, P->valid, g, n, invW, stage, hist)
+        if (vec) { if (with_hist) XD_DENSE(true, true); else XD_DENSE(true, false); }
+        else { if (with_hist) XD_DENSE(false, true); else XD_DENSE(false, false); }
+#undef XD_DENSE
+    }
+    return hipGetLastError() == hipSuccess ? XDEMHIP_OK : xd_fail(ctx, XDEMHIP_EHIP, "dh_shift kernel launch failed");
+}
+
+// One evaluation: the data pass, the median's selection, |dh - median|'s selection, ONE fetch.  Inputs of SEL_BRACKET_MIN_N values
+// and more take the bracketed route of select_run.h for both selections (a sample, one counting pass, the candidates) with the
+// decoding done by dh_sel_finish_kernel; should a bracket miss -- the integer counts of the counting pass tell -- the evaluation is
+// run again with the plain digit passes, which cannot miss.  Nothing is allocated here once the plan's buffers exist.
+template <typename T>
+int shift_nmad_typed(xdemhip_dh_plan* P, const NkGeom& g, double nfact, double* median, double* nmad, int64_t* count) {
+    typedef typename KeyT<T>::type K;
+    xdemhip_ctx* ctx = P->ctx;
+    const int64_t n = P->drawn ? P->n_idx : P->H * P->W;
+    int rc = ensure_stage(P, n);
+    if (rc == XDEMHIP_OK) rc = ensure_selection(P, n);
+    if (rc) return rc;
+    unsigned char* scratch = P->sel_scratch;
+    DhEvalOut* d_out = reinterpret_cast<DhEvalOut*>(scratch + scratch_size(1));
+    const SelState<K>* d_st = reinterpret_cast<const SelState<K>*>(scratch + OFF_STATE);
+    const uint64_t* d_succ = reinterpret_cast<const uint64_t*>(scratch + off_succ(1));
+    T* stage = static_cast<T*>(P->stage);
+    const T* d_med = reinterpret_cast<const T*>(&d_out->slot);
+    DhEvalOut h;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        const bool plain = attempt == 1 || n < SEL_BRACKET_MIN_N;
+        XD_HIP_CHECK(ctx, hipMemsetAsync(d_out, 0, sizeof(DhEvalOut), ctx->stream));
+        bool queued = false;
+        if (plain) {
+            uint64_t* hist = select_reset<K>(ctx, scratch, 1);
+            rc = launch_shift<T>(P, g, true, hist);
+            if (rc == XDEMHIP_OK) rc = select_enqueue<T>(ctx, stage, nullptr, n, n, nullptr, 1, scratch, SEL_MEDIAN, nullptr, 0, true, nullptr, nullptr, true);
+        } else {
+            rc = launch_shift<T>(P, g, false, nullptr);
+            if (rc == XDEMHIP_OK) rc = select_bracketed_enqueue<T, ArraySource<T>>(ctx, ArraySource<T>{stage, nullptr}, n, 1, scratch, &P->sel_ws, &queued);
+            if (rc == XDEMHIP_OK && !queued) rc = select_enqueue<T>(ctx, stage, nullptr, n, n, nullptr, 1, scratch, SEL_MEDIAN, nullptr);
+        }
+        if (rc) return rc;
+        hipLaunchKernelGGL((dh_sel_finish_kernel<T>), dim3(1), dim3(1), 0, ctx->stream, d_st, d_succ, queued ? P->sel_ws.d_small : (const uint64_t*)nullptr,
+                           P->sel_ws.nb_max, 0, d_out);
+        bool queued2 = false;
+        if (!plain) rc = select_bracketed_enqueue<T, AbsDevSource<T>>(ctx, AbsDevSource<T>{stage, d_med, (T)0}, n, 1, scratch, &P->sel_ws, &queued2);
+        if (rc == XDEMHIP_OK && !queued2) {
+            hipLaunchKernelGGL((dh_absdev_kernel<T>), dim3(grid_for(ctx, n, 256, 16)), dim3(256), 0, ctx->stream, stage, n, d_med);
+            rc = select_enqueue<T>(ctx, stage, nullptr, n, n, nullptr, 1, scratch, SEL_MEDIAN, nullptr);
+        }
+        if (rc) return rc;
+        hipLaunchKernelGGL((dh_sel_finish_kernel<T>), dim3(1), dim3(1), 0, ctx->stream, d_st, d_succ, queued2 ? P->sel_ws.d_small : (const uint64_t*)nullptr,
+                           P->sel_ws.nb_max, 1, d_out);
+        if (hipGetLastError() != hipSuccess) return xd_fail(ctx, XDEMHIP_EHIP, "dh selection kernel launch failed");
+        rc = xd_d2h(ctx, &h, d_out, sizeof h);
+        if (rc == XDEMHIP_OK) rc = xd_sync(ctx);
+        if (rc) return rc;
+        if (!h.fail) break;
+    }
+    *count = (int64_t)h.count;
+    if (h.count == 0) return xd_fail(ctx, XDEMHIP_EINVAL, "no valid points");
+    *median = h.median;
+    *nmad = (double)(T)((T)nfact * (T)h.mad);   // nfact * np.nanmedian(...): the Python float is a weak scalar (xdemhip_nmad's rule)
+    return XDEMHIP_OK;
+}
+
 int upload_or_use(xdemhip_ctx* ctx, const void* src, size_t bytes, int memspace, void** dptr, bool* own) {
     *own = false;
     if (memspace == XDEMHIP_DEVICE) { *dptr = const_cast<void*>(src); return XDEMHIP_OK; }
@@ -546,6 +842,9 @@ void xdemhip_dh_destroy(xdemhip_dh_plan* P) {
     if (P->valid) (void)hipFree(P->valid);
     if (P->tile_off) (void)hipFree(P->tile_off);
     if (P->idx) (void)hipFree(P->idx);
+    if (P->stage) (void)hipFree(P->stage);
+    if (P->sel_scratch) (void)hipFree(P->sel_scratch);
+    sel_ws_free(P->sel_ws);
     delete P;
 }
 
@@ -730,6 +1029,65 @@ int xdemhip_dh_values(xdemhip_dh_plan* P, void* dh_out, int64_t* col_out, int64_
         if (d_dh) (void)hipFree(d_dh);
         if (d_col) (void)hipFree(d_col);
         if (d_row) (void)hipFree(d_row);
+    }
+    return rc;
+}
+
+int xdemhip_dh_shift_nmad(xdemhip_dh_plan* P, double shift_x, double shift_y, double res_x, double res_y, double nfact, double* median, double* nmad,
+                          int64_t* count) {
+    XdFetchScope fetch_scope_(P ? P->ctx : nullptr);
+    if (!P) return XDEMHIP_EINVAL;
+    xdemhip_ctx* ctx = P->ctx;
+    if (!median || !nmad || !count) return xd_fail(ctx, XDEMHIP_EINVAL, "null argument");
+    if (!(res_x > 0) || !(res_y > 0) || !isfinite(shift_x) || !isfinite(shift_y))
+        return xd_fail(ctx, XDEMHIP_EINVAL, "xdemhip_dh_shift_nmad: finite shifts and positive resolutions");
+    *count = 0;
+    if ((P->drawn ? P->n_idx : P->n_valid) == 0) return xd_fail(ctx, XDEMHIP_EINVAL, "no valid points");
+    XD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    if (!P->drawn) { const int rc_ = ensure_mask(P); if (rc_) return rc_; }
+    const NkGeom g = dh_geom(P, shift_x, shift_y, res_x, res_y);
+    const xdemhip_allreduce_fn hook = ctx->allreduce;   // (one process's pixels: local selections, as in xdemhip_dh_median)
+    ctx->allreduce = nullptr;
+    const int rc = P->dtype == XDEMHIP_F32 ? shift_nmad_typed<float>(P, g, nfact, median, nmad, count)
+                                           : shift_nmad_typed<double>(P, g, nfact, median, nmad, count);
+    ctx->allreduce = hook;
+    return rc;
+}
+
+int xdemhip_dh_shift_values(xdemhip_dh_plan* P, double shift_x, double shift_y, double res_x, double res_y, void* dh_out, int memspace, int64_t* count) {
+    XdFetchScope fetch_scope_(P ? P->ctx : nullptr);
+    if (!P) return XDEMHIP_EINVAL;
+    xdemhip_ctx* ctx = P->ctx;
+    if (!dh_out) return xd_fail(ctx, XDEMHIP_EINVAL, "null argument");
+    if (memspace != XDEMHIP_HOST && memspace != XDEMHIP_DEVICE) return xd_fail(ctx, XDEMHIP_EINVAL, "bad memspace");
+    if (!(res_x > 0) || !(res_y > 0) || !isfinite(shift_x) || !isfinite(shift_y))
+        return xd_fail(ctx, XDEMHIP_EINVAL, "xdemhip_dh_shift_values: finite shifts and positive resolutions");
+    XD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    int rc = ensure_valid_idx(P);
+    if (rc) return rc;
+    const int64_t k = P->n_idx;
+    if (count) *count = k;
+    if (k == 0) return xd_fail(ctx, XDEMHIP_EINVAL, "no valid points");
+    const size_t es = P->dtype == XDEMHIP_F32 ? 4 : 8;
+    void* d_dh = dh_out;
+    if (memspace == XDEMHIP_HOST) {   // (through the staging buffer of the evaluations: it holds at least the selection)
+        rc = ensure_stage(P, P->drawn ? P->n_idx : P->H * P->W);
+        if (rc) return rc;
+        d_dh = P->stage;
+    }
+    const NkGeom g = dh_geom(P, shift_x, shift_y, res_x, res_y);
+    const double invW = 1.0 / (double)P->W;
+    const dim3 grid(grid_for(ctx, k, 256, 16));
+    if (P->dtype == XDEMHIP_F32)
+        hipLaunchKernelGGL((dh_shift_list_kernel<float, false>), grid, dim3(256), 0, ctx->stream, static_cast<const float*>(P->ref),
+                           static_cast<const float*>(P->tba), P->idx, k, g, invW, static_cast<float*>(d_dh), (uint64_t*)nullptr);
+    else
+        hipLaunchKernelGGL((dh_shift_list_kernel<double, false>), grid, dim3(256), 0, ctx->stream, static_cast<const double*>(P->ref),
+                           static_cast<const double*>(P->tba), P->idx, k, g, invW, static_cast<double*>(d_dh), (uint64_t*)nullptr);
+    if (hipGetLastError() != hipSuccess) return xd_fail(ctx, XDEMHIP_EHIP, "dh_shift_list_kernel launch failed");
+    if (memspace == XDEMHIP_HOST) {
+        if (hipMemcpyAsync(dh_out, d_dh, (size_t)k * es, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) return xd_fail(ctx, XDEMHIP_EHIP, "D2H copy failed");
+        rc = xd_sync(ctx);
     }
     return rc;
 }

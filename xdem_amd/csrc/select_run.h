@@ -836,15 +836,18 @@ int run_bin_sums(xdemhip_ctx* ctx, const Src& src, int64_t n, int nb, double* d_
     return xd_allreduce_device(ctx, d_counts, nb, XDEMHIP_RED_SUM_U64);
 }
 
-// Bracketed selection over an element source.  *done = false (and `out` meaningless) when the route is not available --
-// small input, no workspace, plain mode, some rank cannot -- or when a bracket missed / a buffer overflowed: the caller
-// then runs the plain selection on materialised arrays.
+// The device work of the bracketed selection over an element source, queued on the context's stream without a host synchronisation
+// (unless a reduction hook is installed): sample, brackets, the counting pass, the exact selection among the candidates.  *queued =
+// false when the route is not available -- small input, no workspace, plain mode, some rank cannot.  What it leaves on the device:
+// states and successor keys of the candidates' selection in `scratch` (rebased keys), and in ws->d_small the flags ([2] buffer
+// overflow, [3] a bracket missed), the rebase shift (low half of word [4]), the brackets' low keys (from word 8) and the counters
+// [3][nb] total / below / inside (from word 8 + 3 nb_max).  run_select_bracketed below fetches and decodes them on the host;
+// biascorr.hip decodes them in a kernel, so that a second selection can depend on the first without a round trip.
 template <typename T, typename Src>
-int run_select_bracketed(xdemhip_ctx* ctx, const Src& src, int64_t n, int nb, unsigned char* scratch,
-                         std::vector<SelResult<typename KeyT<T>::type>>& out, SelWorkspace* ws, bool* done, bool* passed = nullptr,
-                         const std::function<int()>* before_sync = nullptr /* queues the caller's own result copies behind the route */) {
+int select_bracketed_enqueue(xdemhip_ctx* ctx, const Src& src, int64_t n, int nb, unsigned char* scratch, SelWorkspace* ws, bool* queued,
+                             bool* passed = nullptr) {
     typedef typename KeyT<T>::type K;
-    *done = false;
+    *queued = false;
     if (passed) *passed = false;  // set once the pass over all elements has been queued (sources with side effects rely on it)
     static const bool disabled = getenv("XDEMHIP_NO_BRACKET") != nullptr;  // (A/B timing knob)
     const bool plain = disabled || ctx->selection_mode == 1 || !ws || !ws->d_small || nb > ws->nb_max || ws->es != sizeof(T) || nb > MAX_BINS_PER_SWEEP ||
@@ -910,6 +913,25 @@ int run_select_bracketed(xdemhip_ctx* ctx, const Src& src, int64_t n, int nb, un
     rc = select_enqueue<T>(ctx, static_cast<const T*>(ws->c_vals), ws->c_bins, ws->c_cap, n / 32 + 1, d_flags + 1, nb, scratch, SEL_GIVEN, d_given,
                            0, true, d_klo, d_rbs);
     if (rc) return rc;
+    *queued = true;
+    return XDEMHIP_OK;
+}
+
+// Bracketed selection over an element source.  *done = false (and `out` meaningless) when the route is not available --
+// small input, no workspace, plain mode, some rank cannot -- or when a bracket missed / a buffer overflowed: the caller
+// then runs the plain selection on materialised arrays.
+template <typename T, typename Src>
+int run_select_bracketed(xdemhip_ctx* ctx, const Src& src, int64_t n, int nb, unsigned char* scratch,
+                         std::vector<SelResult<typename KeyT<T>::type>>& out, SelWorkspace* ws, bool* done, bool* passed = nullptr,
+                         const std::function<int()>* before_sync = nullptr /* queues the caller's own result copies behind the route */) {
+    typedef typename KeyT<T>::type K;
+    *done = false;
+    bool queued = false;
+    int rc = select_bracketed_enqueue<T, Src>(ctx, src, n, nb, scratch, ws, &queued, passed);
+    if (rc || !queued) return rc;
+    const uint64_t* d_ctr = ws->d_small;
+    const K* d_klo = reinterpret_cast<const K*>(ws->d_small + 8);
+    const uint64_t* d_cnt = ws->d_small + 8 + 3 * ws->nb_max;
     std::vector<uint64_t> cnt(3 * nb);
     std::vector<K> klo(nb);
     uint64_t h_ctr[5];
