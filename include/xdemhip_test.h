@@ -10,9 +10,7 @@
  *   "nk_narrow"          -1 (default) sample brackets of the one-pass step narrowed by the measured rank offsets, 0 / 1 / 2 fixed.
  *   "vario_grid"         1 (default) raster-sampled points run the integer-lattice pair kernels, 0 always the float64-coordinate ones.
  *   "vario_runs"         1 (default) run-length counting pass of the exact-Dowd route on the Morton-ordered copy, 0 per-pair counters.
- *   "vario_sort"         1 (default) the host side uploads a Morton-ordered copy of every pair block, 0 one copy in the caller's order.
- * Measurement builds (-DXD_EXPERIMENT, csrc/Makefile: libxdemhip_exp*.so) add "terrain_store", "terrain_rows", "terrain_sync",
- * "vario_deff"; the product library refuses those names. */
+ *   "vario_sort"         1 (default) the host side uploads a Morton-ordered copy of every pair block, 0 one copy in the caller's order. */
 #pragma once
 #include "xdemhip.h"
 #ifdef __cplusplus

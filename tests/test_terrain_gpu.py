@@ -1053,3 +1053,23 @@ def test_alloc_planes_with_a_probe_keeps_one_of_the_candidates(terrain):
     assert torch.equal(torch.nan_to_num(planes, nan=-1e30), torch.nan_to_num(want, nan=-1e30))
     plain = terrain.alloc_planes(len(attrs), n, n, torch.float32, ctx, backing="auto")
     assert not hasattr(plain, "_xdem_calibration_ms")
+
+
+def test_retired_measurement_switches_are_refused_and_leave_the_context_usable(terrain):
+    """The four switches of the retired measurement builds ("terrain_store", "terrain_rows", "terrain_sync", "vario_deff") are
+    names the library no longer knows: the binding's set_option (which now routes them to xdemhip_set_option) raises, the
+    test-switch entry point refuses them too, and the refusals leave the context as it was -- the slope plane of a 64 x 96
+    float32 raster is the same before and after, bit for bit."""
+    from xdem_amd import _lib
+
+    ctx = _lib.default_context()
+    dem = _dem((64, 96), seed=3)
+    before = terrain.get_terrain_attribute(dem, "slope", resolution=10.0)
+    for name in ("terrain_store", "terrain_rows", "terrain_sync", "vario_deff"):
+        assert name not in ctx.TEST_SWITCHES
+        with pytest.raises(_lib.XdemHipError):
+            ctx.set_option(name, 1)
+        assert name not in ctx.options
+        assert ctx._L.xdemhip_set_test_switch(ctx.handle, name.encode(), 1) != 0
+    after = terrain.get_terrain_attribute(dem, "slope", resolution=10.0)
+    assert np.isfinite(after).any() and np.array_equal(before, after, equal_nan=True)

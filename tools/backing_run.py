@@ -13,7 +13,7 @@ import torch
 
 from xdem_amd import _lib, terrain
 
-if os.environ.get("XD_LIB"):   # A/B of library builds across processes (measurement variants: xdem_amd/csrc/Makefile)
+if os.environ.get("XD_LIB"):   # A/B of library builds across processes
     _lib.LIB_PATH = os.environ["XD_LIB"]
 from xdem_amd.synth import fbm_torch
 

@@ -14,7 +14,7 @@ import torch
 import bench
 from xdem_amd import _lib, coreg
 
-if os.environ.get("NK_LIB"):  # A/B of library builds across processes (measurement variants: xdem_amd/csrc/Makefile)
+if os.environ.get("NK_LIB"):  # A/B of library builds across processes
     _lib.LIB_PATH = os.environ["NK_LIB"]
 
 m = int(sys.argv[1]) if len(sys.argv) > 1 else 20000

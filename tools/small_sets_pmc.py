@@ -1,5 +1,5 @@
 """Five launches each of the small attribute sets (slope Florinsky / slope+aspect Horn / hillshade / full 11) at 40000^2 -- the
-command the SQ counters of the small sets are collected on (rocprofv3 --pmc passes, tools/sessions/gpu_r05d.sh).  (measurement tool)"""
+command the SQ counters of the small sets are collected on (rocprofv3 --pmc passes of their own).  (measurement tool)"""
 import os
 import sys
 

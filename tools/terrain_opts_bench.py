@@ -1,6 +1,6 @@
 """A/B timing of runtime options of the fused terrain kernel on one GPU (measurement tool).
 
-  python tools/terrain_opts_bench.py [--size 40000] [--reps 4] [--rounds 3] [--opts "terrain_sync=0,2,4,8;terrain_order=0,1"]
+  python tools/terrain_opts_bench.py [--size 40000] [--reps 4] [--rounds 3] [--opts "terrain_order=0,1;terrain_stream=1,256"]
 
 Times the headline launch (Florinsky, 11 attributes, float32, device-resident) for every listed value of every option (the
 others at their defaults), interleaved over `rounds` so that the box's clock drift hits all settings alike.  Times are the
@@ -23,7 +23,7 @@ def main():
     ap.add_argument("--size", type=int, default=40000)
     ap.add_argument("--reps", type=int, default=4)
     ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--opts", default="terrain_sync=0,2,4,8;terrain_order=0,1")
+    ap.add_argument("--opts", default="terrain_order=0,1;terrain_stream=1,256")
     ap.add_argument("--combos", default="")
     ap.add_argument("--json", default=None)
     ap.add_argument("--planes", default="torch", choices=("torch", "scattered"), help="torch.empty planes or the library's scattered backing")

@@ -293,7 +293,7 @@ int xdemhip_synchronize(xdemhip_ctx* ctx) {
 
 // Options of the PRODUCT (include/xdemhip.h): what a caller of the C-ABI may want to set.  Everything that only selects between
 // internal routes that must agree -- for the route-agreement tests and for measurements -- is a TEST SWITCH
-// (xdemhip_set_test_switch, include/xdemhip_test.h); switches of measurement builds exist under -DXD_EXPERIMENT only.
+// (xdemhip_set_test_switch, include/xdemhip_test.h).
 namespace {
 struct XdOpt { const char* name; int lo, hi; int xdemhip_ctx::*field; const char* what; };
 const XdOpt kOptions[] = {
@@ -319,12 +319,6 @@ const XdOpt kTestSwitches[] = {
     {"vario_grid", 0, 1, &xdemhip_ctx::vario_grid, "vario_grid: 0 or 1"},
     {"vario_runs", 0, 1, &xdemhip_ctx::vario_runs, "vario_runs: 0 or 1"},
     {"vario_sort", 0, 1, &xdemhip_ctx::vario_sort, "vario_sort: 0 or 1"},
-#ifdef XD_EXPERIMENT   // measurement builds (csrc/Makefile: libxdemhip_exp*.so) only
-    {"terrain_store", 0, 1, &xdemhip_ctx::terrain_store, "terrain_store: 0 direct, 1 staged row stores"},
-    {"terrain_rows", 0, 1000, &xdemhip_ctx::terrain_rows, "terrain_rows: 0, 16, 24, 32 or an occupancy experiment >= 100"},
-    {"terrain_sync", 0, 32, &xdemhip_ctx::terrain_sync, "terrain_sync: 0 or a power of two <= 32"},
-    {"vario_deff", 0, 1 << 20, &xdemhip_ctx::vario_deff, "vario_deff: 0 .. 2^20"},
-#endif
 };
 int xd_set_from(xdemhip_ctx* ctx, const XdOpt* tab, size_t n, const char* name, int value, bool* found) {
     *found = false;
@@ -367,7 +361,6 @@ int xdemhip_set_test_switch(xdemhip_ctx* ctx, const char* name, int value) {
     if (!ctx || !name) return XDEMHIP_EINVAL;
     if (strcmp(name, "terrain_stream") == 0 && !(value == 0 || value == 1 || value == 2 || value == 3 || value == 128 || value == 256 || value == 512))
         return xd_fail(ctx, XDEMHIP_EINVAL, "terrain_stream: 0, 1, 2, 3, 128, 256 or 512");
-    if (strcmp(name, "terrain_sync") == 0 && (value & (value - 1))) return xd_fail(ctx, XDEMHIP_EINVAL, "terrain_sync: 0 or a power of two <= 32");
     bool found = false;
     const int rc = xd_set_from(ctx, kTestSwitches, sizeof kTestSwitches / sizeof kTestSwitches[0], name, value, &found);
     if (found) return rc;

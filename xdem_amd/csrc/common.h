@@ -33,16 +33,12 @@ struct xdemhip_ctx {
     int nk_fused_dist = 1;   // option "nk_fused_dist": 1 partitioned Nuth-Kaab plans (reduction hook + xdemhip_set_rank) take the one-pass step too: 5-10 all-reduces per step (default), 0 the plain route
     int host_chunk_rows = 0; // option "host_chunk_rows": rows per chunk of host-buffer terrain calls (0 = from the budget); the mp_config tile size
     int host_chunk_mb = 0;   // device budget (MiB) of one row chunk of host-buffer terrain calls; 0 = default
-    int terrain_store = 0;   // option "terrain_store": 0 direct stores (default), 1 staged 1 KiB row stores where possible (measured slower)
-    int terrain_rows = 0;    // option "terrain_rows": tile height of the fused terrain kernel (0 automatic, 16, 24, 32)
     int nk_narrow = -1;      // option "nk_narrow": sample brackets of the one-pass Nuth-Kaab step 2^-k as wide as the rule (-1 = adaptive: from the offsets measured in earlier steps)
     int vario_runs = 1;      // option "vario_runs": run-length counting pass of the bracketed Dowd selection when a Morton-ordered copy is linked (0 = per-pair counters)
-    int vario_deff = 0;      // option "vario_deff": design effect assumed for the pair samples of the bracketed Dowd selection (0 = built-in rule)
     int vario_sort = 1;      // option "vario_sort": the Python side uploads the points of a pair block in Morton order (run-length accumulation of the pair kernels)
     int nk_predict = 1;      // option "nk_predict": 1 a settled one-pass Nuth-Kaab step takes its brackets from the previous step's exact medians moved by the model (no sample kernels, no digit passes over samples; default), 0 every step samples
     int nk_fused = 1;        // option "nk_fused": 1 the Nuth-Kaab step of large single-GPU plans is ONE data pass (14 B/pixel: dh, its median's counting and the aspect-bin counting against sample brackets with per-pixel margins; default), 0 the two passes of round 3
     int terrain_stream = 1;  // option "terrain_stream": 1 streaming strips for the raster interior where they apply (default), 0 tiles only; 128 / 256 / 512 = band height
-    int terrain_sync = 0;    // option "terrain_sync": workgroup barrier every N output rows of the direct-store march (0 none; N a power of two)
     int terrain_order = 0;   // option "terrain_order": 0 one band of tiles per XCD (default), 1 natural order (XCDs interleave along a tile row); strips only: 2 permuted, 3 column-major (measurement)
     int terrain_window_lds = 1;  // option "terrain_window_lds": 1 LDS-tiled window kernel for window sizes != 3 (default), 0 the per-pixel form (its check)
     int terrain_ring_wait = 0;  // option "terrain_ring_wait": 1 = the streaming strips drain every VMEM operation before reading a refilled ring block (test switch for the counted wait)

@@ -51,21 +51,6 @@ __device__ __forceinline__ uint32_t* sel_mask_ptr(uint32_t* a, uint32_t* b, unsi
     return (uint32_t*)(lp)(uintptr_t)r;
 }
 
-// Loads through buffer descriptors: address = descriptor base + per-lane byte offset (a loop-invariant register) + a scalar byte
-// offset -- the row of the chunk -- added by the load unit itself: no vector instruction forms an address inside the row loop
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t fz_rsrc(const void* base) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, 0xFFFFFFFF, 0x00020000);
-}
-__device__ __forceinline__ float fz_bufload(__amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff, float) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)voff, (int)soff, 2 /* nt */));
-}
-__device__ __forceinline__ double fz_bufload(__amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff, double) {
-    return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r, (int)voff, (int)soff, 2));
-}
-__device__ __forceinline__ uint16_t fz_bufload16(__amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff) {
-    return (uint16_t)__builtin_amdgcn_raw_buffer_load_b16(r, (int)voff, (int)soff, 2);
-}
-
 template <typename T> struct FzEps;   // relative slack that covers the roundings of y^ (fast reciprocal) and of y itself
 template <> struct FzEps<float> { static constexpr float rel = 4e-6f, grow = 1.00002f, tiny = 1e-37f; };
 template <> struct FzEps<double> { static constexpr double rel = 1e-14, grow = 1.0000000001, tiny = 1e-300; };
@@ -292,30 +277,14 @@ __device__ __forceinline__ void nk_sums_reduce(const double* __restrict__ wg_sum
     if (t < 5) out5[t] = s_part[0][t];
 }
 
-#ifndef XD_NKZ_ROWS      // (measurement builds override the two pipeline constants of the one-pass kernel)
-#define XD_NKZ_ROWS 8
-#endif
-#ifndef XD_NKZ_PF
-#define XD_NKZ_PF 4
-#endif
-#ifndef XD_NKZ_CAP      // staging slots of the bin candidates per workgroup (float32)
-#define XD_NKZ_CAP 1024
-#endif
-#ifndef XD_NKZ_LB       // workgroups per CU the register allocation aims at
-#define XD_NKZ_LB 7
-#endif
-#ifndef XD_NKZ_BUFFER   // 1: loads through buffer descriptors, 0: global loads from uniform row pointers + 32-bit offsets
-#define XD_NKZ_BUFFER 0
-#endif
-constexpr int NKZ_ROWS = XD_NKZ_ROWS;      // rows between two looks at the staging buffers
-constexpr int NKZ_PF = XD_NKZ_PF;          // rows of loads in flight per wave
-// staging slots per workgroup and kind (flushed once fewer than 2 x NKZ_ROWS rows would still fit; float64: static LDS stays < 48 KiB)
-template <typename T> struct NkzCap { static constexpr int v = sizeof(T) == 4 ? XD_NKZ_CAP : 1024; };
+constexpr int NKZ_ROWS = 8;      // rows between two looks at the staging buffers
+constexpr int NKZ_PF = 4;        // rows of loads in flight per wave
+constexpr int NKZ_CAP = 1024;    // staging slots per workgroup and kind (flushed once fewer than 2 x NKZ_ROWS rows would still fit; float64: static LDS stays < 48 KiB)
 template <typename T> struct FzPair { T lo, hi; };
 
 constexpr int NKZ_CHUNK_MAX = 256;   // rows of a workgroup's chunk (row-tap table in LDS)
 template <typename T, int RULE>   // (RULE 2 = rules 2 / 3 through the bad-bit mask: six more registers -> one workgroup per CU fewer instead of spills; float64 rasters: 5 / 4 -- what the allocator reaches)
-__global__ __launch_bounds__(256, (sizeof(T) == 8 ? (RULE == 2 ? 4 : 5) : (RULE == 2 ? XD_NKZ_LB - 1 : XD_NKZ_LB))) void nk_fused_kernel(const T* __restrict__ ref, const T* __restrict__ tba, const T* __restrict__ slope_tan,
+__global__ __launch_bounds__(256, (sizeof(T) == 8 ? (RULE == 2 ? 4 : 5) : (RULE == 2 ? 6 : 7))) void nk_fused_kernel(const T* __restrict__ ref, const T* __restrict__ tba, const T* __restrict__ slope_tan,
                                                        const nk_bin_t* __restrict__ bcache, NkGeom g, int64_t row0, int64_t row1, int64_t nbuf,
                                                        int nb, int copies, const typename KeyT<T>::type* __restrict__ klo_p,
                                                        const typename KeyT<T>::type* __restrict__ khi_p, const T* vhat_p, const T* delta_p,
@@ -327,7 +296,6 @@ __global__ __launch_bounds__(256, (sizeof(T) == 8 ? (RULE == 2 ? 4 : 5) : (RULE 
                                                        double* wg_sums /* [workgroups][5]: nk_sums_reduce adds them up in a fixed order */,
                                                        const uint64_t* __restrict__ badbits = nullptr, int64_t bad_wpr = 0) {
     typedef typename KeyT<T>::type K;
-    constexpr int NKZ_CAP = NkzCap<T>::v;
     constexpr int SEG = NKZ_CAP / 4;      // staging slots of ONE wave: waves reserve in their own segment with a scalar counter --
                                           // no LDS atomic with return and its round trip on the path of every row (bin candidates are
                                           // ~7 % of the pixels: practically every row of every wave holds some)
@@ -464,23 +432,12 @@ __global__ __launch_bounds__(256, (sizeof(T) == 8 ? (RULE == 2 ? 4 : 5) : (RULE 
     double hl = 0.0;
     struct Pre { T b0, b1, rv, st; nk_bin_t bin; uint32_t bw; };
     Pre pre[NKZ_PF];
-    // (wave-uniform, and said so: the descriptors below must sit in scalar registers -- a descriptor the compiler takes for
-    // lane-varying is read back lane by lane in a loop around every load)
+    // (wave-uniform, and said so: the row pointers below must sit in scalar registers)
     const uint64_t rb0_u = (uint64_t)((i0 - g.roff) * g.W);
     const int64_t rb0 = (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(rb0_u >> 32)) << 32) |
                                   (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)rb0_u));
-    // buffer descriptors: the three rasters indexed by the output pixel from the chunk's first row, tba from the chunk's first
-    // tap row (tap rows ascend with the output row; rows whose taps leave the raster are discarded anyway and read row k_base)
-    const int k_base = __builtin_amdgcn_readfirstlane((tab[0].flags & 1) ? tab[0].k0l : 0);
-#if XD_NKZ_BUFFER
-    const __amdgpu_buffer_rsrc_t r_tba = fz_rsrc(tba + (int64_t)k_base * g.W);
-    const __amdgpu_buffer_rsrc_t r_ref = fz_rsrc(ref + rb0);
-    const __amdgpu_buffer_rsrc_t r_st = fz_rsrc(slope_tan + rb0);
-    const __amdgpu_buffer_rsrc_t r_bin = fz_rsrc(bcache + rb0);
-#endif
     const uint32_t wbytes = (uint32_t)g.W * (uint32_t)sizeof(T), wbytes2 = (uint32_t)g.W * (uint32_t)sizeof(nk_bin_t);
     const uint32_t ob = jl * (uint32_t)sizeof(T), ob2 = jl * (uint32_t)sizeof(nk_bin_t);
-    [[maybe_unused]] auto tap_row = [&](int k) -> uint32_t { return (uint32_t)((k > k_base ? k : k_base) - k_base) * wbytes; };   // (scalar)
     auto issue = [&](int rr, Pre& q) {  // rows past the chunk repeat its last row
         const int rc = rr < nrow ? rr : nrow - 1;
         const int tk = __builtin_amdgcn_readfirstlane(tab[rc].k0l), tf = __builtin_amdgcn_readfirstlane(tab[rc].flags);
@@ -490,15 +447,6 @@ __global__ __launch_bounds__(256, (sizeof(T) == 8 ? (RULE == 2 ? 4 : 5) : (RULE 
         } else {
             q.bw = 0;
         }
-#if XD_NKZ_BUFFER
-        const uint32_t so_t = tap_row(tk + ((tf >> 1) & 1));
-        q.b0 = fz_bufload(r_tba, c0b, so_t, T());
-        q.b1 = fz_bufload(r_tba, c1b, so_t, T());
-        const uint32_t so_r = (uint32_t)rc * wbytes;
-        q.rv = fz_bufload(r_ref, ob, so_r, T());
-        q.st = fz_bufload(r_st, ob, so_r, T());
-        q.bin = (nk_bin_t)__builtin_amdgcn_raw_buffer_load_b8(r_bin, (int)ob2, (int)((uint32_t)rc * wbytes2), 2);
-#else
         const char* rowp = reinterpret_cast<const char*>(tba + (int64_t)(tk + ((tf >> 1) & 1)) * g.W);
         q.b0 = __builtin_nontemporal_load(reinterpret_cast<const T*>(rowp + c0b));
         q.b1 = __builtin_nontemporal_load(reinterpret_cast<const T*>(rowp + c1b));
@@ -506,7 +454,6 @@ __global__ __launch_bounds__(256, (sizeof(T) == 8 ? (RULE == 2 ? 4 : 5) : (RULE 
         q.rv = __builtin_nontemporal_load(reinterpret_cast<const T*>(reinterpret_cast<const char*>(ref + rb0) + o_b));
         q.st = __builtin_nontemporal_load(reinterpret_cast<const T*>(reinterpret_cast<const char*>(slope_tan + rb0) + o_b));
         q.bin = __builtin_nontemporal_load(reinterpret_cast<const nk_bin_t*>(reinterpret_cast<const char*>(bcache + rb0) + ((uint32_t)rc * wbytes2 + ob2)));
-#endif
     };
     // sums of y^ and of the correction terms: float32 partial sums (y^, y^ y^ folded into float64 every NKZ_PF rows; the three
     // correction sums scale a term ~1e-3 of the total and stay float32 over the chunk)
@@ -529,13 +476,8 @@ __global__ __launch_bounds__(256, (sizeof(T) == 8 ? (RULE == 2 ? 4 : 5) : (RULE 
                 if (have == k0l) {
                     top = hl;
                 } else {  // chunk start, or a step of the tap row other than +1: fetch the upper row
-#if XD_NKZ_BUFFER
-                    const uint32_t so_u = tap_row(k0l);
-                    top = hlerp(fz_bufload(r_tba, c0b, so_u, T()), fz_bufload(r_tba, c1b, so_u, T()));
-#else
                     const char* up = reinterpret_cast<const char*>(tba + (int64_t)k0l * g.W);
                     top = hlerp(*reinterpret_cast<const T*>(up + c0b), *reinterpret_cast<const T*>(up + c1b));
-#endif
                 }
                 double bot = top;
                 if (fl & 2) bot = hlerp(b0v, b1v);

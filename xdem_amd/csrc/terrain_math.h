@@ -66,7 +66,6 @@ struct TerrainParams {
     // over the window; |w| <= DBL_EPSILON -> 0 = skipped, as scipy.ndimage does) for zx, zy, zxx, zyy, zxy: used by the
     // rare exact-cancellation path of march_column (see ref_order_sum).
     double wref[5][25];
-    int slot[N_ATTR];  // attribute -> index among the requested planes (staged row stores of terrain.hip)
 };
 
 // ---- the reference's divided convolution kernels (host side) -------------------------------------------
@@ -371,7 +370,7 @@ template <> struct DegScale<double> { static XD_HD double v() { return 57.295779
 // Output sinks.  Planes = one pointer per attribute plane (null when not requested).  DirectSink stores every value
 // straight to its plane: pixels are addressed by a 32-bit BYTE offset from the (wave-uniform) plane pointer at the tile
 // origin, which maps to the scalar-base + VGPR-offset store form; the offset of output row i is o0 + i * ostride (a tile
-// spans far less than 4 GiB per plane).  (terrain.hip adds a sink that stages rows in LDS for 1 KiB row stores.)
+// spans far less than 4 GiB per plane).
 template <typename TOUT> struct Planes { TOUT* p[N_ATTR]; };
 // PTR_COPY: copy the plane pointer through a scalar register inside the store's asm text (see put<>); kernels whose plane
 // pointers are never spilled to VGPR lanes (no v_readlane in their code: tests/test_cabi_and_host.py checks the ISA of the
@@ -380,7 +379,6 @@ template <typename TOUT, bool PTR_COPY = true> struct DirectSink {
     typedef TOUT out_t;
     Planes<TOUT> org;
     uint32_t o0, ostride, o;
-    uint32_t sync_n = 0;  // workgroup barrier after every sync_n-th output row (a power of two; 0 = never): option "terrain_sync"
     XD_HD void begin_row(int i) {
         // byte offset of output row i: o0 + i * ostride with the product formed on the SCALAR unit (i and ostride are
         // wave-uniform) -- one v_add_u32 per row.  (Left to itself hipcc forms a quarter-rate v_mad_u64_u32 per row, or, for the
@@ -396,46 +394,27 @@ template <typename TOUT, bool PTR_COPY = true> struct DirectSink {
 #endif
     }
     template <int K> XD_HD void put(TOUT v) {
-#if defined(XD_NOSTORE)  // (measurement builds: all the math, no output traffic)
-        if (v != (TOUT)12345.678)  return;
-#endif
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(XD_PLAINSTORE)
-        // Streaming, write-through plane stores (`global_store_dword ... nt sc1`; XD_STORE_BITS overrides the bits in
-        // measurement builds): the planes are written once and never read back by this kernel.  Measured at 40000^2 in one
-        // session: plain 15.76 ms, `nt` 15.29, `nt sc1` 15.02, `nt sc0 sc1` 15.05, `sc0 sc1` 15.38.
-#ifndef XD_STORE_BITS
-#define XD_STORE_BITS "nt sc1"
-#endif
+#if defined(__HIP_DEVICE_COMPILE__)
+        // Streaming, write-through plane stores (`global_store_dword ... nt sc1`): the planes are written once and never read
+        // back by this kernel.  Measured at 40000^2 in one session: plain 15.76 ms, `nt` 15.29, `nt sc1` 15.02,
+        // `nt sc0 sc1` 15.05, `sc0 sc1` 15.38.
         if constexpr (sizeof(TOUT) == 4) {
             // The plane pointer goes through a scalar copy inside the asm: a pointer the compiler has just restored from a spill
             // with v_readlane (VALU write of an SGPR) may not be read by a VMEM instruction for 5 wait states -- the compiler
             // inserts them for its own instructions, not for inline asm, and the runtime-mask kernels faulted without them.
             // A SALU read of a VALU-written SGPR and a VMEM read of a SALU-written SGPR need none; `s_nop 4` instead of the
-            // copy (XD_STORE_NOP) measured 1.2 % slower (14.50 vs 14.33 ms).
-#if defined(XD_STORE_NOP)
-            asm volatile("s_nop 4\n\tglobal_store_dword %0, %1, %2 " XD_STORE_BITS ::"v"(o), "v"(v), "s"(org.p[K]) : "memory");
-#else
+            // copy measured 1.2 % slower (14.50 vs 14.33 ms).
             if constexpr (PTR_COPY) {
                 uint64_t ptmp;
-                asm volatile("s_mov_b64 %0, %3\n\tglobal_store_dword %1, %2, %0 " XD_STORE_BITS : "=&s"(ptmp) : "v"(o), "v"(v), "s"(org.p[K]) : "memory");
+                asm volatile("s_mov_b64 %0, %3\n\tglobal_store_dword %1, %2, %0 nt sc1" : "=&s"(ptmp) : "v"(o), "v"(v), "s"(org.p[K]) : "memory");
             } else {
-                asm volatile("global_store_dword %0, %1, %2 " XD_STORE_BITS ::"v"(o), "v"(v), "s"(org.p[K]) : "memory");
+                asm volatile("global_store_dword %0, %1, %2 nt sc1" ::"v"(o), "v"(v), "s"(org.p[K]) : "memory");
             }
-#endif
         } else {
             __builtin_nontemporal_store(v, reinterpret_cast<TOUT*>(reinterpret_cast<char*>(org.p[K]) + o));
         }
 #else
         *reinterpret_cast<TOUT*>(reinterpret_cast<char*>(org.p[K]) + o) = v;
-#endif
-    }
-    XD_HD void end_row(int i) {
-#if defined(__HIP_DEVICE_COMPILE__)
-        // keeps the four waves of the workgroup on the same raster row: their four 256-byte segments of a plane's 1 KiB row
-        // piece then reach the memory controller together (every thread of the workgroup marches, see terrain_tile_kernel)
-        if (sync_n && ((uint32_t)(i + 1) & (sync_n - 1)) == 0) __builtin_amdgcn_s_barrier();
-#else
-        (void)i;
 #endif
     }
 };
@@ -570,13 +549,8 @@ XD_HD void surface_pixel_mixed(float zxf, float zyf, float zxxf, float zyyf, flo
     const double g2 = zx2 + zy2;
     const double opg = 1.0 + g2;
     const bool flat = FULLRANGE && (g2 == 0.0);
-#if defined(XD_RAW_RSQ)  // (measurement builds: hardware seeds without the Newton step, ~2^-26)
-    const double rw = rsq_seed(opg);
-    const double rg = flat ? 0.0 : rsq_seed(g2);
-#else
     const double rw = rsqrt_pos(opg);                              // cos(slope)
     const double rg = flat ? 0.0 : rsqrt_pos(g2);                  // 1 / |grad|  (0 on flat ground: kills every x/g term)
-#endif
     const float rgf = (float)rg;
     // the two arcsine arguments: min(sin, cos) of the slope; the smaller normalised gradient component of the aspect's octant
     const float ax = fabsf(zxf), ay = fabsf(zyf);
@@ -1236,13 +1210,8 @@ XD_HD void march_rows(ROWS& rows, int n_out, const TerrainParams& P, SINK& sk) {
                                 if (tail_cold && !cold) HillshadeF64<SP, TIN, SINK>::go(zx, zy, P, sk);
                             }
                         }
-#if defined(XD_NO_COLD)  // (instruction-count analysis builds only: tools/isa_stats.py)
-                        cold = false;
-#endif
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(XD_NO_COLD)
+#if defined(__HIP_DEVICE_COMPILE__)
                         if (__builtin_expect(tail_decided ? (tail_cold_any != 0) : (__builtin_amdgcn_ballot_w64(cold) != 0), 0))
-#elif defined(__HIP_DEVICE_COMPILE__)
-                        if (__builtin_expect(__builtin_amdgcn_ballot_w64(cold) != 0, 0))
 #endif
                         {
                             if (cold) {
@@ -1259,7 +1228,6 @@ XD_HD void march_rows(ROWS& rows, int n_out, const TerrainParams& P, SINK& sk) {
                             }
                         }
                     }
-                    sk.end_row(i);
 #undef XD_SLOT
                 }
             }

@@ -35,58 +35,16 @@ template <typename TIN, typename TOUT> struct TileArgs {
     int64_t H, W, stride, halo_top, halo_bottom;
     int tiles_x, tiles_y, ntiles, grid8;  // grid8 = padded grid / 8
     int vec_ok;
-    int sync_n, order;      // options "terrain_sync" / "terrain_order"
+    int order;              // test switch "terrain_order"
     // frame mode (frame != 0): only the tiles OUTSIDE the tile rectangle [fr_tx0, fr_tx1) x [fr_ty0, fr_ty1) -- the streaming
     // kernel below covers that interior; ntiles then counts the frame tiles
     int frame, fr_tx0, fr_tx1, fr_ty0, fr_ty1;
-    int nplanes;            // requested planes of this launch (staged stores)
-    TOUT* compact[N_ATTR];  // ... their pointers in ascending attribute order
     TerrainParams P;
     Planes<TOUT> out;
 };
 
-// Output rows leave the workgroup as 1 KiB row stores: every thread parks its pixel of each plane in an LDS staging row
-// ([plane][256 columns], double-buffered over the output rows), one barrier later wave w reads back planes w, w+4, ... as
-// float4 (64 lanes x 16 B = the 256 columns of the tile row) and stores them with one global_store_dwordx4 each -- a
-// quarter of the store instructions of the direct form and 1 KiB contiguous per instruction instead of 256 B
-// (tools/membench.hip: 11.65 ms vs 12.35-13.4 ms for the 76.8 GB of the 40000^2 headline case).  One barrier per row
-// suffices: a wave that passes barrier i+1 has finished its reads of buffer i&1 (they feed its stores), so buffer i&1 is
-// free for row i+2.  Needs float32 planes, W % 4 == 0 and 16-byte aligned planes (else the direct sink is launched).
-template <uint32_t CMASK> struct StagedSink {
-    typedef float out_t;
-    static constexpr int NPL = CMASK ? __builtin_popcount(CMASK) : N_ATTR;
-    float* mine;        // LDS: this thread's column in staging buffer 0, plane slot 0
-    float* cur;
-    const float* stage; // LDS: staging base
-    float* const* compact;  // kernarg: plane pointers in slot order
-    const int* slot;        // kernarg: attribute -> slot (runtime masks)
-    int nplanes;
-    int64_t org_off;    // element offset of the tile origin in a plane (wave-uniform)
-    uint32_t row_bytes; // W * 4
-    bool cols_ok;       // this lane's 4 columns (flush role) lie inside the raster
-    int lane, wave;
-    __device__ __forceinline__ void begin_row(int i) { cur = mine + (i & 1) * (nplanes * TILE_W); }
-    template <int K> __device__ __forceinline__ void put(float v) {
-        const int sl = CMASK ? __builtin_popcount(CMASK & ((1u << K) - 1u)) : slot[K];
-        cur[sl * TILE_W] = v;
-    }
-    __device__ __forceinline__ void end_row(int i) {
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        const float* buf = stage + (i & 1) * (nplanes * TILE_W) + 4 * lane;
-        const uint32_t off = (uint32_t)i * row_bytes + 16u * (uint32_t)lane;
-#pragma unroll
-        for (int j0 = 0; j0 < NPL; j0 += 4) {
-            const int j = j0 + wave;
-            if (j < nplanes) {
-                const float4 v = *reinterpret_cast<const float4*>(buf + j * TILE_W);
-                if (cols_ok) *reinterpret_cast<float4*>(reinterpret_cast<char*>(compact[j] + org_off) + off) = v;
-            }
-        }
-    }
-};
-
-template <int FIT, bool CURV, bool WIN, class SP, typename TIN, typename TOUT, int TH, int STORE, int MINW = 1>
-__global__ __launch_bounds__(256, MINW) void terrain_tile_kernel(const TileArgs<TIN, TOUT> a) {
+template <int FIT, bool CURV, bool WIN, class SP, typename TIN, typename TOUT, int TH>
+__global__ __launch_bounds__(256, 1) void terrain_tile_kernel(const TileArgs<TIN, TOUT> a) {
     constexpr int HALO = Halo<FIT>::v;
     constexpr int VEC = 16 / sizeof(TIN);
     constexpr int NV = PITCH / VEC;
@@ -127,20 +85,10 @@ __global__ __launch_bounds__(256, MINW) void terrain_tile_kernel(const TileArgs<
         const bool rowok = (gy >= -a.halo_top) && (gy < a.H + a.halo_bottom);
         const TIN* src = a.dem + (gy + a.halo_top) * a.stride + gx;
         vec_t val;
-#if defined(XD_NOLOAD)  // (measurement builds: what does the tile load phase cost?  synthetic pixels, no global loads)
-        if (true) {
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) val[e] = (TIN)(1000.0f + 0.37f * (float)((gx + e) & 1023) + 0.21f * (float)(gy & 1023) + 0.01f * (float)(((gx + e) * gy) & 255));
-        } else
-#endif
         if (rowok && a.vec_ok && gx >= 0 && gx + VEC <= a.W) {
-#if defined(XD_PLAINLOAD)  // (measurement builds)
-            val = *reinterpret_cast<const vec_t*>(src);
-#else
             // streaming hint: a tile's rows are used once (the rows shared with the tile row below come back from HBM anyway,
             // FETCH_SIZE = 1.125 x the raster); 1.1 % faster (15.08 vs 15.25 ms in one session)
             val = __builtin_nontemporal_load(reinterpret_cast<const vec_t*>(src));
-#endif
         } else {
 #pragma unroll
             for (int e = 0; e < VEC; ++e) {
@@ -157,38 +105,17 @@ __global__ __launch_bounds__(256, MINW) void terrain_tile_kernel(const TileArgs<
     // (the builtin returns a signed int: go through uint32_t, or a low half >= 2^31 sign-extends over the high half)
     const int64_t org_off = (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(org_u >> 32)) << 32) |
                                       (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)org_u));
-    if constexpr (STORE == 1) {
-        typedef StagedSink<SP::CMASK> sink_t;
-        __shared__ __attribute__((aligned(16))) float stage[2 * sink_t::NPL * TILE_W];
-        sink_t sk;
-        sk.stage = stage;
-        sk.mine = stage + tid;
-        sk.compact = reinterpret_cast<float* const*>(a.compact);
-        sk.slot = a.P.slot;
-        sk.nplanes = SP::CMASK ? sink_t::NPL : a.nplanes;
-        sk.org_off = org_off;
-        sk.row_bytes = (uint32_t)(a.W * sizeof(float));
-        sk.lane = tid & 63;
-        sk.wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-        sk.cols_ok = x0 + 4 * (tid & 63) < a.W;
-        // every thread marches (the row barrier needs all four waves); columns beyond the raster only see NaN padding
-        march_column<FIT, CURV, WIN, SP, TIN, sink_t>(tile + XPAD + tid, PITCH, n_out, a.P, sk);
-    } else {
-        {
-            // Every thread marches (the optional row barrier needs all four waves): a thread whose column lies beyond the raster
-            // takes the raster's last column instead and stores the same values to the same addresses as that column's own
-            // thread -- duplicate identical stores, only in the last tile of a tile row, and no predicate anywhere.
-            const int64_t last = a.W - 1 - x0;
-            const int ct = (int)((int64_t)tid < last ? (int64_t)tid : last);
-            DirectSink<TOUT> sk;
+    // Every thread marches: a thread whose column lies beyond the raster
+    // takes the raster's last column instead and stores the same values to the same addresses as that column's own
+    // thread -- duplicate identical stores, only in the last tile of a tile row, and no predicate anywhere.
+    const int64_t last = a.W - 1 - x0;
+    const int ct = (int)((int64_t)tid < last ? (int64_t)tid : last);
+    DirectSink<TOUT> sk;
 #pragma unroll
-            for (int k = 0; k < N_ATTR; ++k) sk.org.p[k] = a.out.p[k] + org_off;
-            sk.o0 = (uint32_t)(ct * sizeof(TOUT));
-            sk.ostride = (uint32_t)(a.W * sizeof(TOUT));
-            sk.sync_n = (uint32_t)a.sync_n;
-            march_column<FIT, CURV, WIN, SP, TIN, DirectSink<TOUT>>(tile + XPAD + ct, PITCH, n_out, a.P, sk);
-        }
-    }
+    for (int k = 0; k < N_ATTR; ++k) sk.org.p[k] = a.out.p[k] + org_off;
+    sk.o0 = (uint32_t)(ct * sizeof(TOUT));
+    sk.ostride = (uint32_t)(a.W * sizeof(TOUT));
+    march_column<FIT, CURV, WIN, SP, TIN, DirectSink<TOUT>>(tile + XPAD + ct, PITCH, n_out, a.P, sk);
 }
 
 // ---- streaming strips (float32 rasters, the specialised attribute sets) ----------------------------------------------------
@@ -217,9 +144,7 @@ struct StripArgs {
 };
 
 constexpr int RING_ROWS = 32, RING_PITCH = 72;
-#ifndef XD_RING_BLOCK   // (measurement builds: -DXD_RING_BLOCK(n)=8 or 16 for every set)
-#define XD_RING_BLOCK(nplanes) ((nplanes) <= 5 ? 8 : 16)
-#endif
+constexpr int ring_block(int nplanes) { return nplanes <= 5 ? 8 : 16; }   // rows per ring block (RowsRing) of a set of nplanes planes
 
 typedef const __attribute__((address_space(3))) float* lds_cfloat_ptr;   // 32-bit LDS address (a generic pointer costs 64-bit adds)
 // The ring holds RING_ROWS tile rows in RING_ROWS / BLK blocks of BLK rows; a block is refilled as soon as no path reads its rows
@@ -348,9 +273,6 @@ __global__ __launch_bounds__(256, MINW) void terrain_strip_kernel(const StripArg
     for (int k = 0; k < N_ATTR; ++k) sk.org.p[k] = a.out.p[k] + org_off;
     sk.o0 = (uint32_t)(lane * sizeof(float));
     sk.ostride = (uint32_t)(a.W * sizeof(float));
-#if defined(XD_STRIP_SYNC)   // (measurement builds: workgroup barrier every XD_STRIP_SYNC output rows -- the four strips of a group then write
-    sk.sync_n = XD_STRIP_SYNC;   // the same plane rows at about the same time; legal: the four waves march the same number of rows)
-#endif
     march_rows<FIT, CURV, WIN, SP, float, DirectSink<float, PTR_COPY>, ring_t>(rows, n_out, a.P, sk);
 }
 
@@ -525,8 +447,8 @@ static void fill_params(const TerrainLaunch& L, TerrainParams& P) {
 
 struct FrameRect { int tx0 = 0, tx1 = 0, ty0 = 0, ty1 = 0; };  // interior tile rectangle left out in frame mode (empty: all tiles)
 
-template <int FIT, bool CURV, bool WIN, class SP, typename TIN, typename TOUT, int TH, int STORE, int MINW = 1>
-static int launch_tiles(xdemhip_ctx* ctx, const TerrainLaunch& L, uint32_t mask, unsigned dyn_lds = 0, FrameRect fr = FrameRect()) {
+template <int FIT, bool CURV, bool WIN, class SP, typename TIN, typename TOUT, int TH>
+static int launch_tiles(xdemhip_ctx* ctx, const TerrainLaunch& L, uint32_t mask, FrameRect fr = FrameRect()) {
     TileArgs<TIN, TOUT> a;
     a.dem = static_cast<const TIN*>(L.dem);
     a.H = L.H; a.W = L.W; a.stride = L.row_stride; a.halo_top = L.halo_top; a.halo_bottom = L.halo_bottom;
@@ -542,63 +464,22 @@ static int launch_tiles(xdemhip_ctx* ctx, const TerrainLaunch& L, uint32_t mask,
     a.grid8 = (a.ntiles + 7) / 8;
     constexpr int VEC = 16 / sizeof(TIN);
     a.vec_ok = ((reinterpret_cast<uintptr_t>(L.dem) & 15) == 0) && (L.row_stride % VEC == 0);
-    a.sync_n = ctx->terrain_sync;
     a.order = ctx->terrain_order;
     fill_params(L, a.P);
     a.P.mask = mask;
-    a.nplanes = 0;
-    for (int k = 0; k < N_ATTR; ++k) {
-        a.out.p[k] = static_cast<TOUT*>(L.planes[k]);
-        a.compact[k] = nullptr;
-        a.P.slot[k] = 0;
-    }
-    for (int k = 0; k < N_ATTR; ++k)
-        if (mask & (1u << k)) {
-            a.P.slot[k] = a.nplanes;
-            a.compact[a.nplanes++] = static_cast<TOUT*>(L.planes[k]);
-        }
-    hipLaunchKernelGGL((terrain_tile_kernel<FIT, CURV, WIN, SP, TIN, TOUT, TH, STORE, MINW>), dim3(a.grid8 * 8), dim3(256), dyn_lds,
+    for (int k = 0; k < N_ATTR; ++k) a.out.p[k] = static_cast<TOUT*>(L.planes[k]);
+    hipLaunchKernelGGL((terrain_tile_kernel<FIT, CURV, WIN, SP, TIN, TOUT, TH>), dim3(a.grid8 * 8), dim3(256), 0,
                        ctx->stream, a);
     XD_HIP_CHECK(ctx, hipGetLastError());
     return XDEMHIP_OK;
 }
 
-// Tile height and store form.  Default: direct stores (one 256-byte row segment per wave, plane and row) from 32-row
-// (float32 DEM) / 16-row (float64 DEM) tiles.  The staged form (StagedSink: rows leave as 1 KiB float4 stores after an
-// LDS transpose with one workgroup barrier per row; float32 planes, W % 4 == 0, 16-byte aligned planes) is kept behind
-// context option "terrain_store" = 1: measured 5-8 % SLOWER than the direct form on MI355X (profiles/README.md, r02 --
-// the per-row barrier costs more than the wider stores return); "terrain_rows" picks the tile height in measurement builds.
-template <typename TOUT> static bool staged_ok(const TerrainLaunch& L, uint32_t mask) {
-    if (sizeof(TOUT) != 4 || (L.W & 3)) return false;
-    for (int k = 0; k < N_ATTR; ++k)
-        if ((mask & (1u << k)) && (reinterpret_cast<uintptr_t>(L.planes[k]) & 15)) return false;
-    return true;
-}
-
-template <int FIT, bool CURV, bool WIN, class SP, typename TIN, typename TOUT, bool ALLSHAPES = false>
+// Tile height: 32-row (float32 DEM) / 16-row (float64 DEM) tiles with direct stores (one 256-byte row segment per wave, plane
+// and row).  Rows staged in LDS and stored as 1 KiB float4 rows (one workgroup barrier per row) measured 5-8 % SLOWER on
+// MI355X (profiles/README.md, r02): the per-row barrier costs more than the wider stores return.
+template <int FIT, bool CURV, bool WIN, class SP, typename TIN, typename TOUT>
 static int launch_shaped(xdemhip_ctx* ctx, const TerrainLaunch& L, uint32_t mask) {
-    constexpr int TH_DIRECT = (sizeof(TIN) == 4) ? 32 : 16;
-#ifdef XD_EXPERIMENT   // (the staged store form measured 5-8 % slower: measurement builds only -- the product does not carry its kernels)
-    if constexpr (sizeof(TOUT) == 4) {
-        if ((ctx->terrain_store == 1) && staged_ok<TOUT>(L, mask)) {
-            if constexpr (ALLSHAPES) {  // measurement builds: option "terrain_rows"
-                if (ctx->terrain_rows == 32) return launch_tiles<FIT, CURV, WIN, SP, TIN, TOUT, 32, 1>(ctx, L, mask);
-                if (ctx->terrain_rows == 24) return launch_tiles<FIT, CURV, WIN, SP, TIN, TOUT, 24, 1>(ctx, L, mask);
-            }
-            return launch_tiles<FIT, CURV, WIN, SP, TIN, TOUT, 16, 1>(ctx, L, mask);
-        }
-    }
-#endif
-    if constexpr (ALLSHAPES && sizeof(TIN) == 4) {
-        if (ctx->terrain_rows == 16) return launch_tiles<FIT, CURV, WIN, SP, TIN, TOUT, 16, 0>(ctx, L, mask);
-        if (ctx->terrain_rows == 24) return launch_tiles<FIT, CURV, WIN, SP, TIN, TOUT, 24, 0>(ctx, L, mask);
-        // occupancy experiments: 132 = register cap of 4 waves / SIMD (128 VGPRs); 232 / 332 = the default kernel held to 2 / 1
-        // workgroups per CU by unused dynamic LDS
-        if (ctx->terrain_rows == 132) return launch_tiles<FIT, CURV, WIN, SP, TIN, TOUT, 32, 0, 4>(ctx, L, mask);
-        if (ctx->terrain_rows == 232) return launch_tiles<FIT, CURV, WIN, SP, TIN, TOUT, 32, 0>(ctx, L, mask, 40 * 1024);
-        if (ctx->terrain_rows == 332) return launch_tiles<FIT, CURV, WIN, SP, TIN, TOUT, 32, 0>(ctx, L, mask, 90 * 1024);
-    }
-    return launch_tiles<FIT, CURV, WIN, SP, TIN, TOUT, TH_DIRECT, 0>(ctx, L, mask);
+    return launch_tiles<FIT, CURV, WIN, SP, TIN, TOUT, (sizeof(TIN) == 4) ? 32 : 16>(ctx, L, mask);
 }
 
 // Streaming route for float32 in / float32 out and the specialised attribute sets: the interior by terrain_strip_kernel, the
@@ -609,7 +490,7 @@ template <int FIT, bool CURV, bool WIN, class SP>
 static int launch_stream(xdemhip_ctx* ctx, const TerrainLaunch& L, uint32_t mask) {
     constexpr int HALO = Halo<FIT>::v;
     constexpr int TH = 32;
-    if (ctx->terrain_stream == 0 || ctx->terrain_store == 1 || ctx->terrain_rows != 0) return 0;
+    if (ctx->terrain_stream == 0) return 0;
     if ((reinterpret_cast<uintptr_t>(L.dem) & 15) || (L.row_stride & 3)) return 0;   // 16-byte quads of the LDS-DMA
     if (L.row_stride >= ((int64_t)1 << 24) - 64) return 0;                               // 24-bit row offsets inside a block
     FrameRect fr;
@@ -628,7 +509,7 @@ static int launch_stream(xdemhip_ctx* ctx, const TerrainLaunch& L, uint32_t mask
     a.order = ctx->terrain_order;
     fill_params(L, a.P);
     a.P.mask = mask;
-    for (int k = 0; k < N_ATTR; ++k) { a.out.p[k] = static_cast<float*>(L.planes[k]); a.P.slot[k] = 0; }
+    for (int k = 0; k < N_ATTR; ++k) a.out.p[k] = static_cast<float*>(L.planes[k]);
     const int bh = ctx->terrain_stream >= 64 ? ctx->terrain_stream : 128;
     const bool dbg_no_strips = ctx->terrain_stream == 3, dbg_no_frame = ctx->terrain_stream == 2;  // (debug: one of the two launches only)
     const int64_t bands = (a.yi1 - a.yi0 + bh - 1) / bh;
@@ -650,14 +531,14 @@ static int launch_stream(xdemhip_ctx* ctx, const TerrainLaunch& L, uint32_t mask
     // the CPU suite checks the compiled kernels); the register allocator is told so -- left alone it takes 129
     constexpr int MINW = (FIT == 2 && CURV && SP::F64TAIL != 2) ? 1 : 4;   // (the mixed tail of option terrain_math = 0 would spill two registers)
     // ring blocks: the sets of up to five planes march a row in a few hundred cycles and need their refills further ahead (RowsRing)
-    constexpr int RBLK = XD_RING_BLOCK(__builtin_popcount(SP::CMASK));
+    constexpr int RBLK = ring_block(__builtin_popcount(SP::CMASK));
     if (dbg_no_strips) {}
     else if (bh == 128) hipLaunchKernelGGL((terrain_strip_kernel<FIT, CURV, WIN, SP, 128, MINW, RBLK>), grid, block, 0, ctx->stream, a);
     else if (bh == 256) hipLaunchKernelGGL((terrain_strip_kernel<FIT, CURV, WIN, SP, 256, MINW, RBLK>), grid, block, 0, ctx->stream, a);
     else if (bh == 512) hipLaunchKernelGGL((terrain_strip_kernel<FIT, CURV, WIN, SP, 512, MINW, RBLK>), grid, block, 0, ctx->stream, a);
     else return xd_fail(ctx, XDEMHIP_EINVAL, "terrain_stream: 0, 1, 128, 256 or 512");
     XD_HIP_CHECK(ctx, hipGetLastError());
-    const int rc = dbg_no_frame ? XDEMHIP_OK : launch_tiles<FIT, CURV, WIN, SP, float, float, TH, 0>(ctx, L, mask, 0, fr);
+    const int rc = dbg_no_frame ? XDEMHIP_OK : launch_tiles<FIT, CURV, WIN, SP, float, float, TH>(ctx, L, mask, fr);
     return rc == XDEMHIP_OK ? 1 : rc;
 }
 
@@ -680,11 +561,6 @@ static int launch_typed(xdemhip_ctx* ctx, const TerrainLaunch& L) {
         // 2 (default) / 0: lean / mixed tail of the specialised float32 kernels (the runtime-mask kernels keep the mixed tail)
         constexpr bool FF = SameT<TIN, float>::v && SameT<TOUT, float>::v;
         const bool f64tail = FF && (ctx->terrain_math == 1 || L.hs_unclipped);
-#ifdef XD_EXPERIMENT
-        constexpr bool ALLSHAPES = FF;
-#else
-        constexpr bool ALLSHAPES = false;
-#endif
         if constexpr (FF) {
             // float32 in / float32 out, specialised sets: lean tail (option "terrain_math" = 2, the default) or the mixed tail of
             // round 2 (0); the streaming route (interior by wave-autonomous strips + frame by tiles) where the raster qualifies
@@ -704,7 +580,7 @@ static int launch_typed(xdemhip_ctx* ctx, const TerrainLaunch& L) {
         else if (fld) took = launch_stream<2, true, true, Spec<MASK_FULL11, 1, 1, 0, 1, LV>>(ctx, L, mask);                  \
         else if (ztd) took = launch_stream<1, true, true, Spec<MASK_FULL11, 1, 1, 0, 1, LV>>(ctx, L, mask);                  \
         if (took != 0) return took < 0 ? took : XDEMHIP_OK;                                                                  \
-        if (fl) return launch_shaped<2, true, true, Spec<MASK_FULL11, 0, 1, 0, 1, LV>, TIN, TOUT, ALLSHAPES>(ctx, L, mask);  \
+        if (fl) return launch_shaped<2, true, true, Spec<MASK_FULL11, 0, 1, 0, 1, LV>, TIN, TOUT>(ctx, L, mask);             \
         if (zt) return launch_shaped<1, true, true, Spec<MASK_FULL11, 0, 1, 0, 1, LV>, TIN, TOUT>(ctx, L, mask);             \
         if (hn) return launch_shaped<0, false, true, Spec<MASK_SAH_WIN, 0, 1, 0, 1, LV>, TIN, TOUT>(ctx, L, mask);           \
         if (fld) return launch_shaped<2, true, true, Spec<MASK_FULL11, 1, 1, 0, 1, LV>, TIN, TOUT>(ctx, L, mask);            \
@@ -740,7 +616,7 @@ static int launch_typed(xdemhip_ctx* ctx, const TerrainLaunch& L) {
             }
         } else if (!f64tail) {
             if (defaults && mask == MASK_FULL11 && fit == XDEMHIP_FIT_FLORINSKY)
-                return launch_shaped<2, true, true, Spec<MASK_FULL11, 0, 1, 0, 1>, TIN, TOUT, ALLSHAPES>(ctx, L, mask);
+                return launch_shaped<2, true, true, Spec<MASK_FULL11, 0, 1, 0, 1>, TIN, TOUT>(ctx, L, mask);
             if (defaults && mask == MASK_FULL11 && fit == XDEMHIP_FIT_ZEVENBERGTHORNE)
                 return launch_shaped<1, true, true, Spec<MASK_FULL11, 0, 1, 0, 1>, TIN, TOUT>(ctx, L, mask);
             if (defaults && mask == MASK_SAH_WIN && fit == XDEMHIP_FIT_HORN)
@@ -748,7 +624,7 @@ static int launch_typed(xdemhip_ctx* ctx, const TerrainLaunch& L) {
         }
         if constexpr (FF) {
             if (f64tail && defaults && mask == MASK_FULL11 && fit == XDEMHIP_FIT_FLORINSKY)
-                return launch_shaped<2, true, true, Spec<MASK_FULL11, 0, 1, 0, 1, 1>, TIN, TOUT, ALLSHAPES>(ctx, L, mask);
+                return launch_shaped<2, true, true, Spec<MASK_FULL11, 0, 1, 0, 1, 1>, TIN, TOUT>(ctx, L, mask);
         }
 #define XD_GO(F, C, Wn)                                                                             \
     do {                                                                                            \

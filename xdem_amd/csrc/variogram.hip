@@ -41,10 +41,7 @@ namespace xd {
 // spread pair sample (every-a-with-every-b blocks): B slots per lane and tile -> SPREAD_SLOTS / 256 of the pairs of every unit.
 // (4 = 1/64 was the first setting; the brackets scale with 1 / sqrt(sample), the three sampled passes with the sample: 2 slots
 // cost 0.1 % more candidates and save a third of the sampled passes' time on SURVEY 8d's C5)
-#ifndef XD_SPREAD_SLOTS
-#define XD_SPREAD_SLOTS 2
-#endif
-constexpr int SPREAD_SLOTS = XD_SPREAD_SLOTS;
+constexpr int SPREAD_SLOTS = 2;
 constexpr int PT = 256;      // B points per LDS tile; A points per workgroup = NT (256 for sums / succ, 1024 for histograms)
 // (a lane's SPREAD_SLOTS slots lie PT / SPREAD_SLOTS apart, so one wave covers SPREAD_SLOTS of the tile's four 64-slot groups:
 // consecutive waves start in different groups and the waves of a workgroup together cover every B point of the tile -- with one
@@ -235,11 +232,7 @@ __global__ __launch_bounds__(NT, (NT == 1024 && sizeof(T) == 4) ? 8 : 1) void pa
     // run-length counting pass, float32 values (round 5): everything a lane loads when its run enters class l -- the class's d^2
     // interval {low, width} and its bracket {low, high} as float bits -- in ONE 16-byte record (the interval used to be rebuilt from the
     // cell's table entry with two selects and a subtract next to the 8-byte read of the bracket)
-#if defined(XD_NO_CLSREC)   // (measurement build: the round-4 form)
-    constexpr bool CLSREC = false;
-#else
     constexpr bool CLSREC = GRID && OP == OP_BRACKET && sizeof(T) == 4;
-#endif
     __shared__ uint4 s_clsrec[CLSREC ? HIST_BINS_PER_SWEEP_K + 2 : 1];
     const int tid = threadIdx.x;
     if (FAST)  // (NT may be smaller than the table: round 1 loaded only its first NT entries -- wrong classes beyond 32 binades of d^2)
@@ -1631,10 +1624,10 @@ int pairs_medians_typed(xdemhip_pairs* P, int64_t* counts, double* medians, bool
     std::vector<K> klo(nb), khi(nb);
     std::vector<uint64_t> lo_count(nb, 0);
     // Design effect assumed for the sample (select.h): every-a-with-every-b blocks are sampled with per-lane B slots (few pairs
-    // per point), i < j blocks with 4 B slots against all A points; option "vario_deff" overrides (tests, measurements).  A
+    // per point), i < j blocks with 4 B slots against all A points.  A
     // bracket that misses its rank (the integer counts tell) costs one more attempt with the wide brackets before the plain
     // digit passes take over; with a reduction hook the counts are global, so every rank retries alike.
-    uint32_t deff = ctx->vario_deff > 0 ? (uint32_t)ctx->vario_deff : (P->pdist ? PAIR_DEFF_WIDE : PAIR_DEFF_SPREAD);
+    uint32_t deff = P->pdist ? PAIR_DEFF_WIDE : PAIR_DEFF_SPREAD;
     for (int attempt = 0; attempt < 3 && bracket && !done; ++attempt) {
         if (attempt >= 1) {   // a bracket missed its rank: 16 x the assumed design effect (4 x the width), then the wide rule
             if (deff >= PAIR_DEFF_WIDE) break;
