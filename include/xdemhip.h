@@ -387,6 +387,47 @@ int xdemhip_dh_shift_nmad(xdemhip_dh_plan* plan, double shift_x, double shift_y,
 int xdemhip_dh_shift_values(xdemhip_dh_plan* plan, double shift_x, double shift_y, double res_x, double res_y, void* dh_out, int memspace,
                             int64_t* count);
 void xdemhip_dh_destroy(xdemhip_dh_plan* plan);
+
+/* ---- rigid coregistration: LZD and the rotation-capable raster apply (csrc/rigid.hip) ------------------------------------------
+ * The grid passes of xdem.coreg.LZD (Rosenholm & Torlegard 1988; xdem/coreg/affine.py:1417-1776) on a dh plan, and
+ * _iterate_affine_regrid_small_rotations (xdem/coreg/base.py:1389-1519) for resampling="linear".
+ * `transform6` = the north-up geotransform (a, b, c, d, e, f) with b = d = 0: pixel (row, col) has its centre at
+ * x = c + (col + 0.5) a, y = f + (row + 0.5) e.  `matrix16` = a 4 x 4 rigid matrix, row-major, last row (0, 0, 0, 1);
+ * p' = M (p - centroid) + centroid, the products as explicit float64 sums m0 x + m1 y + m2 z + m3 without contraction.
+ *  xdemhip_dh_lzd_gradients  gradx = gradient_x / res_x, grady = -gradient_y / res_y of np.gradient(ref) (affine.py:1440, 1455-1456) in the
+ *                            raster dtype, the resolution taken to that dtype first; made at the first LZD call and kept by the plan.
+ *                            Copies the two planes out (H * W values each).  The raster must be at least 2 x 2.
+ *  xdemhip_dh_lzd_centroid   (mean x, mean y, mean tba) over the selected pixels (affine.py:1744-1746): integer sums of row and column,
+ *                            the float64 sum of tba in a fixed order; *count = the selected pixels.
+ *  xdemhip_dh_lzd_normal     one LZD iteration's normal equations.  Every selected pixel p = (x, y, tba) is moved by the matrix, ref, gradx
+ *                            and grady are interpolated at its new position (row', col') = ((y' - f) / e - 0.5, (x' - c) / a - 0.5) with the
+ *                            bilinear taps and the nodata rule of the Nuth-Kaab step (option "nk_nan_rule"), each rounded to the raster dtype;
+ *                            dh = ref' - z'.  Pixels with a non-finite dh, z', gx or gy are dropped (affine.py:1640).  With (x, y, z) the moved
+ *                            point minus the centroid, a = (-gx, -gy, 1, y + gy z, -x - gx z, gx y - gy x) (the derivatives of
+ *                            affine.py:1496-1503 by t1, t2, t3, alpha1, alpha2, alpha3).  sums_out[29] = the 21 upper-triangle terms of
+ *                            a a^T (row by row), the 6 of a dh, sum dh^2, sum dh, in float64: per-lane accumulators, one partial per
+ *                            workgroup (in a buffer the plan keeps), partials added in a fixed order (two calls return the same bits), one
+ *                            fetch.  *count = pixels kept.
+ *  xdemhip_dh_lzd_values     what upstream hands _lzd_fit: x, y, z (centroid removed), dh, gradx, grady of the pixels kept, float64, raster
+ *                            order.  `out` holds 6 rows of n values, n = the selected pixels (row k starts at out[k * n]); the first *count
+ *                            entries of each row are filled.  `out` is host memory.
+ *  xdemhip_apply_matrix_rst  the DEM seen after the rigid transform, resampled on its own grid: one thread per pixel runs upstream's
+ *                            fixed-point iteration (first guess z of the pixel's own transformed point; inverse transform of (x, y, z_guess),
+ *                            interpolation of dem there, forward transform to (x0, y0, z0); after iteration 1 the pixel keeps z0 if
+ *                            |x0 - x| < 1e-4 res_x or is non-finite, and the same in y; otherwise it keeps z0 of iteration 5).  The
+ *                            interpolation is SciPy's RegularGridInterpolator(method="linear", bounds_error=False): NaN outside the pixel
+ *                            centres' extent and where any node of the cell is non-finite (a position exactly on row k lies in SciPy's cell of
+ *                            rows [k - 1, k], one exactly on column k in the cell of columns [k, k + 1]).  The inverse is formed here as
+ *                            R^T and -(R^T t); `centroid3_or_null`: no centroid is subtracted when null.  All float64,
+ *                            result cast to `dtype`.  The raster must be at least 2 x 2. */
+int xdemhip_dh_lzd_gradients(xdemhip_dh_plan* plan, const double* transform6, void* gradx_out, void* grady_out, int memspace);
+int xdemhip_dh_lzd_centroid(xdemhip_dh_plan* plan, const double* transform6, double* centroid_out, int64_t* count);
+int xdemhip_dh_lzd_normal(xdemhip_dh_plan* plan, const double* transform6, const double* matrix16, const double* centroid3, double* sums_out,
+                          int64_t* count);
+int xdemhip_dh_lzd_values(xdemhip_dh_plan* plan, const double* transform6, const double* matrix16, const double* centroid3, double* out,
+                          int64_t* count);
+int xdemhip_apply_matrix_rst(xdemhip_ctx* ctx, const void* dem, int dtype, int64_t H, int64_t W, const double* transform6, const double* matrix16,
+                             const double* centroid3_or_null, void* out, int memspace);
 /* out = cast(double(elev) + P(x, y)), P = np.polynomial.polynomial.polyval2d(x, y, c) with c[i, j] = coeffs[i * (order + 1) + j]
  * (the reference's fit_params reshaped), x = column, y = row_offset + row, evaluated in NumPy's order bit for bit: Horner in x for
  * every j (polyval, tensor form), then Horner in y (polyval, tensor=False), no fused multiply-add.  out has the dtype of elev: float32

@@ -186,6 +186,12 @@ def lib() -> ctypes.CDLL:
                                               ctypes.c_void_p, ctypes.c_int, c_i64p]
         L.xdemhip_dh_destroy.argtypes = [ctypes.c_void_p]
         L.xdemhip_dh_destroy.restype = None
+        L.xdemhip_dh_lzd_gradients.argtypes = [ctypes.c_void_p, c_dp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+        L.xdemhip_dh_lzd_centroid.argtypes = [ctypes.c_void_p, c_dp, c_dp, c_i64p]
+        L.xdemhip_dh_lzd_normal.argtypes = [ctypes.c_void_p, c_dp, c_dp, c_dp, c_dp, c_i64p]
+        L.xdemhip_dh_lzd_values.argtypes = [ctypes.c_void_p, c_dp, c_dp, c_dp, c_dp, c_i64p]
+        L.xdemhip_apply_matrix_rst.argtypes = [c_ctx, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, c_dp, c_dp, c_dp,
+                                               ctypes.c_void_p, ctypes.c_int]
         L.xdemhip_poly2d_apply.argtypes = [c_ctx, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, c_dp,
                                            ctypes.c_int, ctypes.c_void_p, ctypes.c_int]
         _lib = L

@@ -25,29 +25,7 @@
 #include "select_run.h"
 #include "rank_select.h"
 #include "nk_geom.h"
-
-struct xdemhip_dh_plan {
-    xdemhip_ctx* ctx = nullptr;
-    int dtype = XDEMHIP_F32;
-    int64_t H = 0, W = 0;
-    bool own_inputs = false;
-    void* ref = nullptr;
-    void* tba = nullptr;
-    uint8_t* inlier = nullptr;
-    uint8_t* valid = nullptr;                 // n bytes: inlier & finite(ref) & finite(tba)
-    unsigned long long* tile_off = nullptr;   // exclusive offsets of the valid pixels per tile (n_tiles + 1 words)
-    int64_t n_tiles = 0;
-    int64_t n_valid = 0;
-    int64_t* idx = nullptr;                   // selected pixels (flat indexes, raster order): the drawn ones, or all valid ones on demand
-    int64_t n_idx = 0;
-    bool drawn = false;                       // xdemhip_dh_subsample was called: the drawn pixels are the selection
-    // shifted-dh evaluations (xdemhip_dh_shift_nmad / _values): made at the first evaluation, kept until the plan goes
-    void* stage = nullptr;                    // dh of one evaluation: H * W values (dense route) or n_idx (list route)
-    int64_t stage_n = 0;
-    unsigned char* sel_scratch = nullptr;     // selection states, successor keys, histograms (scratch_size(1)), then the DhEvalOut block
-    xd::SelWorkspace sel_ws;                  // sample / candidate buffers of the bracketed selection (stage_n >= SEL_BRACKET_MIN_N)
-    int64_t sel_ws_n = 0;
-};
+#include "dh_plan.h"
 
 namespace xd {
 namespace {
@@ -825,6 +803,10 @@ inline void norm_axis(int64_t n_global, double* a, double* b) {
 }
 
 }  // namespace
+
+// what rigid.hip needs of the plan's lazily built parts (dh_plan.h)
+int dh_ensure_mask(xdemhip_dh_plan* P) { return ensure_mask(P); }
+int dh_ensure_valid_idx(xdemhip_dh_plan* P) { return ensure_valid_idx(P); }
 }  // namespace xd
 
 using namespace xd;
@@ -844,6 +826,9 @@ void xdemhip_dh_destroy(xdemhip_dh_plan* P) {
     if (P->idx) (void)hipFree(P->idx);
     if (P->stage) (void)hipFree(P->stage);
     if (P->sel_scratch) (void)hipFree(P->sel_scratch);
+    if (P->gradx) (void)hipFree(P->gradx);
+    if (P->grady) (void)hipFree(P->grady);
+    if (P->lzd_part) (void)hipFree(P->lzd_part);
     sel_ws_free(P->sel_ws);
     delete P;
 }

@@ -127,8 +127,8 @@ class DEM:
                       **kwargs) -> "DEM":
         """Align this DEM to ``reference_elev`` (same grid) with ``coreg_method`` (upstream requires one and names Nuth and
         Kaab as the default in its docstring: ``None`` means ``NuthKaab(subsample=1)`` here).  ``random_state`` seeds the
-        subsampling; ``resample`` (keyword, default True) as upstream.  ``coreg_method``: ``NuthKaab``, ``Deramp``,
-        ``VerticalShift`` or a ``CoregPipeline`` of them; ``bias_vars`` belongs to bias corrections with explicit variables, which are
+        subsampling; ``resample`` (keyword, default True) as upstream.  ``coreg_method``: ``NuthKaab``, ``DhMinimize``, ``LZD``,
+        ``Deramp``, ``VerticalShift`` or a ``CoregPipeline`` of them; ``bias_vars`` belongs to bias corrections with explicit variables, which are
         not part of this package."""
         resample = kwargs.pop("resample", True)
         if bias_vars is not None:
@@ -141,6 +141,10 @@ class DEM:
         if reference_elev.shape != self.shape or reference_elev.transform != self.transform:
             raise NotImplementedError("reference and to-be-aligned DEM must share one grid (reprojection is geoutils' job).")
         mask = None if inlier_mask is None else np.asarray(getattr(inlier_mask, "data", inlier_mask), dtype=bool)
+        # (a step that rotates works about a centroid in the grid's coordinates: it gets the transform; the others read the resolution)
+        steps = getattr(method, "pipeline", [method])
+        if any(getattr(step, "_needs_transform", False) for step in steps):
+            kwargs["transform"] = self.transform
         method.fit(reference_elev.data, self.data, mask, resolution=self.res, **kwargs)
         # array interface with transform=: for resample=False the horizontal shift moves the geotransform and only the
         # vertical shift touches the data (xdem/coreg/base.py:1567-1570, _apply_matrix_rst case 2)
