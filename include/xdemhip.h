@@ -428,6 +428,65 @@ int xdemhip_dh_lzd_values(xdemhip_dh_plan* plan, const double* transform6, const
                           int64_t* count);
 int xdemhip_apply_matrix_rst(xdemhip_ctx* ctx, const void* dem, int dtype, int64_t H, int64_t W, const double* transform6, const double* matrix16,
                              const double* centroid3_or_null, void* out, int memspace);
+
+/* ---- ICP coregistration (csrc/icp.hip) -----------------------------------------------------------------------------------------
+ * The device passes of xdem.coreg.ICP (Besl & McKay 1992, Chen & Medioni 1992; xdem/coreg/affine.py:296-328, 773-1182) for two rasters
+ * on one grid, and an exact 3-D nearest-neighbour search for any two clouds.  Everything is float64 without contraction.
+ *  xdemhip_dh_icp_normals    _icp_norms (affine.py:1062-1081) on a dh plan: np.gradient(ref) in the raster dtype,
+ *                            nx = -sin(arctan(d/dcol / res_y)), ny = sin(arctan(d/drow / res_x)) -- upstream's pairing of derivative and
+ *                            resolution -- with the quotient taken in the dtype, g / sqrt(1 + g^2) (= sin(arctan g)) in float64 and rounded
+ *                            once to the dtype, nz = 1 - sqrt(nx^2 + ny^2) in the dtype.  The planes are kept by the plan; the call NARROWS
+ *                            the plan's valid mask to the pixels where all three are finite (*n_valid = the new count), so it must come
+ *                            before xdemhip_dh_subsample or any call that lists the valid pixels: XDEMHIP_EINVAL afterwards.  Outputs
+ *                            (H * W values each, any may be NULL) are copied out; a second call only copies.  At least 2 x 2 pixels.
+ *  xdemhip_icp_create_plan   the clouds of the plan's selected pixels, device-resident, structure of arrays: x, y (pixel centres), ref, tba
+ *                            and -- with_normals -- nx, ny, nz, in raster order.  centroid3 = the per-axis np.median of (x, y, ref), exact
+ *                            (radix selection; an even count averages the two middle values), subtracted from both clouds; std_fac = the
+ *                            mean of the three 1.4826 * median|v - median v| of the centred reference cloud (standardize = 0: 1), both
+ *                            clouds divided by it.  Then the search grid of the reference cloud is built.  *count = the points.
+ *  xdemhip_icp_create_points the same object for arbitrary clouds: ref3n (3 x n, rows x, y, z), query3m (3 x m), optional normals at the
+ *                            reference points; host memory; nothing is centred or scaled.
+ *  xdemhip_icp_cloud         the rows x, y, ref, tba, nx, ny, nz (7 x n, host) of a cloud made from a plan, as standardised.
+ *  xdemhip_icp_grid          the search grid: (x0, y0, h) -- cell (i, j) covers [x0 + i h, x0 + (i + 1) h) x [y0 + j h, y0 + (j + 1) h), the
+ *                            last column and row also what lies beyond -- and its (columns, rows).
+ *  xdemhip_icp_query         nearest reference point of every query point under the 4 x 4 matrix (rows 0..2 used; NULL = identity;
+ *                            p' = (m0 x + m1 y) + m2 z + m3): a uniform grid of square cells over the reference (x, y), sized from the
+ *                            bounding box and n for about three points per cell (an axis of zero extent gets one row of cells), built by
+ *                            a counting sort; one thread per query walks Chebyshev rings of cells around its own cell (clamped to the
+ *                            grid) and keeps the smallest dx dx + dy dy + dz dz, ties to the LOWEST reference index; it stops after a
+ *                            ring once the best is strictly below the squared distance from the query's real position to the nearest
+ *                            unvisited cell (less a rounding allowance).  ind (int64) and dist (the square root) stay on the device for
+ *                            the next calls and are copied to the host outputs that are not NULL.  Two runs return the same bits.
+ *  xdemhip_icp_set_pairs     put ind / dist (m each, host) in the place of a query's result (the moved cloud = the query cloud).
+ *  xdemhip_icp_pairs         the pairs of the fit.  picky (Zinsser et al. 2003; affine.py:1017-1021): per reference index the pair of
+ *                            smallest distance -- atomicMin over the distance bits, then over the query indexes at that distance (pandas
+ *                            idxmin: first occurrence), then the keep flags compacted -- in reference-index order; else every pair in
+ *                            query order.  *n_kept, and optionally the kept (query index, reference index) lists on the host.
+ *  xdemhip_icp_sums          for every kept pair p' = S t (S = step16, t = the query point as moved by the last query), q its reference
+ *                            point: method 1 point-to-plane r = (p' - q) . n, J = [p' x n, n]; method 0 point-to-point r = |p' - q|,
+ *                            u = (p' - q) / r, J = [p' x u, u], a zero row where r = 0.  sums_out[37] = the 21 upper-triangle terms of
+ *                            J J^T (row by row; parameters: rotation vector, then translation), the 6 of J r, sum r^2, and nine moments
+ *                            of p': sums of x^2, y^2, z^2, xy, xz, yz, x, y, z -- with the count they give the normal matrix of the VECTOR
+ *                            residual p' - q, sum D^T D with D = [-[p']x, I], which the point-to-point Gauss-Newton uses (same gradient
+ *                            J^T r; the scalar rows drop r grad^2 r = I - u u^T and do not converge).  Per-lane accumulators, one
+ *                            partial per workgroup, partials added in a fixed order (the same bits every call), one fetch.
+ *  xdemhip_icp_values        what upstream hands _icp_fit: rows ref x, y, z, moved query x, y, z, normals x, y, z of the kept pairs
+ *                            (9 x n_kept, host; the normals' rows are zero without normals). */
+typedef struct xdemhip_icp xdemhip_icp;
+int xdemhip_dh_icp_normals(xdemhip_dh_plan* plan, const double* transform6, void* nx_out, void* ny_out, void* nz_out, int memspace, int64_t* n_valid);
+int xdemhip_icp_create_plan(xdemhip_dh_plan* plan, const double* transform6, int with_normals, int standardize, xdemhip_icp** out, double* centroid3,
+                            double* std_fac, int64_t* count);
+int xdemhip_icp_create_points(xdemhip_ctx* ctx, const double* ref3n, int64_t n, const double* query3m, int64_t m, const double* norms3n_or_null,
+                              xdemhip_icp** out);
+int xdemhip_icp_cloud(xdemhip_icp* icp, double* out7n);
+int xdemhip_icp_grid(xdemhip_icp* icp, double* x0_y0_h, int64_t* gx_gy);
+int xdemhip_icp_query(xdemhip_icp* icp, const double* matrix16_or_null, int64_t* ind_out, double* dist_out);
+int xdemhip_icp_set_pairs(xdemhip_icp* icp, const int64_t* ind, const double* dist);
+int xdemhip_icp_pairs(xdemhip_icp* icp, int picky, int64_t* n_kept, int64_t* query_idx_out, int64_t* ref_idx_out);
+int xdemhip_icp_sums(xdemhip_icp* icp, const double* step16, int method, double* sums_out, int64_t* count);
+int xdemhip_icp_values(xdemhip_icp* icp, double* out9k);
+void xdemhip_icp_destroy(xdemhip_icp* icp);
+
 /* out = cast(double(elev) + P(x, y)), P = np.polynomial.polynomial.polyval2d(x, y, c) with c[i, j] = coeffs[i * (order + 1) + j]
  * (the reference's fit_params reshaped), x = column, y = row_offset + row, evaluated in NumPy's order bit for bit: Horner in x for
  * every j (polyval, tensor form), then Horner in y (polyval, tensor=False), no fused multiply-add.  out has the dtype of elev: float32

@@ -190,6 +190,18 @@ def lib() -> ctypes.CDLL:
         L.xdemhip_dh_lzd_centroid.argtypes = [ctypes.c_void_p, c_dp, c_dp, c_i64p]
         L.xdemhip_dh_lzd_normal.argtypes = [ctypes.c_void_p, c_dp, c_dp, c_dp, c_dp, c_i64p]
         L.xdemhip_dh_lzd_values.argtypes = [ctypes.c_void_p, c_dp, c_dp, c_dp, c_dp, c_i64p]
+        L.xdemhip_dh_icp_normals.argtypes = [ctypes.c_void_p, c_dp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, c_i64p]
+        L.xdemhip_icp_create_plan.argtypes = [ctypes.c_void_p, c_dp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), c_dp, c_dp, c_i64p]
+        L.xdemhip_icp_create_points.argtypes = [c_ctx, c_dp, ctypes.c_int64, c_dp, ctypes.c_int64, c_dp, ctypes.POINTER(ctypes.c_void_p)]
+        L.xdemhip_icp_cloud.argtypes = [ctypes.c_void_p, c_dp]
+        L.xdemhip_icp_grid.argtypes = [ctypes.c_void_p, c_dp, c_i64p]
+        L.xdemhip_icp_query.argtypes = [ctypes.c_void_p, c_dp, c_i64p, c_dp]
+        L.xdemhip_icp_set_pairs.argtypes = [ctypes.c_void_p, c_i64p, c_dp]
+        L.xdemhip_icp_pairs.argtypes = [ctypes.c_void_p, ctypes.c_int, c_i64p, c_i64p, c_i64p]
+        L.xdemhip_icp_sums.argtypes = [ctypes.c_void_p, c_dp, ctypes.c_int, c_dp, c_i64p]
+        L.xdemhip_icp_values.argtypes = [ctypes.c_void_p, c_dp]
+        L.xdemhip_icp_destroy.argtypes = [ctypes.c_void_p]
+        L.xdemhip_icp_destroy.restype = None
         L.xdemhip_apply_matrix_rst.argtypes = [c_ctx, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, c_dp, c_dp, c_dp,
                                                ctypes.c_void_p, ctypes.c_int]
         L.xdemhip_poly2d_apply.argtypes = [c_ctx, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, c_dp,

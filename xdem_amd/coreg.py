@@ -30,6 +30,7 @@ from ._coregbase import subsample_ranks, subsample_valid_mask  # noqa: F401
 from .biascorr import Deramp, DhPlan, VerticalShift, _check_weights, polynomial_2d  # noqa: F401  (upstream's xdem.coreg offers them here)
 from .rigid import (LZD, apply_matrix, invert_matrix, matrix_from_translations_rotations,  # noqa: F401  (and these)
                     translations_rotations_from_matrix, _make_matrix_valid)
+from .icp import ICP, nearest  # noqa: F401
 from .spatialstats import nmad
 
 

@@ -829,6 +829,8 @@ void xdemhip_dh_destroy(xdemhip_dh_plan* P) {
     if (P->gradx) (void)hipFree(P->gradx);
     if (P->grady) (void)hipFree(P->grady);
     if (P->lzd_part) (void)hipFree(P->lzd_part);
+    for (int a = 0; a < 3; ++a)
+        if (P->icp_n[a]) (void)hipFree(P->icp_n[a]);
     sel_ws_free(P->sel_ws);
     delete P;
 }

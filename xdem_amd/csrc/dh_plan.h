@@ -1,5 +1,5 @@
 // dh_plan.h -- the dh plan (elevation difference of two rasters on one grid) as the translation units that work on it see it:
-// biascorr.hip creates and destroys it, rigid.hip adds the LZD passes.
+// biascorr.hip creates and destroys it, rigid.hip adds the LZD passes, icp.hip the normal planes of ICP.
 #pragma once
 #include "common.h"
 #include "select.h"
@@ -32,6 +32,9 @@ struct xdemhip_dh_plan {
     double grad_res_x = 0.0, grad_res_y = 0.0;  // the resolutions the planes were formed with
     double* lzd_part = nullptr;               // per-workgroup partials and totals of the normal-equation pass
     int64_t lzd_part_n = 0;
+    // ICP (icp.hip): the normal planes nx, ny, nz of ref in the raster dtype; making them narrows `valid` by their finiteness
+    void* icp_n[3] = {nullptr, nullptr, nullptr};
+    double icp_res_x = 0.0, icp_res_y = 0.0;
 };
 
 namespace xd {
