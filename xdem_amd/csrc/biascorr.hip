@@ -14,7 +14,7 @@
 // cy = sy = (H_global - 1) / 2 (a half-width of 0 is taken as 1): x = column, y = row_offset + row, as np.meshgrid(arange(W),
 // arange(H)) numbers them.  In raw pixel coordinates the normal equations of order 2 on a 2000 x 3000 grid are useless; in
 // normalised ones their condition number is ~2e2 (order 2) to ~1e5 (order 4).  Everything is accumulated in float64 and
-// combined in a fixed order: two calls return the same bits.
+// combined in a fixed order (fixed_sums.h; its reduce kernel and host side live here and serve rigid.hip and icp.hip too): same bits every call.
 #include <math.h>
 #include <string.h>
 
@@ -95,7 +95,7 @@ __global__ __launch_bounds__(256) void dh_valid_kernel(const T* __restrict__ ref
 // ---- moments, dense route ----------------------------------------------------------------------------------------------------
 // One row at a time per workgroup (rows blockIdx.x, + gridDim.x, ...).  v is constant along a row: a lane keeps only S_a = sum u^a
 // (a <= 2K) and D_i = sum dh u^i (i <= K) over its columns; the row's sums are reduced over the workgroup (wave shuffles, then the
-// four waves in order) and lane t < NT multiplies its row sum by the power of v of the term it owns.
+// four waves in order: wave_sum and block_sum's order, fixed_sums.h) and lane t < NT multiplies its row sum by the power of v of the term it owns.
 template <int K> struct PolyTerms {
     static constexpr int NA = 2 * K + 1, NR = K + 1, NS = NA + NR, NT = NA * NA + NR * NR;
 };
@@ -163,11 +163,7 @@ __global__ __launch_bounds__(256) void dh_moments_rows_kernel(const T* __restric
             for (int64_t c = threadIdx.x; c < W; c += 256) moments_pixel<T, K>(rr[c], tr[c], ir == nullptr || ir[c] != 0, (double)c * ax + bx, s);
         }
 #pragma unroll
-        for (int e = 0; e < NS; ++e) {
-            double x = s[e];
-            for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
-            s[e] = x;
-        }
+        for (int e = 0; e < NS; ++e) s[e] = wave_sum<double>(s[e]);
         if (lane == 0) {
 #pragma unroll
             for (int e = 0; e < NS; ++e) red[wave][e] = s[e];
@@ -226,22 +222,6 @@ __global__ __launch_bounds__(256) void dh_moments_list_kernel(const T* __restric
     }
     (void)NR;
     if ((int)threadIdx.x < NT) part[(int64_t)blockIdx.x * NT + threadIdx.x] = acc;
-}
-
-// per-workgroup partials -> totals: one workgroup per term, lane l adds the partials of workgroups l, l + 256, ... in order, then a
-// fixed tree over the lanes (the same bits every call)
-__global__ __launch_bounds__(256) void dh_moments_reduce_kernel(const double* __restrict__ part, int nblocks, int nt, double* __restrict__ out) {
-    __shared__ double s[256];
-    const int t = blockIdx.x;
-    double a = 0.0;
-    for (int b = threadIdx.x; b < nblocks; b += 256) a += part[(int64_t)b * nt + t];
-    s[threadIdx.x] = a;
-    __syncthreads();
-    for (int half = 128; half > 0; half >>= 1) {
-        if ((int)threadIdx.x < half) s[threadIdx.x] += s[threadIdx.x + half];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[t] = s[0];
 }
 
 // ---- dh for the median / values routes ---------------------------------------------------------------------------------------
@@ -528,8 +508,7 @@ int launch_apply(xdemhip_ctx* ctx, const T* elev, int64_t H, int64_t W, int64_t 
         default: return xd_fail(ctx, XDEMHIP_EINVAL, "xdemhip_poly2d_apply: order must be 0..5");
     }
 #undef XD_APPLY_CASE
-    if (hipGetLastError() != hipSuccess) return xd_fail(ctx, XDEMHIP_EHIP, "poly2d_apply_kernel launch failed");
-    return XDEMHIP_OK;
+    return launched(ctx, "poly2d_apply_kernel");
 }
 
 template <typename T, int K>
@@ -547,9 +526,8 @@ int launch_moments_t(xdemhip_dh_plan* P, int64_t row_offset, double ax, double b
         hipLaunchKernelGGL((dh_moments_list_kernel<T, K>), dim3((unsigned)nb), dim3(256), 0, ctx->stream, static_cast<const T*>(P->ref),
                            static_cast<const T*>(P->tba), P->idx, k, per, P->W, row_offset, ax, bx, ay, by, d_part);
     } else {
-        int64_t nb = (int64_t)ctx->num_cu * 8;
-        if (nb > P->H) nb = P->H;
-        *nblocks = (int)nb;
+        const int nb = fixed_sums_grid(ctx, P->H);
+        *nblocks = nb;
         const bool vec = (P->W % 4 == 0) && ((uintptr_t)P->ref % 16 == 0) && ((uintptr_t)P->tba % 16 == 0) &&
                          (P->inlier == nullptr || (uintptr_t)P->inlier % 4 == 0);
         if (vec)
@@ -559,7 +537,7 @@ int launch_moments_t(xdemhip_dh_plan* P, int64_t row_offset, double ax, double b
             hipLaunchKernelGGL((dh_moments_rows_kernel<T, K, false>), dim3((unsigned)nb), dim3(256), 0, ctx->stream, static_cast<const T*>(P->ref),
                                static_cast<const T*>(P->tba), P->inlier, P->H, P->W, row_offset, ax, bx, ay, by, d_part);
     }
-    return hipGetLastError() == hipSuccess ? XDEMHIP_OK : xd_fail(ctx, XDEMHIP_EHIP, "moments kernel launch failed");
+    return launched(ctx, "moments kernel");
 }
 
 template <typename T>
@@ -594,7 +572,7 @@ void launch_valid_t(xdemhip_dh_plan* P, bool write_mask) {
 int launch_valid(xdemhip_dh_plan* P, bool write_mask) {
     if (P->dtype == XDEMHIP_F32) launch_valid_t<float>(P, write_mask);
     else launch_valid_t<double>(P, write_mask);
-    return hipGetLastError() == hipSuccess ? XDEMHIP_OK : xd_fail(P->ctx, XDEMHIP_EHIP, "dh_valid_kernel launch failed");
+    return launched(P->ctx, "dh_valid_kernel");
 }
 
 // the valid mask, built on first need (the subsample and values routes; the whole-raster moments and median recompute validity).  The
@@ -611,7 +589,7 @@ int ensure_mask(xdemhip_dh_plan* P) {
     const int rc = launch_valid(P, true);
     if (rc) return rc;
     hipLaunchKernelGGL(rank_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, P->tile_off, P->n_tiles, P->tile_off + P->n_tiles);
-    return hipGetLastError() == hipSuccess ? XDEMHIP_OK : xd_fail(ctx, XDEMHIP_EHIP, "dh_scan_kernel launch failed");
+    return launched(ctx, "dh_scan_kernel");
 }
 
 // the list of all valid pixels (raster order), for the values route of a plan that was never subsampled
@@ -626,7 +604,7 @@ int ensure_valid_idx(xdemhip_dh_plan* P) {
     }
     hipLaunchKernelGGL((rank_select_kernel<RankOut::List>), dim3((unsigned)P->n_tiles), dim3(256), 0, ctx->stream, P->valid, P->H * P->W,
                        (const unsigned long long*)nullptr, (const uint8_t*)nullptr, P->tile_off, P->idx, (uint8_t*)nullptr);
-    if (hipGetLastError() != hipSuccess) return xd_fail(ctx, XDEMHIP_EHIP, "dh_sel_kernel launch failed");
+    if (launched(ctx, "dh_sel_kernel")) return XDEMHIP_EHIP;
     P->n_idx = P->n_valid;
     return XDEMHIP_OK;
 }
@@ -650,7 +628,7 @@ int median_typed(xdemhip_dh_plan* P, double* median, int64_t* count) {
                            P->W, d, (int64_t*)nullptr, (int64_t*)nullptr);
     else
         hipLaunchKernelGGL((dh_dense_kernel<T>), g, dim3(256), 0, ctx->stream, static_cast<const T*>(P->ref), static_cast<const T*>(P->tba), P->inlier, n, d);
-    if (hipGetLastError() != hipSuccess) { cleanup(); return xd_fail(ctx, XDEMHIP_EHIP, "dh kernel launch failed"); }
+    if (launched(ctx, "dh kernel")) { cleanup(); return XDEMHIP_EHIP; }
     std::vector<SelResult<K>> r;
     const xdemhip_allreduce_fn hook = ctx->allreduce;   // (one process's pixels: a local selection)
     ctx->allreduce = nullptr;
@@ -725,7 +703,7 @@ int launch_shift(xdemhip_dh_plan* P, const NkGeom& g, bool with_hist, uint64_t* 
         else { if (with_hist) XD_DENSE(false, true); else XD_DENSE(false, false); }
 #undef XD_DENSE
     }
-    return hipGetLastError() == hipSuccess ? XDEMHIP_OK : xd_fail(ctx, XDEMHIP_EHIP, "dh_shift kernel launch failed");
+    return launched(ctx, "dh_shift kernel");
 }
 
 // One evaluation: the data pass, the median's selection, |dh - median|'s selection, ONE fetch.  Inputs of SEL_BRACKET_MIN_N values
@@ -772,7 +750,7 @@ int shift_nmad_typed(xdemhip_dh_plan* P, const NkGeom& g, double nfact, double* 
         if (rc) return rc;
         hipLaunchKernelGGL((dh_sel_finish_kernel<T>), dim3(1), dim3(1), 0, ctx->stream, d_st, d_succ, queued2 ? P->sel_ws.d_small : (const uint64_t*)nullptr,
                            P->sel_ws.nb_max, 1, d_out);
-        if (hipGetLastError() != hipSuccess) return xd_fail(ctx, XDEMHIP_EHIP, "dh selection kernel launch failed");
+        if (launched(ctx, "dh selection kernel")) return XDEMHIP_EHIP;
         rc = xd_d2h(ctx, &h, d_out, sizeof h);
         if (rc == XDEMHIP_OK) rc = xd_sync(ctx);
         if (rc) return rc;
@@ -804,9 +782,46 @@ inline void norm_axis(int64_t n_global, double* a, double* b) {
 
 }  // namespace
 
-// what rigid.hip needs of the plan's lazily built parts (dh_plan.h)
+// what rigid.hip and icp.hip need of the plan's lazily built parts (dh_plan.h)
 int dh_ensure_mask(xdemhip_dh_plan* P) { return ensure_mask(P); }
 int dh_ensure_valid_idx(xdemhip_dh_plan* P) { return ensure_valid_idx(P); }
+// ---- the reduce kernel and the host side of the fixed-order sums (fixed_sums.h) -----------------------------------------------------
+// per-workgroup partials -> totals: one workgroup per term, lane l adds the partials of workgroups l, l + 256, ... in order, then a
+// fixed tree over the lanes (the same bits every call)
+static __global__ __launch_bounds__(256) void fixed_sums_reduce_kernel(const double* __restrict__ part, int nblocks, int nt, double* __restrict__ out) {
+    __shared__ double s[256];
+    const int t = blockIdx.x;
+    double a = 0.0;
+    for (int b = threadIdx.x; b < nblocks; b += 256) a += part[(int64_t)b * nt + t];
+    s[threadIdx.x] = a;
+    __syncthreads();
+    for (int half = 128; half > 0; half >>= 1) {
+        if ((int)threadIdx.x < half) s[threadIdx.x] += s[threadIdx.x + half];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[t] = s[0];
+}
+int FixedSums::reserve(xdemhip_ctx* ctx, int nt, const char* who) {
+    const int64_t need = ((int64_t)ctx->num_cu * 8 + 1) * nt;
+    if (cap >= need) return XDEMHIP_OK;
+    if (part) { (void)hipStreamSynchronize(ctx->stream); release(); }
+    if (hipMalloc(reinterpret_cast<void**>(&part), (size_t)need * 8) != hipSuccess) {
+        (void)hipGetLastError();
+        part = nullptr;
+        return xd_fail(ctx, XDEMHIP_ENOMEM, std::string("hipMalloc failed (") + who + ")");
+    }
+    cap = need;
+    return XDEMHIP_OK;
+}
+int fixed_sums_finish(xdemhip_ctx* ctx, const FixedSums& fs, int nblocks, int nt, const char* what, double* totals) {
+    double* d_out = fs.part + (int64_t)nblocks * nt;
+    hipLaunchKernelGGL(fixed_sums_reduce_kernel, dim3((unsigned)nt), dim3(256), 0, ctx->stream, fs.part, nblocks, nt, d_out);
+    int rc = launched(ctx, what);
+    (void)hipEventRecord(ctx->ev_stop, ctx->stream);
+    ctx->timed = (rc == XDEMHIP_OK);
+    if (rc == XDEMHIP_OK) rc = xd_d2h(ctx, totals, d_out, (size_t)nt * 8);   // the one fetch of the call
+    return rc == XDEMHIP_OK ? xd_sync(ctx) : rc;
+}
 }  // namespace xd
 
 using namespace xd;
@@ -828,7 +843,7 @@ void xdemhip_dh_destroy(xdemhip_dh_plan* P) {
     if (P->sel_scratch) (void)hipFree(P->sel_scratch);
     if (P->gradx) (void)hipFree(P->gradx);
     if (P->grady) (void)hipFree(P->grady);
-    if (P->lzd_part) (void)hipFree(P->lzd_part);
+    P->sums.release();
     for (int a = 0; a < 3; ++a)
         if (P->icp_n[a]) (void)hipFree(P->icp_n[a]);
     sel_ws_free(P->sel_ws);
@@ -874,7 +889,7 @@ int xdemhip_dh_create(xdemhip_ctx* ctx, const void* ref, const void* tba, const 
     // (counts only: the mask itself is built by the routes that read it)
     { const int rc_ = launch_valid(P, false); if (rc_) return fail(rc_); }
     hipLaunchKernelGGL(rank_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, P->tile_off, P->n_tiles, P->tile_off + P->n_tiles);
-    if (hipGetLastError() != hipSuccess) return fail(xd_fail(ctx, XDEMHIP_EHIP, "xdemhip_dh_create: kernel launch failed"));
+    if (launched(ctx, "xdemhip_dh_create: kernel")) return fail(XDEMHIP_EHIP);
     unsigned long long total = 0;
     { const int rc_ = xd_d2h(ctx, &total, P->tile_off + P->n_tiles, 8); if (rc_) return fail(rc_); }
     { const int rc_ = xd_sync(ctx); if (rc_) return fail(rc_); }
@@ -905,7 +920,7 @@ int xdemhip_dh_subsample(xdemhip_dh_plan* P, const int64_t* ranks, int64_t k, in
     }
     hipLaunchKernelGGL((rank_select_kernel<RankOut::List>), dim3((unsigned)P->n_tiles), dim3(256), 0, ctx->stream, P->valid, P->H * P->W, P->tile_off,
                        rs.mark, rs.off, idx, (uint8_t*)nullptr);
-    int rc = hipGetLastError() == hipSuccess ? XDEMHIP_OK : xd_fail(ctx, XDEMHIP_EHIP, "xdemhip_dh_subsample: kernel launch failed");
+    int rc = launched(ctx, "xdemhip_dh_subsample: kernel");
     if (rc == XDEMHIP_OK) rc = xd_sync(ctx);
     if (rc) { (void)hipFree(idx); return rc; }
     if (P->idx) (void)hipFree(P->idx);
@@ -933,33 +948,17 @@ int xdemhip_dh_poly_moments(xdemhip_dh_plan* P, int order, int64_t row_offset, i
     double ax, bx, ay, by;
     norm_axis(W_global, &ax, &bx);
     norm_axis(H_global, &ay, &by);
-    const int64_t max_blocks = (int64_t)ctx->num_cu * 8;
-    double* d_part = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&d_part), (size_t)(max_blocks * NT + NT) * 8) != hipSuccess) {
-        (void)hipGetLastError();
-        return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed (xdemhip_dh_poly_moments)");
-    }
+    { const int rc_ = P->sums.reserve(ctx, NT, "xdemhip_dh_poly_moments"); if (rc_) return rc_; }
     int nblocks = 0;
     (void)hipEventRecord(ctx->ev_start, ctx->stream);
-    int rc = P->dtype == XDEMHIP_F32 ? launch_moments<float>(P, order, row_offset, ax, bx, ay, by, d_part, &nblocks)
-                                     : launch_moments<double>(P, order, row_offset, ax, bx, ay, by, d_part, &nblocks);
-    if (rc == XDEMHIP_OK) {
-        double* d_out = d_part + max_blocks * NT;
-        hipLaunchKernelGGL(dh_moments_reduce_kernel, dim3((unsigned)NT), dim3(256), 0, ctx->stream, d_part, nblocks, NT, d_out);
-        if (hipGetLastError() != hipSuccess) rc = xd_fail(ctx, XDEMHIP_EHIP, "dh_moments_reduce_kernel launch failed");
-        (void)hipEventRecord(ctx->ev_stop, ctx->stream);
-        ctx->timed = (rc == XDEMHIP_OK);
-        std::vector<double> h(NT);
-        if (rc == XDEMHIP_OK) rc = xd_d2h(ctx, h.data(), d_out, (size_t)NT * 8);
-        if (rc == XDEMHIP_OK) rc = xd_sync(ctx);
-        if (rc == XDEMHIP_OK) {
-            memcpy(m_out, h.data(), (size_t)NA * NA * 8);
-            memcpy(r_out, h.data() + NA * NA, (size_t)NR * NR * 8);
-        }
-    }
-    (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_part);
-    return rc;
+    int rc = P->dtype == XDEMHIP_F32 ? launch_moments<float>(P, order, row_offset, ax, bx, ay, by, P->sums.part, &nblocks)
+                                     : launch_moments<double>(P, order, row_offset, ax, bx, ay, by, P->sums.part, &nblocks);
+    double h[PolyTerms<DH_MAX_ORDER>::NT];
+    if (rc == XDEMHIP_OK) rc = fixed_sums_finish(ctx, P->sums, nblocks, NT, "dh_moments_reduce_kernel", h);
+    if (rc) return rc;
+    memcpy(m_out, h, (size_t)NA * NA * 8);
+    memcpy(r_out, h + NA * NA, (size_t)NR * NR * 8);
+    return XDEMHIP_OK;
 }
 
 int xdemhip_dh_median(xdemhip_dh_plan* P, double* median, int64_t* count) {
@@ -1004,7 +1003,7 @@ int xdemhip_dh_values(xdemhip_dh_plan* P, void* dh_out, int64_t* col_out, int64_
         else
             hipLaunchKernelGGL((dh_gather_kernel<double>), g, dim3(256), 0, ctx->stream, static_cast<const double*>(P->ref), static_cast<const double*>(P->tba),
                                P->idx, k, P->W, static_cast<double*>(d_dh), d_col, d_row);
-        if (hipGetLastError() != hipSuccess) rc = xd_fail(ctx, XDEMHIP_EHIP, "dh_gather_kernel launch failed");
+        rc = launched(ctx, "dh_gather_kernel");
     }
     if (rc == XDEMHIP_OK && own) {
         if (dh_out && hipMemcpyAsync(dh_out, d_dh, (size_t)k * es, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = xd_fail(ctx, XDEMHIP_EHIP, "D2H copy failed");
@@ -1071,7 +1070,7 @@ int xdemhip_dh_shift_values(xdemhip_dh_plan* P, double shift_x, double shift_y, 
     else
         hipLaunchKernelGGL((dh_shift_list_kernel<double, false>), grid, dim3(256), 0, ctx->stream, static_cast<const double*>(P->ref),
                            static_cast<const double*>(P->tba), P->idx, k, g, invW, static_cast<double*>(d_dh), (uint64_t*)nullptr);
-    if (hipGetLastError() != hipSuccess) return xd_fail(ctx, XDEMHIP_EHIP, "dh_shift_list_kernel launch failed");
+    if (launched(ctx, "dh_shift_list_kernel")) return XDEMHIP_EHIP;
     if (memspace == XDEMHIP_HOST) {
         if (hipMemcpyAsync(dh_out, d_dh, (size_t)k * es, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) return xd_fail(ctx, XDEMHIP_EHIP, "D2H copy failed");
         rc = xd_sync(ctx);

@@ -77,6 +77,34 @@ inline int xd_fail(xdemhip_ctx* ctx, int code, const std::string& msg) {
     return code;
 }
 
+// after one or more kernel launches: XDEMHIP_OK, or XDEMHIP_EHIP with "`what` launch failed"
+inline int launched(xdemhip_ctx* ctx, const char* what) {
+    return hipGetLastError() == hipSuccess ? XDEMHIP_OK : xd_fail(ctx, XDEMHIP_EHIP, std::string(what) + " launch failed");
+}
+
+// A device buffer for the length of a scope.  `rc` is XDEMHIP_ENOMEM with "hipMalloc failed (`who`)" where there is none; at the end
+// of the scope the stream is synchronised (the queued work may still use the buffer) and the buffer freed.  Host destinations of
+// copies queued on the stream are declared BEFORE it, so that they outlive that synchronisation on every return path.
+struct XdScratch {
+    xdemhip_ctx* ctx;
+    void* p = nullptr;
+    int rc = XDEMHIP_OK;
+    XdScratch(xdemhip_ctx* c, size_t bytes, const char* who) : ctx(c) {
+        if (hipMalloc(&p, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            p = nullptr;
+            rc = xd_fail(ctx, XDEMHIP_ENOMEM, std::string("hipMalloc failed (") + who + ")");
+        }
+    }
+    ~XdScratch() {
+        if (!p) return;
+        (void)hipStreamSynchronize(ctx->stream);
+        (void)hipFree(p);
+    }
+    XdScratch(const XdScratch&) = delete;
+    XdScratch& operator=(const XdScratch&) = delete;
+};
+
 // Queue a small device-to-host copy whose destination is filled by the next xd_sync(ctx) (falls back to a plain copy when
 // the staging buffer is full).  `dst` must stay alive until that xd_sync; xd_drop_pending forgets undelivered blocks (entry
 // points call it on their way in and out, so an error return never leaves a dangling destination behind).

@@ -1,9 +1,11 @@
 // dh_plan.h -- the dh plan (elevation difference of two rasters on one grid) as the translation units that work on it see it:
-// biascorr.hip creates and destroys it, rigid.hip adds the LZD passes, icp.hip the normal planes of ICP.
+// biascorr.hip creates and destroys it, rigid.hip adds the LZD passes, icp.hip the normal planes of ICP.  The fixed-order sums of
+// the moments and of the LZD normal equations go through the plan's one partials buffer (fixed_sums.h); ICP's through its own.
 #pragma once
 #include "common.h"
 #include "select.h"
 #include "select_run.h"
+#include "fixed_sums.h"
 
 struct xdemhip_dh_plan {
     xdemhip_ctx* ctx = nullptr;
@@ -26,12 +28,11 @@ struct xdemhip_dh_plan {
     unsigned char* sel_scratch = nullptr;     // selection states, successor keys, histograms (scratch_size(1)), then the DhEvalOut block
     xd::SelWorkspace sel_ws;                  // sample / candidate buffers of the bracketed selection (stage_n >= SEL_BRACKET_MIN_N)
     int64_t sel_ws_n = 0;
+    xd::FixedSums sums;                       // per-workgroup partials and totals of the moments (biascorr.hip) and of the LZD normal equations
     // LZD (rigid.hip): gradient planes of ref in the raster dtype, made at the first LZD call, kept until the plan goes
     void* gradx = nullptr;                    // gradient_x / res_x
     void* grady = nullptr;                    // -gradient_y / res_y
     double grad_res_x = 0.0, grad_res_y = 0.0;  // the resolutions the planes were formed with
-    double* lzd_part = nullptr;               // per-workgroup partials and totals of the normal-equation pass
-    int64_t lzd_part_n = 0;
     // ICP (icp.hip): the normal planes nx, ny, nz of ref in the raster dtype; making them narrows `valid` by their finiteness
     void* icp_n[3] = {nullptr, nullptr, nullptr};
     double icp_res_x = 0.0, icp_res_y = 0.0;

@@ -10,7 +10,8 @@
 //   _icp_fit_func and its least squares                                  affine.py:773-974   -> icp_sums_kernel: J^T J, J^T r
 // Everything is float64 without contraction (-ffp-contract=off).  The search is exact: the squared distance is dx dx + dy dy + dz dz
 // in that order, ties go to the lowest reference index, and a ring walk stops only when no unvisited cell can hold a point as near.
-// The sums are added in a fixed order: two calls return the same bits.
+// The sums are added in a fixed order: two calls return the same bits (fixed_sums.h, shared with biascorr.hip and rigid.hip; the
+// gradient stencil, the matrix product and the transform check are those of rigid.hip: rigid_geom.h).
 #include <math.h>
 #include <string.h>
 
@@ -20,6 +21,7 @@
 #include "select.h"
 #include "select_run.h"
 #include "rank_select.h"
+#include "rigid_geom.h"
 #include "dh_plan.h"
 
 struct xdemhip_icp {
@@ -48,8 +50,7 @@ struct xdemhip_icp {
     int64_t* pair_r = nullptr;
     int64_t k = -1;
     bool picky = false;
-    double* part = nullptr;
-    int64_t part_n = 0;
+    xd::FixedSums sums;                         // per-workgroup partials and totals of the fit's sums (fixed_sums.h)
 };
 
 namespace xd {
@@ -57,8 +58,6 @@ namespace {
 
 constexpr int ICP_NS = 37;   // 21 upper-triangle terms of J J^T, 6 of J r, r^2, 9 moments of p' (squares, products, sums)
 constexpr double ICP_OCCUPANCY = 3.0;
-
-__device__ __forceinline__ bool d_finite(double v) { return fabs(v) <= 1.79769313486231570e308; }
 
 // ---- normal planes ---------------------------------------------------------------------------------------------------------------
 // sin(arctan(g)) = g / sqrt(1 + g^2), evaluated in float64 and rounded once to the raster dtype (|g| = inf and beyond 1e150: +-1)
@@ -69,7 +68,7 @@ template <typename T> __device__ __forceinline__ T sin_atan(T g) {
     return (T)(d / sqrt(1.0 + d * d));
 }
 
-// np.gradient(ref) in the raster dtype; nx = -sin(arctan(d/dcol / res_y)), ny = sin(arctan(d/drow / res_x)) -- upstream's pairing --
+// np.gradient(ref) in the raster dtype (np_gradient_at, rigid_geom.h); nx = -sin(arctan(d/dcol / res_y)), ny = sin(arctan(d/drow / res_x)) -- upstream's pairing --
 // nz = 1 - sqrt(nx^2 + ny^2) in the dtype.  valid[p] loses the pixels where a plane is not finite.  H, W >= 2.
 template <typename T>
 __global__ __launch_bounds__(256) void icp_normals_kernel(const T* __restrict__ ref, int64_t H, int64_t W, T res_x, T res_y, T* __restrict__ pnx,
@@ -78,12 +77,7 @@ __global__ __launch_bounds__(256) void icp_normals_kernel(const T* __restrict__ 
     for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (int64_t)gridDim.x * blockDim.x) {
         const int64_t r = p / W, c = p - r * W;
         T gc, gr;
-        if (c == 0) gc = t_sub(ref[p + 1], ref[p]);
-        else if (c == W - 1) gc = t_sub(ref[p], ref[p - 1]);
-        else gc = t_div(t_sub(ref[p + 1], ref[p - 1]), (T)2);
-        if (r == 0) gr = t_sub(ref[p + W], ref[p]);
-        else if (r == H - 1) gr = t_sub(ref[p], ref[p - W]);
-        else gr = t_div(t_sub(ref[p + W], ref[p - W]), (T)2);
+        np_gradient_at<T>(ref, H, W, r, c, gc, gr);
         const T vx = -sin_atan<T>(t_div(gc, res_y));
         const T vy = sin_atan<T>(t_div(gr, res_x));
         const T vz = t_sub((T)1, (T)sqrt(t_add(t_mul(vx, vx), t_mul(vy, vy))));
@@ -173,8 +167,6 @@ __global__ __launch_bounds__(256) void icp_cell_scatter_kernel(const double* __r
 }
 
 // ---- the query -------------------------------------------------------------------------------------------------------------------
-struct Mat12 { double m[12]; };
-
 // One thread per query point: the point under the matrix, then rings of cells (Chebyshev distance 0, 1, 2, ... around the cell the
 // point falls in, clamped to the grid).  A row of a ring's cells is one contiguous run of the sorted arrays.  After ring k every cell
 // not yet seen lies beyond column cx -+ k or row cy -+ k: its points are at least `d` away in x or y, d taken from the point's own
@@ -186,10 +178,8 @@ __global__ __launch_bounds__(256) void icp_query_kernel(Grid g, const unsigned l
                                                         int64_t* __restrict__ ind, double* __restrict__ dist) {
     const double EPS = 2.220446049250313e-16;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (int64_t)gridDim.x * blockDim.x) {
-        const double x = qx[i], y = qy[i], z = qz[i];
-        const double px = ((M.m[0] * x + M.m[1] * y) + M.m[2] * z) + M.m[3];
-        const double py = ((M.m[4] * x + M.m[5] * y) + M.m[6] * z) + M.m[7];
-        const double pz = ((M.m[8] * x + M.m[9] * y) + M.m[10] * z) + M.m[11];
+        double px, py, pz;
+        mat12_apply(M.m, qx[i], qy[i], qz[i], px, py, pz);
         tx[i] = px; ty[i] = py; tz[i] = pz;
         const int cx = cell_of(px, g.x0, g.h, g.gx), cy = cell_of(py, g.y0, g.h, g.gy);
         int last = cx;
@@ -264,15 +254,6 @@ __global__ __launch_bounds__(256) void icp_picky3_kernel(const unsigned long lon
 }
 
 // ---- the sums of the fit ---------------------------------------------------------------------------------------------------------
-template <typename V> __device__ __forceinline__ V block_sum(V x, V* red) {
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
-    __syncthreads();
-    const V r = ((red[0] + red[1]) + red[2]) + red[3];
-    __syncthreads();
-    return r;
-}
-
 struct PairSrc {
     const int64_t* pair_r;              // picky: the reference indexes kept, ascending; else null
     const unsigned long long* bestq;    // picky: the query index of each reference index
@@ -286,7 +267,8 @@ __device__ __forceinline__ void pair_of(const PairSrc& s, int64_t p, int64_t& qi
 // For every kept pair: p' = S t, the residual r and its row J = [p' x n, n] (point-to-plane, r = (p' - q) . n) or [p' x u, u]
 // (point-to-point, r = |p' - q|, u = (p' - q) / r, a zero row where r = 0) about p', and the nine moments of p' from which the host
 // forms the normal matrix of the vector residual p' - q (point-to-point: the rows of the scalar distance leave out r grad^2 r =
-// I - u u^T, which is not small).  Per-lane accumulators, one partial per workgroup: part[b * (ICP_NS + 1) + k], slot ICP_NS = the count.
+// I - u u^T, which is not small).  Per-lane accumulators, one partial per workgroup (block_sums_store, fixed_sums.h):
+// part[b * (ICP_NS + 1) + k], slot ICP_NS = the count.
 __global__ __launch_bounds__(256) void icp_sums_kernel(PairSrc src, int64_t k, const double* __restrict__ tx, const double* __restrict__ ty,
                                                        const double* __restrict__ tz, const double* __restrict__ rx, const double* __restrict__ ry,
                                                        const double* __restrict__ rz, const double* __restrict__ nx, const double* __restrict__ ny,
@@ -300,10 +282,8 @@ __global__ __launch_bounds__(256) void icp_sums_kernel(PairSrc src, int64_t k, c
         int64_t qi, ri;
         pair_of(src, p, qi, ri);
         if (ri < 0 || qi < 0) continue;   // (a query that found nothing: a non-finite point)
-        const double x = tx[qi], y = ty[qi], z = tz[qi];
-        const double px = ((S.m[0] * x + S.m[1] * y) + S.m[2] * z) + S.m[3];
-        const double py = ((S.m[4] * x + S.m[5] * y) + S.m[6] * z) + S.m[7];
-        const double pz = ((S.m[8] * x + S.m[9] * y) + S.m[10] * z) + S.m[11];
+        double px, py, pz;
+        mat12_apply(S.m, tx[qi], ty[qi], tz[qi], px, py, pz);
         const double dx = px - rx[ri], dy = py - ry[ri], dz = pz - rz[ri];
         double ux, uy, uz, r;
         if (plane) {
@@ -328,30 +308,7 @@ __global__ __launch_bounds__(256) void icp_sums_kernel(PairSrc src, int64_t k, c
         s[34] += px; s[35] += py; s[36] += pz;
         cnt += 1.0;
     }
-    double* out = part + (int64_t)blockIdx.x * (ICP_NS + 1);
-#pragma unroll
-    for (int t = 0; t < ICP_NS; ++t) {
-        const double v = block_sum<double>(s[t], red);
-        if (threadIdx.x == 0) out[t] = v;
-    }
-    const double v = block_sum<double>(cnt, red);
-    if (threadIdx.x == 0) out[ICP_NS] = v;
-}
-
-// per-workgroup partials -> totals: one workgroup per term, lane l adds the partials of workgroups l, l + 256, ... in order, then a
-// fixed tree over the lanes
-__global__ __launch_bounds__(256) void icp_reduce_kernel(const double* __restrict__ part, int nblocks, int nt, double* __restrict__ out) {
-    __shared__ double s[256];
-    const int t = blockIdx.x;
-    double a = 0.0;
-    for (int b = threadIdx.x; b < nblocks; b += 256) a += part[(int64_t)b * nt + t];
-    s[threadIdx.x] = a;
-    __syncthreads();
-    for (int half = 128; half > 0; half >>= 1) {
-        if ((int)threadIdx.x < half) s[threadIdx.x] += s[threadIdx.x + half];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[t] = s[0];
+    block_sums_store<ICP_NS>(s, cnt, red, part);
 }
 
 // the kept pairs as upstream hands them to _icp_fit: out rows 0-2 = ref, 3-5 = the moved query points, 6-8 = the normals (k each)
@@ -382,17 +339,6 @@ template <typename P> int icp_alloc(xdemhip_icp* I, P** p, size_t bytes, const c
     }
     I->owned.push_back(d);
     *p = static_cast<P*>(d);
-    return XDEMHIP_OK;
-}
-
-int launched(xdemhip_ctx* ctx, const char* what) {
-    return hipGetLastError() == hipSuccess ? XDEMHIP_OK : xd_fail(ctx, XDEMHIP_EHIP, std::string(what) + " launch failed");
-}
-
-int icp_check_transform(xdemhip_ctx* ctx, const double* t, const char* who) {
-    if (!t) return xd_fail(ctx, XDEMHIP_EINVAL, "null argument");
-    if (t[1] != 0.0 || t[3] != 0.0 || !(fabs(t[0]) > 0) || !(fabs(t[4]) > 0) || !isfinite(t[0]) || !isfinite(t[4]) || !isfinite(t[2]) || !isfinite(t[5]))
-        return xd_fail(ctx, XDEMHIP_EINVAL, std::string(who) + ": transform6 = (a, 0, c, 0, e, f) with finite entries and a, e != 0");
     return XDEMHIP_OK;
 }
 
@@ -480,6 +426,7 @@ void icp_free(xdemhip_icp* I) {
     (void)hipSetDevice(I->ctx->device);
     (void)hipStreamSynchronize(I->ctx->stream);
     for (void* p : I->owned) (void)hipFree(p);
+    I->sums.release();
     delete I;
 }
 
@@ -522,7 +469,7 @@ int xdemhip_dh_icp_normals(xdemhip_dh_plan* P, const double* transform6, void* n
     if (!P) return XDEMHIP_EINVAL;
     xdemhip_ctx* ctx = P->ctx;
     if (memspace != XDEMHIP_HOST && memspace != XDEMHIP_DEVICE) return xd_fail(ctx, XDEMHIP_EINVAL, "bad memspace");
-    { const int rc_ = icp_check_transform(ctx, transform6, "xdemhip_dh_icp_normals"); if (rc_) return rc_; }
+    { const int rc_ = check_transform(ctx, transform6, "xdemhip_dh_icp_normals"); if (rc_) return rc_; }
     if (P->H < 2 || P->W < 2) return xd_fail(ctx, XDEMHIP_EINVAL, "ICP normals need a raster of at least 2 x 2 pixels (np.gradient)");
     XD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     const double res_x = fabs(transform6[0]), res_y = fabs(transform6[4]);
@@ -556,7 +503,7 @@ int xdemhip_icp_create_plan(xdemhip_dh_plan* P, const double* transform6, int wi
     if (!P) return XDEMHIP_EINVAL;
     xdemhip_ctx* ctx = P->ctx;
     if (!out || !centroid3 || !std_fac) return xd_fail(ctx, XDEMHIP_EINVAL, "null argument");
-    { const int rc_ = icp_check_transform(ctx, transform6, "xdemhip_icp_create_plan"); if (rc_) return rc_; }
+    { const int rc_ = check_transform(ctx, transform6, "xdemhip_icp_create_plan"); if (rc_) return rc_; }
     if (with_normals && !P->icp_n[0]) return xd_fail(ctx, XDEMHIP_EINVAL, "xdemhip_icp_create_plan: call xdemhip_dh_icp_normals first");
     XD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     { const int rc_ = dh_ensure_valid_idx(P); if (rc_) return rc_; }
@@ -754,18 +701,16 @@ int xdemhip_icp_pairs(xdemhip_icp* I, int picky, int64_t* n_kept, int64_t* query
     *n_kept = I->k;
     if ((query_idx_out || ref_idx_out) && I->k > 0) {
         if (!query_idx_out || !ref_idx_out) return xd_fail(ctx, XDEMHIP_EINVAL, "xdemhip_icp_pairs: both index outputs or none");
-        int64_t* d = nullptr;
-        if (hipMalloc(reinterpret_cast<void**>(&d), (size_t)I->k * 16) != hipSuccess) { (void)hipGetLastError(); return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed (xdemhip_icp_pairs)"); }
+        XdScratch buf(ctx, (size_t)I->k * 16, "xdemhip_icp_pairs");
+        if (buf.rc) return buf.rc;
+        int64_t* d = static_cast<int64_t*>(buf.p);
         hipLaunchKernelGGL(icp_values_kernel, dim3(grid_for(ctx, I->k, 256, 16)), dim3(256), 0, ctx->stream, pair_src(I), I->k, I->tx, I->ty, I->tz, I->rx, I->ry,
                            I->rz, I->nx, I->ny, I->nz, (double*)nullptr, d, d + I->k);
         int rc = launched(ctx, "icp_values_kernel");
         if (rc == XDEMHIP_OK && (hipMemcpyAsync(query_idx_out, d, (size_t)I->k * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
                                  hipMemcpyAsync(ref_idx_out, d + I->k, (size_t)I->k * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess))
             rc = xd_fail(ctx, XDEMHIP_EHIP, "D2H copy failed");
-        if (rc == XDEMHIP_OK) rc = xd_sync(ctx);
-        (void)hipStreamSynchronize(ctx->stream);
-        (void)hipFree(d);
-        return rc;
+        return rc == XDEMHIP_OK ? xd_sync(ctx) : rc;
     }
     return XDEMHIP_OK;
 }
@@ -782,29 +727,15 @@ int xdemhip_icp_sums(xdemhip_icp* I, const double* step16, int method, double* s
     if (I->k == 0) return xd_fail(ctx, XDEMHIP_EINVAL, "no valid points");
     XD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     const int NT = ICP_NS + 1;
-    int64_t nb = (int64_t)ctx->num_cu * 8;
-    const int64_t units = (I->k + 255) / 256;
-    if (nb > units) nb = units;
-    if (nb < 1) nb = 1;
-    const int64_t need = nb * NT + NT;
-    if (I->part_n < need) {   // (the old buffer stays owned until the object goes)
-        { const int rc_ = icp_alloc(I, &I->part, (size_t)((int64_t)ctx->num_cu * 8 * NT + NT) * 8, "ICP partial sums"); if (rc_) return rc_; }
-        I->part_n = (int64_t)ctx->num_cu * 8 * NT + NT;
-    }
+    const int nb = fixed_sums_grid(ctx, (I->k + 255) / 256);
+    { const int rc_ = I->sums.reserve(ctx, NT, "ICP partial sums"); if (rc_) return rc_; }
     Mat12 S;
     memcpy(S.m, step16, sizeof S.m);
-    double* d_out = I->part + nb * NT;
     (void)hipEventRecord(ctx->ev_start, ctx->stream);
     hipLaunchKernelGGL(icp_sums_kernel, dim3((unsigned)nb), dim3(256), 0, ctx->stream, pair_src(I), I->k, I->tx, I->ty, I->tz, I->rx, I->ry, I->rz, I->nx, I->ny,
-                       I->nz, S, method, I->part);
-    hipLaunchKernelGGL(icp_reduce_kernel, dim3((unsigned)NT), dim3(256), 0, ctx->stream, I->part, (int)nb, NT, d_out);
-    int rc = launched(ctx, "icp_sums_kernel");
-    (void)hipEventRecord(ctx->ev_stop, ctx->stream);
-    ctx->timed = (rc == XDEMHIP_OK);
+                       I->nz, S, method, I->sums.part);
     double h[ICP_NS + 1];
-    if (rc == XDEMHIP_OK) rc = xd_d2h(ctx, h, d_out, sizeof h);   // the one fetch of the evaluation
-    if (rc == XDEMHIP_OK) rc = xd_sync(ctx);
-    if (rc) return rc;
+    { const int rc_ = fixed_sums_finish(ctx, I->sums, nb, NT, "icp_sums_kernel", h); if (rc_) return rc_; }
     memcpy(sums_out, h, ICP_NS * 8);
     *count = (int64_t)h[ICP_NS];
     return XDEMHIP_OK;
@@ -818,16 +749,14 @@ int xdemhip_icp_values(xdemhip_icp* I, double* out9k) {
     if (I->k < 0) return xd_fail(ctx, XDEMHIP_EINVAL, "xdemhip_icp_values: call xdemhip_icp_pairs first");
     if (I->k == 0) return xd_fail(ctx, XDEMHIP_EINVAL, "no valid points");
     XD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    double* d = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&d), (size_t)I->k * 72) != hipSuccess) { (void)hipGetLastError(); return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed (xdemhip_icp_values)"); }
+    XdScratch buf(ctx, (size_t)I->k * 72, "xdemhip_icp_values");
+    if (buf.rc) return buf.rc;
+    double* d = static_cast<double*>(buf.p);
     hipLaunchKernelGGL(icp_values_kernel, dim3(grid_for(ctx, I->k, 256, 16)), dim3(256), 0, ctx->stream, pair_src(I), I->k, I->tx, I->ty, I->tz, I->rx, I->ry, I->rz,
                        I->nx, I->ny, I->nz, d, (int64_t*)nullptr, (int64_t*)nullptr);
     int rc = launched(ctx, "icp_values_kernel");
     if (rc == XDEMHIP_OK && hipMemcpyAsync(out9k, d, (size_t)I->k * 72, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = xd_fail(ctx, XDEMHIP_EHIP, "D2H copy failed");
-    if (rc == XDEMHIP_OK) rc = xd_sync(ctx);
-    (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d);
-    return rc;
+    return rc == XDEMHIP_OK ? xd_sync(ctx) : rc;
 }
 
 }  // extern "C"

@@ -9,7 +9,9 @@
 //   _iterate_affine_regrid_small_rotations(resampling="linear")          base.py:1389-1519         -> apply_matrix_kernel
 // The model is linear in its six parameters, so what upstream's least_squares converges to is the solution of the normal equations
 // (the precedent: Deramp's moments).  Everything is float64 without contraction (-ffp-contract=off) and summed in a fixed order: two
-// calls return the same bits, and the per-pixel values are bit for bit those of tests/rigid_oracle.py.
+// calls return the same bits, and the per-pixel values are bit for bit those of tests/rigid_oracle.py.  The order of the sums and the
+// host sequence around them are those of fixed_sums.h; the gradient stencil, the matrix product and the transform check are shared with
+// icp.hip (rigid_geom.h).
 #include <math.h>
 #include <string.h>
 
@@ -21,6 +23,7 @@
 #include "rank_select.h"
 #include "nk_geom.h"
 #include "bi_point.h"
+#include "rigid_geom.h"
 #include "dh_plan.h"
 
 namespace xd {
@@ -37,18 +40,15 @@ struct Rigid {
     int has_centroid;
 };
 
-// p' = M (p - centroid) + centroid, the products as explicit sums in the order m0 x + m1 y + m2 z + m3
+// p' = M (p - centroid) + centroid (mat12_apply, rigid_geom.h)
 __device__ __forceinline__ void rigid_apply(const double* m, const Rigid& R, double x, double y, double z, double& ox, double& oy, double& oz) {
     if (R.has_centroid) { x = x - R.cx; y = y - R.cy; z = z - R.cz; }
-    ox = ((m[0] * x + m[1] * y) + m[2] * z) + m[3];
-    oy = ((m[4] * x + m[5] * y) + m[6] * z) + m[7];
-    oz = ((m[8] * x + m[9] * y) + m[10] * z) + m[11];
+    mat12_apply(m, x, y, z, ox, oy, oz);
     if (R.has_centroid) { ox = ox + R.cx; oy = oy + R.cy; oz = oz + R.cz; }
 }
-__device__ __forceinline__ bool d_finite(double v) { return fabs(v) <= 1.79769313486231570e308; }
 
 // ---- gradient planes -----------------------------------------------------------------------------------------------------------
-// np.gradient(ref) in the raster dtype (central differences, one-sided at the borders), gradx = gx / res_x, grady = -gy / res_y with
+// np.gradient(ref) in the raster dtype (np_gradient_at, rigid_geom.h), gradx = gx / res_x, grady = -gy / res_y with
 // the resolution taken to the raster dtype first (NumPy 2: a Python float next to a float32 array is a float32).  H, W >= 2.
 template <typename T>
 __global__ __launch_bounds__(256) void lzd_gradient_kernel(const T* __restrict__ ref, int64_t H, int64_t W, T res_x, T res_y, T* __restrict__ gradx,
@@ -57,12 +57,7 @@ __global__ __launch_bounds__(256) void lzd_gradient_kernel(const T* __restrict__
     for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (int64_t)gridDim.x * blockDim.x) {
         const int64_t r = p / W, c = p - r * W;
         T gx, gy;
-        if (c == 0) gx = t_sub(ref[p + 1], ref[p]);
-        else if (c == W - 1) gx = t_sub(ref[p], ref[p - 1]);
-        else gx = t_div(t_sub(ref[p + 1], ref[p - 1]), (T)2);
-        if (r == 0) gy = t_sub(ref[p + W], ref[p]);
-        else if (r == H - 1) gy = t_sub(ref[p], ref[p - W]);
-        else gy = t_div(t_sub(ref[p + W], ref[p - W]), (T)2);
+        np_gradient_at<T>(ref, H, W, r, c, gx, gy);
         gradx[p] = t_div(gx, res_x);
         grady[p] = t_div(-gy, res_y);
     }
@@ -90,16 +85,6 @@ __device__ __forceinline__ bool lzd_pixel(const T* __restrict__ ref, const T* __
     return d_finite(o.dh) && d_finite(o.z) && d_finite(o.gx) && d_finite(o.gy);
 }
 
-// sum over the workgroup (256 lanes = 4 waves): wave shuffles, then the four waves in order
-template <typename V> __device__ __forceinline__ V block_sum(V x, V* red) {
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
-    __syncthreads();
-    const V r = ((red[0] + red[1]) + red[2]) + red[3];
-    __syncthreads();
-    return r;
-}
-
 __device__ __forceinline__ void lzd_accumulate(const LzdPixel& p, double* s) {
     const double a[6] = {-p.gx, -p.gy, 1.0, p.y + p.gy * p.z, -p.x - p.gx * p.z, p.gx * p.y - p.gy * p.x};
     int k = 0;
@@ -115,7 +100,8 @@ __device__ __forceinline__ void lzd_accumulate(const LzdPixel& p, double* s) {
 
 // The hot kernel.  Dense route (idx == nullptr): workgroup b takes the tiles b, b + gridDim.x, ... of the valid mask (RANK_TILE pixels
 // each, a lane strides through a tile so that a wave reads consecutive pixels).  List route: the drawn pixels, grid-strided.  Per-lane
-// float64 accumulators, one partial per workgroup: part[b * (LZD_NS + 1) + k], slot LZD_NS = the count (exact in float64).
+// float64 accumulators, one partial per workgroup (block_sums_store, fixed_sums.h): part[b * (LZD_NS + 1) + k], slot LZD_NS = the count
+// (exact in float64).
 template <typename T>
 __global__ __launch_bounds__(256) void lzd_normal_kernel(const T* __restrict__ ref, const T* __restrict__ tba, const T* __restrict__ gradx,
                                                          const T* __restrict__ grady, const uint8_t* __restrict__ valid,
@@ -144,30 +130,7 @@ __global__ __launch_bounds__(256) void lzd_normal_kernel(const T* __restrict__ r
             }
         }
     }
-    double* out = part + (int64_t)blockIdx.x * (LZD_NS + 1);
-#pragma unroll
-    for (int k = 0; k < LZD_NS; ++k) {
-        const double v = block_sum<double>(s[k], red);
-        if (threadIdx.x == 0) out[k] = v;
-    }
-    const double v = block_sum<double>(cnt, red);
-    if (threadIdx.x == 0) out[LZD_NS] = v;
-}
-
-// per-workgroup partials -> totals: one workgroup per term, lane l adds the partials of workgroups l, l + 256, ... in order, then a
-// fixed tree over the lanes (the same bits every call)
-__global__ __launch_bounds__(256) void lzd_reduce_kernel(const double* __restrict__ part, int nblocks, int nt, double* __restrict__ out) {
-    __shared__ double s[256];
-    const int t = blockIdx.x;
-    double a = 0.0;
-    for (int b = threadIdx.x; b < nblocks; b += 256) a += part[(int64_t)b * nt + t];
-    s[threadIdx.x] = a;
-    __syncthreads();
-    for (int half = 128; half > 0; half >>= 1) {
-        if ((int)threadIdx.x < half) s[threadIdx.x] += s[threadIdx.x + half];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[t] = s[0];
+    block_sums_store<LZD_NS>(s, cnt, red, part);
 }
 
 // centroid sums over the listed pixels: integer sums of row and column, the float64 sum of tba in a fixed order.  ipart[b * 2 + 0 / 1],
@@ -239,13 +202,6 @@ __global__ __launch_bounds__(256) void apply_matrix_kernel(const T* __restrict__
     }
 }
 
-int check_transform(xdemhip_ctx* ctx, const double* t, const char* who) {
-    if (!t) return xd_fail(ctx, XDEMHIP_EINVAL, "null argument");
-    if (t[1] != 0.0 || t[3] != 0.0 || !(fabs(t[0]) > 0) || !(fabs(t[4]) > 0) || !isfinite(t[0]) || !isfinite(t[4]) || !isfinite(t[2]) || !isfinite(t[5]))
-        return xd_fail(ctx, XDEMHIP_EINVAL, std::string(who) + ": transform6 = (a, 0, c, 0, e, f) with finite entries and a, e != 0");
-    return XDEMHIP_OK;
-}
-
 // (the inverse of the rigid matrix: R^T and -(R^T t), the products as explicit sums)
 Rigid make_rigid(const double* t, const double* m16, const double* centroid) {
     Rigid R;
@@ -283,7 +239,7 @@ int ensure_gradients_t(xdemhip_dh_plan* P, double res_x, double res_y) {
     }
     hipLaunchKernelGGL((lzd_gradient_kernel<T>), dim3(grid_for(ctx, n, 256, 16)), dim3(256), 0, ctx->stream, static_cast<const T*>(P->ref), P->H, P->W,
                        (T)res_x, (T)res_y, static_cast<T*>(P->gradx), static_cast<T*>(P->grady));
-    if (hipGetLastError() != hipSuccess) return xd_fail(ctx, XDEMHIP_EHIP, "lzd_gradient_kernel launch failed");
+    if (launched(ctx, "lzd_gradient_kernel")) return XDEMHIP_EHIP;
     P->grad_res_x = res_x; P->grad_res_y = res_y;
     return XDEMHIP_OK;
 }
@@ -345,26 +301,22 @@ int xdemhip_dh_lzd_centroid(xdemhip_dh_plan* P, const double* transform6, double
     if (count) *count = k;
     if (k == 0) return xd_fail(ctx, XDEMHIP_EINVAL, "no valid points");
     const int nblocks = grid_for(ctx, k, 256, 4);
-    unsigned long long* d_ip = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&d_ip), (size_t)(nblocks + 1) * 24) != hipSuccess) {
-        (void)hipGetLastError();
-        return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed (xdemhip_dh_lzd_centroid)");
-    }
+    unsigned long long hi[2] = {0, 0};   // (the fetches' destinations: declared first, they outlive the scratch buffer's synchronisation)
+    double hz = 0.0;
+    XdScratch buf(ctx, (size_t)(nblocks + 1) * 24, "xdemhip_dh_lzd_centroid");
+    if (buf.rc) return buf.rc;
     // layout: integer partials (2 per workgroup) and totals (2), then the float64 partials and total
+    unsigned long long* d_ip = static_cast<unsigned long long*>(buf.p);
     unsigned long long* d_iout = d_ip + 2 * (size_t)nblocks;
     double* d_dp = reinterpret_cast<double*>(d_iout + 2);
     double* d_dout = d_dp + nblocks;
     if (P->dtype == XDEMHIP_F32) launch_centroid<float>(P, nblocks, d_ip, d_dp);
     else launch_centroid<double>(P, nblocks, d_ip, d_dp);
     hipLaunchKernelGGL(lzd_centroid_reduce_kernel, dim3(1), dim3(64), 0, ctx->stream, d_ip, d_dp, nblocks, d_iout, d_dout);
-    int rc = hipGetLastError() == hipSuccess ? XDEMHIP_OK : xd_fail(ctx, XDEMHIP_EHIP, "lzd_centroid_kernel launch failed");
-    unsigned long long hi[2] = {0, 0};
-    double hz = 0.0;
+    int rc = launched(ctx, "lzd_centroid_kernel");
     if (rc == XDEMHIP_OK) rc = xd_d2h(ctx, hi, d_iout, 16);
     if (rc == XDEMHIP_OK) rc = xd_d2h(ctx, &hz, d_dout, 8);
     if (rc == XDEMHIP_OK) rc = xd_sync(ctx);
-    (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_ip);
     if (rc) return rc;
     const double nk = (double)k;
     centroid_out[0] = transform6[2] + ((double)hi[1] / nk + 0.5) * transform6[0];
@@ -385,37 +337,16 @@ int xdemhip_dh_lzd_normal(xdemhip_dh_plan* P, const double* transform6, const do
     XD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     if (!P->drawn) { const int rc_ = dh_ensure_mask(P); if (rc_) return rc_; }
     { const int rc_ = ensure_gradients(P, transform6); if (rc_) return rc_; }
-    const int64_t units = P->drawn ? (P->n_idx + 255) / 256 : P->n_tiles;
-    int64_t nb = (int64_t)ctx->num_cu * 8;
-    if (nb > units) nb = units;
-    if (nb < 1) nb = 1;
+    const int nb = fixed_sums_grid(ctx, P->drawn ? (P->n_idx + 255) / 256 : P->n_tiles);
     const int NT = LZD_NS + 1;
-    // the partials and the totals behind them: made at the first call, kept by the plan (nothing is allocated per iteration)
-    const int64_t need = nb * NT + NT;
-    if (P->lzd_part_n < need) {
-        if (P->lzd_part) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(P->lzd_part); P->lzd_part = nullptr; P->lzd_part_n = 0; }
-        if (hipMalloc(reinterpret_cast<void**>(&P->lzd_part), (size_t)need * 8) != hipSuccess) {
-            (void)hipGetLastError();
-            P->lzd_part = nullptr;
-            return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed (xdemhip_dh_lzd_normal)");
-        }
-        P->lzd_part_n = need;
-    }
-    double* d_part = P->lzd_part;
+    { const int rc_ = P->sums.reserve(ctx, NT, "xdemhip_dh_lzd_normal"); if (rc_) return rc_; }
     const NkGeom g = lzd_geom(P);
     const Rigid R = make_rigid(transform6, matrix16, centroid3);
     (void)hipEventRecord(ctx->ev_start, ctx->stream);
-    if (P->dtype == XDEMHIP_F32) launch_normal<float>(P, g, R, (int)nb, d_part);
-    else launch_normal<double>(P, g, R, (int)nb, d_part);
-    double* d_out = d_part + nb * NT;
-    hipLaunchKernelGGL(lzd_reduce_kernel, dim3((unsigned)NT), dim3(256), 0, ctx->stream, d_part, (int)nb, NT, d_out);
-    int rc = hipGetLastError() == hipSuccess ? XDEMHIP_OK : xd_fail(ctx, XDEMHIP_EHIP, "lzd_normal_kernel launch failed");
-    (void)hipEventRecord(ctx->ev_stop, ctx->stream);
-    ctx->timed = (rc == XDEMHIP_OK);
+    if (P->dtype == XDEMHIP_F32) launch_normal<float>(P, g, R, nb, P->sums.part);
+    else launch_normal<double>(P, g, R, nb, P->sums.part);
     double h[LZD_NS + 1];
-    if (rc == XDEMHIP_OK) rc = xd_d2h(ctx, h, d_out, sizeof h);   // the one fetch of the call
-    if (rc == XDEMHIP_OK) rc = xd_sync(ctx);
-    if (rc) return rc;
+    { const int rc_ = fixed_sums_finish(ctx, P->sums, nb, NT, "lzd_normal_kernel", h); if (rc_) return rc_; }
     memcpy(sums_out, h, LZD_NS * 8);
     *count = (int64_t)h[LZD_NS];
     return XDEMHIP_OK;
@@ -434,19 +365,17 @@ int xdemhip_dh_lzd_values(xdemhip_dh_plan* P, const double* transform6, const do
     const int64_t n = P->n_idx;
     if (n == 0) return xd_fail(ctx, XDEMHIP_EINVAL, "no valid points");
     { const int rc_ = ensure_gradients(P, transform6); if (rc_) return rc_; }
-    double* d_out = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&d_out), (size_t)n * 49) != hipSuccess) {   // six float64 rows, then the keep bytes
-        (void)hipGetLastError();
-        return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed (xdemhip_dh_lzd_values)");
-    }
+    std::vector<double> h;          // (the copies' destinations: declared first, so that they outlive the scratch buffer's synchronisation)
+    std::vector<uint8_t> keep;
+    XdScratch buf(ctx, (size_t)n * 49, "xdemhip_dh_lzd_values");   // six float64 rows, then the keep bytes
+    if (buf.rc) return buf.rc;
+    double* d_out = static_cast<double*>(buf.p);
     uint8_t* d_keep = reinterpret_cast<uint8_t*>(d_out + 6 * n);
     const NkGeom g = lzd_geom(P);
     const Rigid R = make_rigid(transform6, matrix16, centroid3);
     if (P->dtype == XDEMHIP_F32) launch_values<float>(P, g, R, d_out, d_keep);
     else launch_values<double>(P, g, R, d_out, d_keep);
-    int rc = hipGetLastError() == hipSuccess ? XDEMHIP_OK : xd_fail(ctx, XDEMHIP_EHIP, "lzd_values_kernel launch failed");
-    std::vector<double> h;
-    std::vector<uint8_t> keep;
+    int rc = launched(ctx, "lzd_values_kernel");
     if (rc == XDEMHIP_OK) {
         h.resize((size_t)6 * n);
         keep.resize((size_t)n);
@@ -455,8 +384,6 @@ int xdemhip_dh_lzd_values(xdemhip_dh_plan* P, const double* transform6, const do
             rc = xd_fail(ctx, XDEMHIP_EHIP, "D2H copy failed");
     }
     if (rc == XDEMHIP_OK) rc = xd_sync(ctx);
-    (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_out);
     if (rc) return rc;
     // the pixels left, in raster order: row a of the result starts at out[a * n] (n = the selection's size), *count entries are filled
     int64_t m = 0;
@@ -504,7 +431,7 @@ int xdemhip_apply_matrix_rst(xdemhip_ctx* ctx, const void* dem, int dtype, int64
         else
             hipLaunchKernelGGL((apply_matrix_kernel<double>), grid, dim3(256), 0, ctx->stream, static_cast<const double*>(d_in), H, W, R, tol_x, tol_y,
                                static_cast<double*>(d_out));
-        if (hipGetLastError() != hipSuccess) rc = xd_fail(ctx, XDEMHIP_EHIP, "apply_matrix_kernel launch failed");
+        rc = launched(ctx, "apply_matrix_kernel");
         (void)hipEventRecord(ctx->ev_stop, ctx->stream);
         ctx->timed = (rc == XDEMHIP_OK);
     }

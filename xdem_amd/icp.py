@@ -13,20 +13,20 @@ Every pass over the rasters and the clouds runs in ``csrc/icp.hip``:
   from the device and runs on the host exactly as ``_icp_fit`` calls it.
 
 The clouds' coordinates are pixel centres under the 6-tuple transform, as in ``xdem_amd.rigid``; NMAD is ``1.4826 * median|v - median v|``
-(geoutils' ``nmad`` is absent: **parity unpinned**).  ``CPD``, point-cloud inputs and ``initial_shift`` are not implemented."""
+(geoutils' ``nmad`` is absent: **parity unpinned**).  ``CPD``, point-cloud inputs and ``initial_shift`` are not implemented.  The front
+of ``fit``, the iteration loop, ``apply`` and the accessors are ``rigid._RigidStep``'s; ``solve_scaled`` is ``rigid``'s."""
 from __future__ import annotations
 
 import ctypes
-import logging
 from typing import Any, Callable
 
 import numpy as np
 import scipy.optimize
 
 from . import _lib
-from ._coregbase import _Plan, _Step, _with_transform, draw
-from .biascorr import DhPlan, _check_weights, _host_array
-from .rigid import _c6, _transform6, apply_matrix, matrix_from_translations_rotations, translations_rotations_from_matrix
+from ._coregbase import _Plan, draw
+from .biascorr import DhPlan
+from .rigid import _c6, _iterate, _RigidStep, matrix_from_translations_rotations, solve_scaled, translations_rotations_from_matrix
 
 _DP = ctypes.POINTER(ctypes.c_double)
 _IP = ctypes.POINTER(ctypes.c_int64)
@@ -181,20 +181,6 @@ def normal_system(sums: np.ndarray, count: int = 0, vector: bool = False) -> tup
     return N, b
 
 
-def solve_scaled(N: np.ndarray, b: np.ndarray) -> np.ndarray:
-    """N x = b in float64 after scaling by N's diagonal, minimum-norm where N is singular (``rigid.solve_normal``'s solve)."""
-    d = np.sqrt(np.diag(N))
-    d = np.where(d > 0, 1.0 / np.where(d > 0, d, 1.0), 1.0)
-    Ns, bs = N * d[:, None] * d[None, :], b * d
-    try:
-        q = np.linalg.solve(Ns, bs)
-        if not np.all(np.isfinite(q)):
-            raise np.linalg.LinAlgError
-    except np.linalg.LinAlgError:
-        q = np.linalg.lstsq(Ns, bs, rcond=None)[0]
-    return q * d
-
-
 def gn_update(sums: np.ndarray, count: int = 0, only_translation: bool = False, vector: bool = False) -> np.ndarray:
     """The Gauss-Newton update (omega, dt) -- 6 numbers, omega = 0 with ``only_translation`` -- from the sums."""
     N, b = normal_system(sums, count, vector)
@@ -255,7 +241,7 @@ def fit_func(inputs, params, method: str) -> np.ndarray:
 
 
 # ---- ICP ----------------------------------------------------------------------------------------------------------------------------
-class ICP(_Step):
+class ICP(_RigidStep):
     """Iterative closest point registration: a rigid transform (rotation + translation) between two DEMs on one grid.  Constructor of
     ``xdem.coreg.ICP`` (affine.py:2137-2181).  The estimated transform lands in ``meta["outputs"]["affine"]``: "matrix", rotation
     centred on "centroid", and the translations "shift_x", "shift_y", "shift_z"."""
@@ -288,7 +274,7 @@ class ICP(_Step):
             return "device"
         return "host"
 
-    def _check(self) -> str:
+    def _check(self) -> None:
         method = self.meta["inputs"]["specific"]["icp_method"]
         if method not in METHODS:
             raise ValueError(BAD_METHOD)
@@ -298,7 +284,6 @@ class ICP(_Step):
                 raise ValueError(BAD_LSQ_APPROX)
         elif not callable(fm):
             raise TypeError(f"Argument `fit_minimizer` must be a function (callable) or \"lsq_approx\", got {type(fm)}.")
-        return method
 
     def _step_matrix(self, cloud: IcpCloud, k: int, method: str, **kwargs: Any) -> np.ndarray:
         """The step transform of one iteration from the pairs the cloud holds (``_icp_fit``)."""
@@ -322,84 +307,21 @@ class ICP(_Step):
         ``icp``, affine.py:1084-1182).  The grid comes from ``transform``, or from ``resolution`` alone (then its origin is the
         lower-left corner).  ``kwargs`` go to ``fit_minimizer`` (and select the host route); the iterations' matrices (standardised
         coordinates) and statistics land in ``meta["outputs"]["iterative"]``."""
-        _check_weights(weights)
-        if bias_vars is not None:
-            raise NotImplementedError("bias_vars is not used by ICP.")
-        if hasattr(reference_elev, "geometry") or hasattr(to_be_aligned_elev, "geometry"):
-            raise NotImplementedError("point-cloud inputs are not supported: both elevation datasets must be arrays on one grid")
-        method = self._check()
-        if subsample is not None:
-            self.meta["inputs"]["random"]["subsample"] = subsample
-        if random_state is not None:
-            self.meta["inputs"]["random"]["random_state"] = random_state
-        it, spec = self.meta["inputs"]["iterative"], self.meta["inputs"]["specific"]
-        plane = method == "point-to-plane"
-        logging.info("Running ICP coregistration")
-        with DhPlan(reference_elev, to_be_aligned_elev, inlier_mask) as plan:
-            if plan.shape[0] < 2 or plan.shape[1] < 2:
-                raise ValueError("Shape of array too small for calculating a numerical gradient, at least (edge_order + 1) elements are required.")
-            t6 = _transform6(transform, resolution, plan.shape)
+        with self._open(reference_elev, to_be_aligned_elev, inlier_mask, bias_vars, weights, subsample, random_state, transform, resolution) as (plan, t6):
+            it, spec = self.meta["inputs"]["iterative"], self.meta["inputs"]["specific"]
+            method = spec["icp_method"]
+            plane = method == "point-to-plane"
             if plane:
                 icp_normals(plan, t6, fetch=False)
             n = draw(plan, self.meta["inputs"]["random"]["subsample"], self.meta["inputs"]["random"]["random_state"])
             with IcpCloud.from_plan(plan, t6, plane, bool(self.meta["inputs"]["affine"]["standardize"])) as cloud:
-                tolerance = it["tolerance"] / cloud.std_fac
-                matrix = np.eye(4)
-                history = []
-                for i in range(int(it["max_iterations"])):   # _iterate_method (affine.py:102-147) over _icp_iteration_step
+
+                def step_matrix(matrix: np.ndarray) -> np.ndarray:   # _icp_iteration_step: query, picky removal, fit
                     cloud.query(matrix, fetch=False)
-                    k = cloud.pairs(bool(spec["icp_picky"]))
-                    step = self._step_matrix(cloud, k, method, **kwargs)
-                    matrix = step @ matrix
-                    stat = float(np.sqrt(np.sum(step[:3, 3]) ** 2))   # upstream's statistic: |t1 + t2 + t3|
-                    history.append((matrix.copy(), stat))
-                    if i > 1 and stat < tolerance:
-                        break
-                matrix = matrix.copy()
+                    return self._step_matrix(cloud, cloud.pairs(bool(spec["icp_picky"])), method, **kwargs)
+
+                matrix, history = _iterate(step_matrix, it["max_iterations"], it["tolerance"] / cloud.std_fac)
                 matrix[:3, 3] *= cloud.std_fac
                 centroid = cloud.centroid
-        self.meta["outputs"]["affine"] = {"centroid": centroid, "matrix": matrix, "shift_x": matrix[0, 3], "shift_y": matrix[1, 3],
-                                          "shift_z": matrix[2, 3]}
-        self.meta["outputs"]["random"] = {"subsample_final": int(n)}
-        self.meta["outputs"]["iterative"] = {"last_iteration": len(history), "last_tolerance": history[-1][1] if history else None,
-                                             "matrices": [h[0] for h in history], "statistics": [h[1] for h in history]}
+        self._store(centroid, matrix, n, history)
         return self
-
-    def apply(self, elev, bias_vars=None, resample: bool = True, resampling: str = "bilinear", transform=None, crs=None, z_name=None,
-              resolution=None):
-        """``Coreg.apply`` for an affine method that is no translation (base.py:2701-2725): ``apply_matrix`` with the stored matrix
-        around the stored centroid.  With ``transform=`` the call returns ``(array, transform)``, with ``resolution=`` the array."""
-        if "affine" not in self.meta["outputs"]:
-            raise AssertionError(".fit() does not seem to have been called yet")
-        if bias_vars is not None:
-            raise NotImplementedError("bias_vars is not used by ICP.")
-        if not resample:
-            raise NotImplementedError(f"Option `resample=False` not supported by {self.__class__},"
-                                      f" only available for translation coregistrations such as NuthKaab.")
-        if resampling not in ("bilinear", "linear"):
-            raise NotImplementedError(f"resampling={resampling!r}: only \"linear\" is implemented for matrices with a rotation.")
-        arr = _host_array(elev)
-        t6 = _transform6(transform, resolution, np.shape(arr))
-        out, _ = apply_matrix(arr, self.to_matrix(), centroid=self.meta["outputs"]["affine"]["centroid"], resample=True, resampling="linear",
-                              transform=t6)
-        return _with_transform(out, transform)
-
-    @property
-    def is_affine(self) -> bool:
-        return True
-
-    def to_matrix(self) -> np.ndarray:
-        return np.array(self.meta["outputs"]["affine"]["matrix"], dtype=np.float64)
-
-    def centroid(self) -> tuple[float, float, float] | None:
-        """The centroid the rotation is centred on (``AffineCoreg.centroid``); None before ``fit``."""
-        return self.meta["outputs"].get("affine", {}).get("centroid")
-
-    def to_translations(self) -> tuple[float, float, float]:
-        m = self.to_matrix()
-        return (float(m[0, 3]), float(m[1, 3]), float(m[2, 3]))
-
-    def to_rotations(self, return_degrees: bool = True) -> tuple[float, float, float]:
-        """Extrinsic Euler rotations about X, Y and Z of the estimated transform."""
-        r = translations_rotations_from_matrix(self.to_matrix(), return_degrees=return_degrees)[3:]
-        return (float(r[0]), float(r[1]), float(r[2]))

@@ -16,9 +16,12 @@ Every pass over the grids runs in ``csrc/rigid.hip``:
 
 The grid's coordinates are pixel centres under the 6-tuple transform ``(a, b, c, d, e, f)``: ``x = c + (col + 0.5) a``,
 ``y = f + (row + 0.5) e`` -- geoutils' ``_coords`` / ``_interp_points`` / ``to_pointcloud`` are un-vendored and absent, **parity unpinned**;
-the convention is self-consistent (an identity matrix samples pixel (r, c) at (r, c))."""
+the convention is self-consistent (an identity matrix samples pixel (r, c) at (r, c)).
+
+``_RigidStep`` carries what LZD and ``xdem_amd.icp.ICP`` share: the front of ``fit``, the iteration loop, the outputs, ``apply`` and the accessors."""
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import logging
 from typing import Any, Callable
@@ -210,15 +213,8 @@ def lzd_values(plan: DhPlan, t6, matrix, centroid) -> np.ndarray:
     return np.ascontiguousarray(out[:, : int(cnt.value)])
 
 
-def solve_normal(sums: np.ndarray, only_translation: bool = False) -> np.ndarray:
-    """The least-squares parameters ``(t1, t2, t3[, alpha1, alpha2, alpha3])`` from the 29 sums: N p = b with N the (leading 3 x 3 of the)
-    6 x 6 normal matrix, solved in float64 after scaling by its diagonal (minimum-norm where N is singular, e.g. a flat reference)."""
-    N = np.zeros((6, 6), dtype=np.float64)
-    N[np.triu_indices(6)] = sums[:21]
-    N = N + np.triu(N, 1).T
-    b = np.array(sums[21:27], dtype=np.float64)
-    k = 3 if only_translation else 6
-    N, b = N[:k, :k], b[:k]
+def solve_scaled(N: np.ndarray, b: np.ndarray) -> np.ndarray:
+    """N x = b in float64 after scaling by N's diagonal, minimum-norm where N is singular (e.g. a flat reference)."""
     d = np.sqrt(np.diag(N))
     d = np.where(d > 0, 1.0 / np.where(d > 0, d, 1.0), 1.0)
     Ns, bs = N * d[:, None] * d[None, :], b * d
@@ -231,6 +227,15 @@ def solve_normal(sums: np.ndarray, only_translation: bool = False) -> np.ndarray
     return q * d
 
 
+def solve_normal(sums: np.ndarray, only_translation: bool = False) -> np.ndarray:
+    """The least-squares parameters ``(t1, t2, t3[, alpha1, alpha2, alpha3])`` from the 29 sums: N p = b with N the (leading 3 x 3 of the)
+    6 x 6 normal matrix (``solve_scaled``)."""
+    N = np.zeros((6, 6), dtype=np.float64)
+    N[np.triu_indices(6)] = sums[:21]
+    k = 3 if only_translation else 6
+    return solve_scaled((N + np.triu(N, 1).T)[:k, :k], np.array(sums[21:27], dtype=np.float64)[:k])
+
+
 def design_rows(arrays) -> np.ndarray:
     """(6, k): the model's derivatives by (t1, t2, t3, alpha1, alpha2, alpha3) per pixel -- the rows the kernel accumulates:
     (-gx, -gy, 1, y + gy z, -x - gx z, gx y - gy x).  The model is linear: its residual is ``p @ rows - dh``."""
@@ -238,8 +243,96 @@ def design_rows(arrays) -> np.ndarray:
     return np.array([-gx, -gy, np.ones_like(x), y + gy * z, -x - gx * z, gx * y - gy * x])
 
 
+# ---- what LZD and ICP share ---------------------------------------------------------------------------------------------------------
+def _iterate(step_matrix: Callable[[np.ndarray], np.ndarray], max_iterations: int, tolerance: float) -> tuple[np.ndarray, list]:
+    """Upstream's ``_iterate_method`` (affine.py:102-147): ``step_matrix(matrix)`` makes an iteration's step from the transform so far.
+    Returns the transform and the ``(transform, statistic)`` of every iteration; the statistic is upstream's, |t1 + t2 + t3|."""
+    matrix, history = np.eye(4), []
+    for i in range(int(max_iterations)):
+        step = step_matrix(matrix)
+        matrix = step @ matrix
+        stat = float(np.sqrt(np.sum(step[:3, 3]) ** 2))
+        history.append((matrix.copy(), stat))
+        if i > 1 and stat < tolerance:
+            break
+    return matrix, history
+
+
+class _RigidStep(_Step):
+    """What the steps that estimate a rotation and a translation (LZD, ICP) share -- the counterpart of ``coreg._TranslationStep``: the
+    front of ``fit``, the writing of its outputs, ``apply`` through ``apply_matrix`` and the accessors of the stored transform."""
+
+    def _check(self) -> None:   # (a step's own checks of its inputs, made before anything of the call is stored)
+        pass
+
+    @contextlib.contextmanager
+    def _open(self, reference_elev, to_be_aligned_elev, inlier_mask, bias_vars, weights, subsample, random_state, transform, resolution):
+        """The front of ``fit``: the refusals, ``subsample`` / ``random_state`` into ``meta``, the dh plan (at least 2 x 2), the transform."""
+        name = type(self).__name__
+        _check_weights(weights)
+        if bias_vars is not None:
+            raise NotImplementedError(f"bias_vars is not used by {name}.")
+        if hasattr(reference_elev, "geometry") or hasattr(to_be_aligned_elev, "geometry"):
+            raise NotImplementedError("point-cloud inputs are not supported: both elevation datasets must be arrays on one grid")
+        self._check()
+        if subsample is not None:
+            self.meta["inputs"]["random"]["subsample"] = subsample
+        if random_state is not None:
+            self.meta["inputs"]["random"]["random_state"] = random_state
+        logging.info(f"Running {name} coregistration")
+        with DhPlan(reference_elev, to_be_aligned_elev, inlier_mask) as plan:
+            if plan.shape[0] < 2 or plan.shape[1] < 2:
+                raise ValueError("Shape of array too small for calculating a numerical gradient, at least (edge_order + 1) elements are required.")
+            yield plan, _transform6(transform, resolution, plan.shape)
+
+    def _store(self, centroid, matrix: np.ndarray, n: int, history: list) -> None:
+        """``meta["outputs"]`` of a fit: "affine", "random", "iterative"."""
+        self.meta["outputs"]["affine"] = {"centroid": centroid, "matrix": matrix, "shift_x": matrix[0, 3], "shift_y": matrix[1, 3],
+                                          "shift_z": matrix[2, 3]}
+        self.meta["outputs"]["random"] = {"subsample_final": int(n)}
+        self.meta["outputs"]["iterative"] = {"last_iteration": len(history), "last_tolerance": history[-1][1] if history else None,
+                                             "matrices": [h[0] for h in history], "statistics": [h[1] for h in history]}
+
+    def apply(self, elev, bias_vars=None, resample: bool = True, resampling: str = "bilinear", transform=None, crs=None, z_name=None,
+              resolution=None):
+        """``Coreg.apply`` for an affine method that is no translation (base.py:2701-2725): ``apply_matrix`` with the stored matrix
+        around the stored centroid.  With ``transform=`` the call returns ``(array, transform)``, with ``resolution=`` the array."""
+        if "affine" not in self.meta["outputs"]:
+            raise AssertionError(".fit() does not seem to have been called yet")
+        if bias_vars is not None:
+            raise NotImplementedError(f"bias_vars is not used by {type(self).__name__}.")
+        if not resample:
+            raise NotImplementedError(f"Option `resample=False` not supported by {self.__class__},"
+                                      f" only available for translation coregistrations such as NuthKaab.")
+        if resampling not in ("bilinear", "linear"):
+            raise NotImplementedError(f"resampling={resampling!r}: only \"linear\" is implemented for matrices with a rotation.")
+        arr = _host_array(elev)
+        t6 = _transform6(transform, resolution, np.shape(arr))
+        out, _ = apply_matrix(arr, self.to_matrix(), centroid=self.meta["outputs"]["affine"]["centroid"], resample=True, resampling="linear",
+                              transform=t6)
+        return _with_transform(out, transform)
+
+    @property
+    def is_affine(self) -> bool:
+        return True
+
+    def to_matrix(self) -> np.ndarray:
+        return np.array(self.meta["outputs"]["affine"]["matrix"], dtype=np.float64)
+
+    def centroid(self) -> tuple[float, float, float] | None:
+        """The centroid the rotation is centred on (``AffineCoreg.centroid``); None before ``fit``."""
+        return self.meta["outputs"].get("affine", {}).get("centroid")
+
+    def to_translations(self) -> tuple[float, float, float]:
+        return tuple(float(v) for v in self.to_matrix()[:3, 3])
+
+    def to_rotations(self, return_degrees: bool = True) -> tuple[float, float, float]:
+        """Extrinsic Euler rotations about X, Y and Z of the estimated transform."""
+        return tuple(float(v) for v in translations_rotations_from_matrix(self.to_matrix(), return_degrees=return_degrees)[3:])
+
+
 # ---- LZD ----------------------------------------------------------------------------------------------------------------------------
-class LZD(_Step):
+class LZD(_RigidStep):
     """Least Z-difference coregistration (Rosenholm & Torlegard 1988): a rigid transform (rotation + translation) between two DEMs on
     one grid.  Constructor of ``xdem.coreg.LZD`` (affine.py:2559-2589).  The estimated transform lands in
     ``meta["outputs"]["affine"]``: "matrix", rotation centred on "centroid", and the translations "shift_x", "shift_y", "shift_z"."""
@@ -292,74 +385,10 @@ class LZD(_Step):
         ``_fit_rst_rst``, affine.py:1680-1776).  The grid comes from ``transform``, or from ``resolution`` alone (then its origin is
         the lower-left corner).  ``kwargs`` go to ``fit_minimizer`` (and select the host route); the iterations' matrices and
         statistics land in ``meta["outputs"]["iterative"]``."""
-        _check_weights(weights)
-        if bias_vars is not None:
-            raise NotImplementedError("bias_vars is not used by LZD.")
-        if hasattr(reference_elev, "geometry") or hasattr(to_be_aligned_elev, "geometry"):
-            raise NotImplementedError("point-cloud inputs are not supported: both elevation datasets must be arrays on one grid")
-        if subsample is not None:
-            self.meta["inputs"]["random"]["subsample"] = subsample
-        if random_state is not None:
-            self.meta["inputs"]["random"]["random_state"] = random_state
-        it = self.meta["inputs"]["iterative"]
-        logging.info("Running LZD coregistration")
-        with DhPlan(reference_elev, to_be_aligned_elev, inlier_mask) as plan:
-            if plan.shape[0] < 2 or plan.shape[1] < 2:
-                raise ValueError("Shape of array too small for calculating a numerical gradient, at least (edge_order + 1) elements are required.")
-            t6 = _transform6(transform, resolution, plan.shape)
+        with self._open(reference_elev, to_be_aligned_elev, inlier_mask, bias_vars, weights, subsample, random_state, transform, resolution) as (plan, t6):
             n = draw(plan, self.meta["inputs"]["random"]["subsample"], self.meta["inputs"]["random"]["random_state"])
             centroid, _ = lzd_centroid(plan, t6)
-            matrix = np.eye(4)
-            history = []
-            for i in range(int(it["max_iterations"])):   # _iterate_method (affine.py:102-147)
-                step = self._step_matrix(plan, t6, matrix, centroid, **kwargs)
-                matrix = step @ matrix
-                stat = float(np.sqrt(np.sum(step[:3, 3]) ** 2))   # upstream's statistic: |t1 + t2 + t3|
-                history.append((matrix.copy(), stat))
-                if i > 1 and stat < it["tolerance"]:
-                    break
-        self.meta["outputs"]["affine"] = {"centroid": centroid, "matrix": matrix, "shift_x": matrix[0, 3], "shift_y": matrix[1, 3],
-                                          "shift_z": matrix[2, 3]}
-        self.meta["outputs"]["random"] = {"subsample_final": int(n)}
-        self.meta["outputs"]["iterative"] = {"last_iteration": len(history), "last_tolerance": history[-1][1] if history else None,
-                                             "matrices": [h[0] for h in history], "statistics": [h[1] for h in history]}
+            it = self.meta["inputs"]["iterative"]
+            matrix, history = _iterate(lambda m: self._step_matrix(plan, t6, m, centroid, **kwargs), it["max_iterations"], it["tolerance"])
+        self._store(centroid, matrix, n, history)
         return self
-
-    def apply(self, elev, bias_vars=None, resample: bool = True, resampling: str = "bilinear", transform=None, crs=None, z_name=None,
-              resolution=None):
-        """``Coreg.apply`` for an affine method that is no translation (base.py:2701-2725): ``apply_matrix`` with the stored matrix
-        around the stored centroid.  With ``transform=`` the call returns ``(array, transform)``, with ``resolution=`` the array."""
-        if "affine" not in self.meta["outputs"]:
-            raise AssertionError(".fit() does not seem to have been called yet")
-        if bias_vars is not None:
-            raise NotImplementedError("bias_vars is not used by LZD.")
-        if not resample:
-            raise NotImplementedError(f"Option `resample=False` not supported by {self.__class__},"
-                                      f" only available for translation coregistrations such as NuthKaab.")
-        if resampling not in ("bilinear", "linear"):
-            raise NotImplementedError(f"resampling={resampling!r}: only \"linear\" is implemented for matrices with a rotation.")
-        arr = _host_array(elev)
-        t6 = _transform6(transform, resolution, np.shape(arr))
-        out, _ = apply_matrix(arr, self.to_matrix(), centroid=self.meta["outputs"]["affine"]["centroid"], resample=True, resampling="linear",
-                              transform=t6)
-        return _with_transform(out, transform)
-
-    @property
-    def is_affine(self) -> bool:
-        return True
-
-    def to_matrix(self) -> np.ndarray:
-        return np.array(self.meta["outputs"]["affine"]["matrix"], dtype=np.float64)
-
-    def centroid(self) -> tuple[float, float, float] | None:
-        """The centroid the rotation is centred on (``AffineCoreg.centroid``); None before ``fit``."""
-        return self.meta["outputs"].get("affine", {}).get("centroid")
-
-    def to_translations(self) -> tuple[float, float, float]:
-        m = self.to_matrix()
-        return (float(m[0, 3]), float(m[1, 3]), float(m[2, 3]))
-
-    def to_rotations(self, return_degrees: bool = True) -> tuple[float, float, float]:
-        """Extrinsic Euler rotations about X, Y and Z of the estimated transform."""
-        r = translations_rotations_from_matrix(self.to_matrix(), return_degrees=return_degrees)[3:]
-        return (float(r[0]), float(r[1]), float(r[2]))
