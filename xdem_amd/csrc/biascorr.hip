@@ -614,35 +614,26 @@ int median_typed(xdemhip_dh_plan* P, double* median, int64_t* count) {
     typedef typename KeyT<T>::type K;
     xdemhip_ctx* ctx = P->ctx;
     const int64_t n = P->drawn ? P->n_idx : P->H * P->W;
-    T* d = nullptr;
-    void* scratch = nullptr;
-    auto cleanup = [&]() { if (d) (void)hipFree(d); if (scratch) (void)hipFree(scratch); };
-    if (hipMalloc(reinterpret_cast<void**>(&d), (size_t)n * sizeof(T)) != hipSuccess || hipMalloc(&scratch, scratch_size(1)) != hipSuccess) {
-        (void)hipGetLastError();
-        cleanup();
-        return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed (xdemhip_dh_median)");
-    }
+    XdBuffers buf(ctx, "xdemhip_dh_median");
+    T* d = buf.alloc<T>((size_t)n);
+    unsigned char* scratch = buf.alloc<unsigned char>(scratch_size(1));
+    if (buf.rc) return buf.rc;
     const dim3 g(grid_for(ctx, n, 256, 16));
     if (P->drawn)
         hipLaunchKernelGGL((dh_gather_kernel<T>), g, dim3(256), 0, ctx->stream, static_cast<const T*>(P->ref), static_cast<const T*>(P->tba), P->idx, n,
                            P->W, d, (int64_t*)nullptr, (int64_t*)nullptr);
     else
         hipLaunchKernelGGL((dh_dense_kernel<T>), g, dim3(256), 0, ctx->stream, static_cast<const T*>(P->ref), static_cast<const T*>(P->tba), P->inlier, n, d);
-    if (launched(ctx, "dh kernel")) { cleanup(); return XDEMHIP_EHIP; }
+    if (launched(ctx, "dh kernel")) return XDEMHIP_EHIP;
     std::vector<SelResult<K>> r;
-    const xdemhip_allreduce_fn hook = ctx->allreduce;   // (one process's pixels: a local selection)
-    ctx->allreduce = nullptr;
-    SelWorkspace ws;
-    if (n >= SEL_BRACKET_MIN_N) (void)sel_ws_create(ctx, n, sizeof(T), 1, ws);  // (on failure: plain selection)
-    int rc = run_select<T>(ctx, d, nullptr, n, 1, static_cast<unsigned char*>(scratch), r, &ws);
-    ctx->allreduce = hook;
+    XdLocalSelection local(ctx);   // (one process's pixels)
+    SelWorkspaceLocal lws(ctx);
+    if (n >= SEL_BRACKET_MIN_N) (void)sel_ws_create(ctx, n, sizeof(T), 1, lws.ws);  // (on failure: plain selection)
+    const int rc = run_select<T>(ctx, d, nullptr, n, 1, scratch, r, &lws.ws);
     if (rc == XDEMHIP_OK) {
         *count = (int64_t)r[0].st.count;
         *median = median_from<T>(r[0]);
     }
-    (void)hipStreamSynchronize(ctx->stream);
-    sel_ws_free(ws);
-    cleanup();
     return rc;
 }
 
@@ -763,15 +754,6 @@ int shift_nmad_typed(xdemhip_dh_plan* P, const NkGeom& g, double nfact, double* 
     return XDEMHIP_OK;
 }
 
-int upload_or_use(xdemhip_ctx* ctx, const void* src, size_t bytes, int memspace, void** dptr, bool* own) {
-    *own = false;
-    if (memspace == XDEMHIP_DEVICE) { *dptr = const_cast<void*>(src); return XDEMHIP_OK; }
-    if (hipMalloc(dptr, bytes) != hipSuccess) { (void)hipGetLastError(); *dptr = nullptr; return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed"); }
-    *own = true;
-    if (hipMemcpyAsync(*dptr, src, bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return xd_fail(ctx, XDEMHIP_EHIP, "H2D copy failed");
-    return XDEMHIP_OK;
-}
-
 inline void norm_axis(int64_t n_global, double* a, double* b) {
     double half = 0.5 * (double)(n_global - 1);
     const double centre = half;
@@ -869,11 +851,11 @@ int xdemhip_dh_create(xdemhip_ctx* ctx, const void* ref, const void* tba, const 
     if (memspace == XDEMHIP_HOST) {
         P->own_inputs = true;
         bool own = false;
-        int rc = upload_or_use(ctx, ref, (size_t)n * es, memspace, &P->ref, &own);
-        if (rc == XDEMHIP_OK) rc = upload_or_use(ctx, tba, (size_t)n * es, memspace, &P->tba, &own);
+        int rc = xd_upload_keep(ctx, ref, (size_t)n * es, memspace, &P->ref, &own);
+        if (rc == XDEMHIP_OK) rc = xd_upload_keep(ctx, tba, (size_t)n * es, memspace, &P->tba, &own);
         if (rc == XDEMHIP_OK && inlier) {
             void* d = nullptr;
-            rc = upload_or_use(ctx, inlier, (size_t)n, memspace, &d, &own);
+            rc = xd_upload_keep(ctx, inlier, (size_t)n, memspace, &d, &own);
             P->inlier = static_cast<uint8_t*>(d);
         }
         if (rc) return fail(rc);
@@ -983,40 +965,20 @@ int xdemhip_dh_values(xdemhip_dh_plan* P, void* dh_out, int64_t* col_out, int64_
     if (count) *count = k;
     if (k == 0) return xd_fail(ctx, XDEMHIP_EINVAL, "no valid points");
     const size_t es = P->dtype == XDEMHIP_F32 ? 4 : 8;
-    void* d_dh = nullptr;
-    int64_t *d_col = nullptr, *d_row = nullptr;
-    bool own = memspace == XDEMHIP_HOST;
-    if (own) {
-        if ((dh_out && hipMalloc(&d_dh, (size_t)k * es) != hipSuccess) || (col_out && hipMalloc(reinterpret_cast<void**>(&d_col), (size_t)k * 8) != hipSuccess) ||
-            (row_out && hipMalloc(reinterpret_cast<void**>(&d_row), (size_t)k * 8) != hipSuccess)) {
-            (void)hipGetLastError();
-            rc = xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed (xdemhip_dh_values)");
-        }
-    } else {
-        d_dh = dh_out; d_col = col_out; d_row = row_out;
-    }
-    if (rc == XDEMHIP_OK) {
-        const dim3 g(grid_for(ctx, k, 256, 16));
-        if (P->dtype == XDEMHIP_F32)
-            hipLaunchKernelGGL((dh_gather_kernel<float>), g, dim3(256), 0, ctx->stream, static_cast<const float*>(P->ref), static_cast<const float*>(P->tba),
-                               P->idx, k, P->W, static_cast<float*>(d_dh), d_col, d_row);
-        else
-            hipLaunchKernelGGL((dh_gather_kernel<double>), g, dim3(256), 0, ctx->stream, static_cast<const double*>(P->ref), static_cast<const double*>(P->tba),
-                               P->idx, k, P->W, static_cast<double*>(d_dh), d_col, d_row);
-        rc = launched(ctx, "dh_gather_kernel");
-    }
-    if (rc == XDEMHIP_OK && own) {
-        if (dh_out && hipMemcpyAsync(dh_out, d_dh, (size_t)k * es, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = xd_fail(ctx, XDEMHIP_EHIP, "D2H copy failed");
-        if (rc == XDEMHIP_OK && col_out && hipMemcpyAsync(col_out, d_col, (size_t)k * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = xd_fail(ctx, XDEMHIP_EHIP, "D2H copy failed");
-        if (rc == XDEMHIP_OK && row_out && hipMemcpyAsync(row_out, d_row, (size_t)k * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = xd_fail(ctx, XDEMHIP_EHIP, "D2H copy failed");
-    }
-    if (own) {
-        (void)hipStreamSynchronize(ctx->stream);
-        if (d_dh) (void)hipFree(d_dh);
-        if (d_col) (void)hipFree(d_col);
-        if (d_row) (void)hipFree(d_row);
-    }
-    return rc;
+    XdBuffers buf(ctx, "xdemhip_dh_values");
+    void* d_dh = buf.output(dh_out, (size_t)k * es, memspace);
+    int64_t* d_col = buf.output(col_out, (size_t)k * 8, memspace);
+    int64_t* d_row = buf.output(row_out, (size_t)k * 8, memspace);
+    if (buf.rc) return buf.rc;
+    const dim3 g(grid_for(ctx, k, 256, 16));
+    if (P->dtype == XDEMHIP_F32)
+        hipLaunchKernelGGL((dh_gather_kernel<float>), g, dim3(256), 0, ctx->stream, static_cast<const float*>(P->ref), static_cast<const float*>(P->tba),
+                           P->idx, k, P->W, static_cast<float*>(d_dh), d_col, d_row);
+    else
+        hipLaunchKernelGGL((dh_gather_kernel<double>), g, dim3(256), 0, ctx->stream, static_cast<const double*>(P->ref), static_cast<const double*>(P->tba),
+                           P->idx, k, P->W, static_cast<double*>(d_dh), d_col, d_row);
+    rc = launched(ctx, "dh_gather_kernel");
+    return rc == XDEMHIP_OK ? buf.finish() : rc;
 }
 
 int xdemhip_dh_shift_nmad(xdemhip_dh_plan* P, double shift_x, double shift_y, double res_x, double res_y, double nfact, double* median, double* nmad,
@@ -1032,12 +994,9 @@ int xdemhip_dh_shift_nmad(xdemhip_dh_plan* P, double shift_x, double shift_y, do
     XD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     if (!P->drawn) { const int rc_ = ensure_mask(P); if (rc_) return rc_; }
     const NkGeom g = dh_geom(P, shift_x, shift_y, res_x, res_y);
-    const xdemhip_allreduce_fn hook = ctx->allreduce;   // (one process's pixels: local selections, as in xdemhip_dh_median)
-    ctx->allreduce = nullptr;
-    const int rc = P->dtype == XDEMHIP_F32 ? shift_nmad_typed<float>(P, g, nfact, median, nmad, count)
-                                           : shift_nmad_typed<double>(P, g, nfact, median, nmad, count);
-    ctx->allreduce = hook;
-    return rc;
+    XdLocalSelection local(ctx);   // (one process's pixels, as in xdemhip_dh_median)
+    return P->dtype == XDEMHIP_F32 ? shift_nmad_typed<float>(P, g, nfact, median, nmad, count)
+                                   : shift_nmad_typed<double>(P, g, nfact, median, nmad, count);
 }
 
 int xdemhip_dh_shift_values(xdemhip_dh_plan* P, double shift_x, double shift_y, double res_x, double res_y, void* dh_out, int memspace, int64_t* count) {
@@ -1093,31 +1052,16 @@ int xdemhip_poly2d_apply(xdemhip_ctx* ctx, const void* elev, int dtype, int64_t 
     memset(&cf, 0, sizeof cf);
     for (int i = 0; i < K * K; ++i) cf.c[i] = coeffs[i];
     const size_t bytes = (size_t)(H * W) * (dtype == XDEMHIP_F32 ? 4 : 8);
-    void *d_in = nullptr, *d_out = out;
-    bool own = false;
-    int rc = upload_or_use(ctx, elev, bytes, memspace, &d_in, &own);
-    if (rc == XDEMHIP_OK && memspace == XDEMHIP_HOST && hipMalloc(&d_out, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        d_out = nullptr;
-        rc = xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed (xdemhip_poly2d_apply)");
-    }
-    if (rc == XDEMHIP_OK) {
-        (void)hipEventRecord(ctx->ev_start, ctx->stream);
-        rc = dtype == XDEMHIP_F32 ? launch_apply<float>(ctx, static_cast<const float*>(d_in), H, W, row_offset, cf, K, static_cast<float*>(d_out))
+    XdBuffers buf(ctx, "xdemhip_poly2d_apply");
+    const void* d_in = buf.input(elev, bytes, memspace);
+    void* d_out = buf.output(out, bytes, memspace);
+    if (buf.rc) return buf.rc;
+    (void)hipEventRecord(ctx->ev_start, ctx->stream);
+    int rc = dtype == XDEMHIP_F32 ? launch_apply<float>(ctx, static_cast<const float*>(d_in), H, W, row_offset, cf, K, static_cast<float*>(d_out))
                                   : launch_apply<double>(ctx, static_cast<const double*>(d_in), H, W, row_offset, cf, K, static_cast<double*>(d_out));
-        (void)hipEventRecord(ctx->ev_stop, ctx->stream);
-        ctx->timed = (rc == XDEMHIP_OK);
-    }
-    if (rc == XDEMHIP_OK && memspace == XDEMHIP_HOST) {
-        if (hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = xd_fail(ctx, XDEMHIP_EHIP, "D2H copy failed");
-        if (rc == XDEMHIP_OK) rc = xd_sync(ctx);
-    }
-    if (memspace == XDEMHIP_HOST) {
-        (void)hipStreamSynchronize(ctx->stream);
-        if (own && d_in) (void)hipFree(d_in);
-        if (d_out) (void)hipFree(d_out);
-    }
-    return rc;
+    (void)hipEventRecord(ctx->ev_stop, ctx->stream);
+    ctx->timed = (rc == XDEMHIP_OK);
+    return rc == XDEMHIP_OK ? buf.finish() : rc;
 }
 
 }  // extern "C"

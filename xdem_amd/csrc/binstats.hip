@@ -223,27 +223,17 @@ struct xdemhip_binstats {
 
 namespace {
 
-int upload(xdemhip_ctx* ctx, const void* src, size_t bytes, int memspace, void** dst, bool* own) {
-    if (memspace == XDEMHIP_DEVICE) { *dst = const_cast<void*>(src); *own = false; return XDEMHIP_OK; }
-    if (hipMalloc(dst, bytes) != hipSuccess) return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed");
-    *own = true;
-    XD_HIP_CHECK(ctx, hipMemcpyAsync(*dst, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-    return XDEMHIP_OK;
-}
-
 template <typename T>
 int run_typed(xdemhip_binstats* P, int nb, int want_nmad, double nfact, int64_t* counts, double* medians, double* nmads) {
     typedef typename KeyT<T>::type K;
     xdemhip_ctx* ctx = P->ctx;
-    void* scratch = nullptr;
-    if (hipMalloc(&scratch, scratch_size(nb)) != hipSuccess) return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc(scratch) failed");
-    unsigned char* base = static_cast<unsigned char*>(scratch);
+    XdBuffers buf(ctx, "xdemhip_binstats_run");
+    unsigned char* base = buf.alloc<unsigned char>(scratch_size(nb));
+    if (buf.rc) return buf.rc;
     std::vector<SelResult<K>> hs;
-    SelWorkspace ws;
-    if (P->n >= SEL_BRACKET_MIN_N && nb <= MAX_BINS_PER_SWEEP && sel_ws_create(ctx, P->n, sizeof(T), nb, ws) != XDEMHIP_OK) {
-        (void)hipFree(scratch);
-        return XDEMHIP_ENOMEM;
-    }
+    SelWorkspaceLocal local(ctx);
+    SelWorkspace& ws = local.ws;
+    if (P->n >= SEL_BRACKET_MIN_N && nb <= MAX_BINS_PER_SWEEP && sel_ws_create(ctx, P->n, sizeof(T), nb, ws) != XDEMHIP_OK) return XDEMHIP_ENOMEM;
     int rc = run_select<T>(ctx, static_cast<const T*>(P->values), P->bins, P->n, nb, base, hs, &ws);
     std::vector<T> med(nb);
     if (rc == XDEMHIP_OK)
@@ -254,10 +244,9 @@ int run_typed(xdemhip_binstats* P, int nb, int want_nmad, double nfact, int64_t*
         }
     if (rc == XDEMHIP_OK && want_nmad) {
         T* d_med = reinterpret_cast<T*>(base);  // (the edge area of the scratch block is free here)
-        void* d_med_big = nullptr;
         if (sizeof(T) * (size_t)nb > OFF_STATS) {
-            if (hipMalloc(&d_med_big, sizeof(T) * (size_t)nb) != hipSuccess) { (void)hipFree(scratch); return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed"); }
-            d_med = static_cast<T*>(d_med_big);
+            d_med = buf.alloc<T>((size_t)nb);
+            if (buf.rc) return buf.rc;
         }
         hipError_t e = hipMemcpyAsync(d_med, med.data(), sizeof(T) * (size_t)nb, hipMemcpyHostToDevice, ctx->stream);
         if (e == hipSuccess) {
@@ -272,10 +261,7 @@ int run_typed(xdemhip_binstats* P, int nb, int want_nmad, double nfact, int64_t*
                 const double m = median_from<T>(hs[k]);
                 nmads[k] = (double)(T)((T)nfact * (T)m);  // nfact * np.nanmedian(...): the Python float is a weak scalar
             }
-        if (d_med_big) (void)hipFree(d_med_big);
     }
-    sel_ws_free(ws);
-    (void)hipFree(scratch);
     return rc;
 }
 
@@ -305,7 +291,7 @@ int xdemhip_binstats_create(xdemhip_ctx* ctx, const void* values, int dtype, int
     xdemhip_binstats* P = new xdemhip_binstats;
     P->ctx = ctx; P->dtype = dtype; P->n = n;
     const size_t es = dtype == XDEMHIP_F32 ? 4 : 8;
-    int rc = upload(ctx, values, (size_t)n * es, memspace, &P->values, &P->own_values);
+    int rc = xd_upload_keep(ctx, values, (size_t)n * es, memspace, &P->values, &P->own_values);
     if (rc == XDEMHIP_OK && (hipMalloc(reinterpret_cast<void**>(&P->valid), (size_t)n) != hipSuccess ||
                              hipMalloc(reinterpret_cast<void**>(&P->bins), (size_t)n * 2) != hipSuccess ||
                              hipMalloc(&P->absdev, (size_t)n * es) != hipSuccess))
@@ -328,7 +314,7 @@ int xdemhip_binstats_add_var(xdemhip_binstats* P, const void* var, int dtype, in
     void* d = nullptr;
     bool own = false;
     const size_t es = dtype == XDEMHIP_F32 ? 4 : 8;
-    int rc = upload(ctx, var, (size_t)P->n * es, memspace, &d, &own);
+    int rc = xd_upload_keep(ctx, var, (size_t)P->n * es, memspace, &d, &own);
     if (rc != XDEMHIP_OK) return rc;
     P->var.push_back(d); P->var_dtype.push_back(dtype); P->var_own.push_back(own);
     const dim3 g(grid_for(ctx, P->n, 256, 16));
@@ -346,9 +332,10 @@ int xdemhip_binstats_finalize(xdemhip_binstats* P, int64_t* n_valid, double* var
     if (!n_valid || !var_min || !var_max) return xd_fail(ctx, XDEMHIP_EINVAL, "null output");
     XD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     const size_t nv = P->var.size();
-    uint64_t* d_out = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&d_out), 24 * (nv + 1)) != hipSuccess) return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed");
-    std::vector<uint64_t> h(3 * (nv + 1));
+    std::vector<uint64_t> h(3 * (nv + 1));   // (the copy's destination: declared first, it outlives the buffer's synchronisation)
+    XdBuffers buf(ctx, "xdemhip_binstats_finalize");
+    uint64_t* d_out = buf.alloc<uint64_t>(3 * (nv + 1));
+    if (buf.rc) return buf.rc;
     for (size_t i = 0; i <= nv; ++i) { h[3 * i] = ~(uint64_t)0; h[3 * i + 1] = 0; h[3 * i + 2] = 0; }
     hipError_t e = hipMemcpyAsync(d_out, h.data(), 24 * (nv + 1), hipMemcpyHostToDevice, ctx->stream);
     const dim3 g(grid_for(ctx, P->n, 256, 16));
@@ -364,7 +351,6 @@ int xdemhip_binstats_finalize(xdemhip_binstats* P, int64_t* n_valid, double* var
     }
     if (e == hipSuccess) e = hipMemcpyAsync(h.data(), d_out, 24 * (nv + 1), hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_out);
     if (e != hipSuccess) return xd_fail(ctx, XDEMHIP_EHIP, std::string("binstats finalize failed: ") + hipGetErrorString(e));
     *n_valid = (int64_t)h[2];
     for (size_t i = 0; i < nv; ++i) {
@@ -403,30 +389,21 @@ int xdemhip_binstats_run(xdemhip_binstats* P, int n_dims, const int* var_ids, co
     }
     for (int d = n_dims - 1, s = 1; d >= 0; --d) { D.stride[d] = s; s *= (n_edges[d] - 1); }
     if ((size_t)tot * 8 > 60 * 1024) return xd_fail(ctx, XDEMHIP_EUNSUPPORTED, "too many bin edges for the LDS table");
-    double* d_edges = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&d_edges), (size_t)tot * 8) != hipSuccess) return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed");
-    hipError_t e = hipMemcpyAsync(d_edges, edges, (size_t)tot * 8, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) {
-        if ((size_t)tot * 8 > 48 * 1024)
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(bin_ids_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, tot * 8);
-    }
+    XdBuffers buf(ctx, "xdemhip_binstats_run");
+    const double* d_edges = buf.input(edges, (size_t)tot * 8, XDEMHIP_HOST);
+    if (buf.rc) return buf.rc;
+    hipError_t e = (size_t)tot * 8 > 48 * 1024
+                       ? hipFuncSetAttribute(reinterpret_cast<const void*>(bin_ids_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, tot * 8)
+                       : hipSuccess;
     if (e == hipSuccess) {
         hipLaunchKernelGGL(bin_ids_kernel, dim3(grid_for(ctx, P->n, 256, 16)), dim3(256), (size_t)tot * 8, ctx->stream, D, d_edges, tot,
                            P->valid, P->n, P->bins);
         e = hipGetLastError();
     }
-    int rc = XDEMHIP_OK;
-    if (e != hipSuccess) rc = xd_fail(ctx, XDEMHIP_EHIP, std::string("bin id launch failed: ") + hipGetErrorString(e));
-    if (rc == XDEMHIP_OK) {
-        const xdemhip_allreduce_fn hook = ctx->allreduce;
-        ctx->allreduce = nullptr;  // single-device helper
-        rc = P->dtype == XDEMHIP_F32 ? run_typed<float>(P, (int)nb, want_nmad, nfact, counts, medians, nmads)
-                                     : run_typed<double>(P, (int)nb, want_nmad, nfact, counts, medians, nmads);
-        ctx->allreduce = hook;
-    }
-    (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_edges);
-    return rc;
+    if (e != hipSuccess) return xd_fail(ctx, XDEMHIP_EHIP, std::string("bin id launch failed: ") + hipGetErrorString(e));
+    XdLocalSelection local(ctx);  // single-device helper
+    return P->dtype == XDEMHIP_F32 ? run_typed<float>(P, (int)nb, want_nmad, nfact, counts, medians, nmads)
+                                   : run_typed<double>(P, (int)nb, want_nmad, nfact, counts, medians, nmads);
 }
 
 int xdemhip_binstats_bin_numbers(xdemhip_binstats* P, uint16_t* bins_out) {
@@ -445,44 +422,34 @@ template <typename T>
 static int nmad_typed(xdemhip_ctx* ctx, const void* values, int64_t n, double nfact, double abs_limit, int memspace, double* median,
                       double* nmad_out, int64_t* count) {
     typedef typename KeyT<T>::type K;
-    void *d_v = nullptr, *d_w = nullptr, *scratch = nullptr;
-    bool own = false;
-    auto cleanup = [&]() { if (own && d_v) (void)hipFree(d_v); if (d_w) (void)hipFree(d_w); if (scratch) (void)hipFree(scratch); };
-    int rc = upload(ctx, values, (size_t)n * sizeof(T), memspace, &d_v, &own);
-    if (rc == XDEMHIP_OK && (hipMalloc(&d_w, (size_t)n * sizeof(T)) != hipSuccess || hipMalloc(&scratch, scratch_size(1)) != hipSuccess))
-        rc = xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed");
-    if (rc != XDEMHIP_OK) { cleanup(); return rc; }
+    XdBuffers buf(ctx, "xdemhip_nmad");
+    const T* src = buf.input(static_cast<const T*>(values), (size_t)n * sizeof(T), memspace);
+    T* d_w = buf.alloc<T>((size_t)n);
+    unsigned char* base = buf.alloc<unsigned char>(scratch_size(1));
+    if (buf.rc) return buf.rc;
     const dim3 g(grid_for(ctx, n, 256, 16));
-    const T* src = static_cast<const T*>(d_v);
     if (abs_limit == abs_limit && abs_limit < INFINITY) {
-        hipLaunchKernelGGL((clip_abs_kernel<T>), g, dim3(256), 0, ctx->stream, src, n, (T)abs_limit, static_cast<T*>(d_w));
-        // the filtered copy becomes the data; the deviations need a second buffer
-        void* d_f = d_w;
-        d_w = nullptr;
-        if (hipMalloc(&d_w, (size_t)n * sizeof(T)) != hipSuccess) { d_w = d_f; cleanup(); return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed"); }
-        if (own) (void)hipFree(d_v);
-        d_v = d_f; own = true;
-        src = static_cast<const T*>(d_v);
+        hipLaunchKernelGGL((clip_abs_kernel<T>), g, dim3(256), 0, ctx->stream, src, n, (T)abs_limit, d_w);
+        // the filtered copy becomes the data; the deviations need a second buffer, and an uploaded copy of the input can go
+        T* d_f = d_w;
+        d_w = buf.alloc<T>((size_t)n);
+        if (buf.rc) return buf.rc;
+        buf.release(src);
+        src = d_f;
     }
-    unsigned char* base = static_cast<unsigned char*>(scratch);
     std::vector<SelResult<K>> r;
-    const xdemhip_allreduce_fn hook = ctx->allreduce;
-    ctx->allreduce = nullptr;
-    SelWorkspace ws;
-    if (n >= SEL_BRACKET_MIN_N) (void)sel_ws_create(ctx, n, sizeof(T), 1, ws);  // (on failure: plain selection)
-    rc = run_select<T>(ctx, src, nullptr, n, 1, base, r, &ws);
+    XdLocalSelection local(ctx);
+    SelWorkspaceLocal lws(ctx);
+    if (n >= SEL_BRACKET_MIN_N) (void)sel_ws_create(ctx, n, sizeof(T), 1, lws.ws);  // (on failure: plain selection)
+    int rc = run_select<T>(ctx, src, nullptr, n, 1, base, r, &lws.ws);
     if (rc == XDEMHIP_OK) {
         *count = (int64_t)r[0].st.count;
         const double med = median_from<T>(r[0]);
         *median = med;
-        hipLaunchKernelGGL((absdev1_kernel<T>), g, dim3(256), 0, ctx->stream, src, n, (T)med, static_cast<T*>(d_w));
-        rc = run_select<T>(ctx, static_cast<const T*>(d_w), nullptr, n, 1, base, r, &ws);
+        hipLaunchKernelGGL((absdev1_kernel<T>), g, dim3(256), 0, ctx->stream, src, n, (T)med, d_w);
+        rc = run_select<T>(ctx, d_w, nullptr, n, 1, base, r, &lws.ws);
         if (rc == XDEMHIP_OK) *nmad_out = (double)(T)((T)nfact * (T)median_from<T>(r[0]));
     }
-    ctx->allreduce = hook;
-    (void)hipStreamSynchronize(ctx->stream);
-    sel_ws_free(ws);
-    cleanup();
     return rc;
 }
 
@@ -520,46 +487,23 @@ int xdemhip_interp_grid_linear(xdemhip_ctx* ctx, int n_dims, const double* axes,
         if (ngrid > (1 << 24)) return xd_fail(ctx, XDEMHIP_EUNSUPPORTED, "interpolation grid too large");
     }
     for (int d = n_dims - 1, st = 1; d >= 0; --d) { G.stride[d] = st; st *= n_axis[d]; }
-    std::vector<void*> owned;
-    double *d_axes = nullptr, *d_grid = nullptr, *d_out = nullptr;
-    auto cleanup = [&]() {
-        for (void* p : owned) (void)hipFree(p);
-        if (d_axes) (void)hipFree(d_axes);
-        if (d_grid) (void)hipFree(d_grid);
-        if (memspace == XDEMHIP_HOST && d_out) (void)hipFree(d_out);
-    };
-    int rc = XDEMHIP_OK;
-    for (int d = 0; d < n_dims && rc == XDEMHIP_OK; ++d) {
-        void* p = nullptr;
-        bool own = false;
-        rc = upload(ctx, vars[d], (size_t)n * (var_dtypes[d] == XDEMHIP_F32 ? 4 : 8), memspace, &p, &own);
-        if (own) owned.push_back(p);
-        G.var[d] = p; G.var_f32[d] = var_dtypes[d] == XDEMHIP_F32;
+    XdBuffers buf(ctx, "xdemhip_interp_grid_linear");
+    for (int d = 0; d < n_dims; ++d) {
+        G.var[d] = buf.input(vars[d], (size_t)n * (var_dtypes[d] == XDEMHIP_F32 ? 4 : 8), memspace);
+        G.var_f32[d] = var_dtypes[d] == XDEMHIP_F32;
     }
-    if (rc == XDEMHIP_OK && (hipMalloc(reinterpret_cast<void**>(&d_axes), (size_t)tot * 8) != hipSuccess ||
-                             hipMalloc(reinterpret_cast<void**>(&d_grid), (size_t)ngrid * 8) != hipSuccess))
-        rc = xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed");
-    if (rc == XDEMHIP_OK) {
-        if (memspace == XDEMHIP_DEVICE) d_out = out;
-        else if (hipMalloc(reinterpret_cast<void**>(&d_out), (size_t)n * 8) != hipSuccess) rc = xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed");
-    }
-    if (rc != XDEMHIP_OK) { cleanup(); return rc; }
-    hipError_t e = hipMemcpyAsync(d_axes, axes, (size_t)tot * 8, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_grid, grid_values, (size_t)ngrid * 8, hipMemcpyHostToDevice, ctx->stream);
+    const double* d_axes = buf.input(axes, (size_t)tot * 8, XDEMHIP_HOST);
+    const double* d_grid = buf.input(grid_values, (size_t)ngrid * 8, XDEMHIP_HOST);
+    double* d_out = buf.output(out, (size_t)n * 8, memspace);
+    if (buf.rc) return buf.rc;
     const int in_lds = ((size_t)(tot + ngrid) * 8 <= 40 * 1024);
     const size_t lds = (size_t)(tot + (in_lds ? ngrid : 0)) * 8;
-    if (e == hipSuccess && lds > 48 * 1024) rc = xd_fail(ctx, XDEMHIP_EUNSUPPORTED, "too many grid axis points");
-    if (e == hipSuccess && rc == XDEMHIP_OK) {
-        hipLaunchKernelGGL(interp_grid_kernel, dim3(grid_for(ctx, n, 256, 16)), dim3(256), lds, ctx->stream, G, d_axes, tot, d_grid,
-                           (int)ngrid, in_lds, n, scale, d_out);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess && rc == XDEMHIP_OK && memspace == XDEMHIP_HOST)
-        e = hipMemcpyAsync(out, d_out, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess && rc == XDEMHIP_OK) rc = xd_fail(ctx, XDEMHIP_EHIP, std::string("grid interpolation failed: ") + hipGetErrorString(e));
-    cleanup();
-    return rc;
+    if (lds > 48 * 1024) return xd_fail(ctx, XDEMHIP_EUNSUPPORTED, "too many grid axis points");
+    hipLaunchKernelGGL(interp_grid_kernel, dim3(grid_for(ctx, n, 256, 16)), dim3(256), lds, ctx->stream, G, d_axes, tot, d_grid,
+                       (int)ngrid, in_lds, n, scale, d_out);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return xd_fail(ctx, XDEMHIP_EHIP, std::string("grid interpolation failed: ") + hipGetErrorString(e));
+    return buf.finish();
 }
 
 }  // extern "C"

@@ -82,27 +82,108 @@ inline int launched(xdemhip_ctx* ctx, const char* what) {
     return hipGetLastError() == hipSuccess ? XDEMHIP_OK : xd_fail(ctx, XDEMHIP_EHIP, std::string(what) + " launch failed");
 }
 
-// A device buffer for the length of a scope.  `rc` is XDEMHIP_ENOMEM with "hipMalloc failed (`who`)" where there is none; at the end
-// of the scope the stream is synchronised (the queued work may still use the buffer) and the buffer freed.  Host destinations of
-// copies queued on the stream are declared BEFORE it, so that they outlive that synchronisation on every return path.
-struct XdScratch {
+inline int xd_sync(xdemhip_ctx* ctx);
+
+// The device buffers of one call.  alloc() gives a buffer for the length of the scope.  input() and output() give the device side of a
+// caller's array (sizes in bytes, the pointer's type kept): the array itself where it is on the device (XDEMHIP_DEVICE), else a
+// buffer of the scope, the upload queued on the context's stream at once and the download by finish().  A null array stays null.  A
+// failure returns nullptr and sets `rc`: XDEMHIP_ENOMEM with "hipMalloc failed (`who`)" and HIP's last error cleared, XDEMHIP_EHIP
+// for a copy; after a failure every further request returns nullptr, so a call site asks for all it needs and looks at `rc` once.
+// finish() ends a call that went well: the downloads are queued and, if the scope owns anything, the stream is waited for (xd_sync,
+// its status returned) and the buffers freed.  On every other path the end of the scope does the same without a status.  A scope
+// that owns nothing does nothing, which keeps device routes asynchronous.  Host destinations of copies queued on the stream, other
+// than the caller's own arrays, are declared BEFORE it, so that they outlive that synchronisation on every return path.
+struct XdBuffers {
     xdemhip_ctx* ctx;
-    void* p = nullptr;
+    const char* who;
     int rc = XDEMHIP_OK;
-    XdScratch(xdemhip_ctx* c, size_t bytes, const char* who) : ctx(c) {
+    struct Out { void* host; const void* dev; size_t bytes; };
+    std::vector<void*> owned;
+    std::vector<Out> outs;
+    XdBuffers(xdemhip_ctx* c, const char* w) : ctx(c), who(w) {}
+    void* alloc(size_t bytes) {
+        void* p = nullptr;
+        if (rc != XDEMHIP_OK) return nullptr;
         if (hipMalloc(&p, bytes) != hipSuccess) {
             (void)hipGetLastError();
-            p = nullptr;
             rc = xd_fail(ctx, XDEMHIP_ENOMEM, std::string("hipMalloc failed (") + who + ")");
+            return nullptr;
         }
+        if (p) owned.push_back(p);
+        return p;
     }
-    ~XdScratch() {
-        if (!p) return;
+    template <typename T> T* alloc(size_t count) { return static_cast<T*>(alloc(count * sizeof(T))); }
+    template <typename T> const T* input(const T* src, size_t bytes, int memspace) {
+        if (memspace == XDEMHIP_DEVICE || !src) return src;
+        T* d = static_cast<T*>(alloc(bytes));
+        if (d && hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
+            rc = xd_fail(ctx, XDEMHIP_EHIP, std::string("H2D copy failed (") + who + ")");
+            return nullptr;
+        }
+        return d;
+    }
+    template <typename T> T* output(T* dst, size_t bytes, int memspace) {
+        if (memspace == XDEMHIP_DEVICE || !dst) return dst;
+        T* d = static_cast<T*>(alloc(bytes));
+        if (d) outs.push_back({dst, d, bytes});
+        return d;
+    }
+    int finish() {
+        for (const Out& o : outs)
+            if (rc == XDEMHIP_OK && hipMemcpyAsync(o.host, o.dev, o.bytes, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+                rc = xd_fail(ctx, XDEMHIP_EHIP, std::string("D2H copy failed (") + who + ")");
+        if (owned.empty()) return rc;
+        const int synced = xd_sync(ctx);
+        if (rc == XDEMHIP_OK) rc = synced;
+        free_all();
+        return rc;
+    }
+    // free one buffer of the scope now (the queued work that uses it is waited for); a pointer the scope does not own is left alone
+    void release(const void* p) {
+        for (size_t i = 0; i < owned.size(); ++i)
+            if (owned[i] == p) {
+                (void)hipStreamSynchronize(ctx->stream);
+                (void)hipFree(owned[i]);
+                owned.erase(owned.begin() + (ptrdiff_t)i);
+                return;
+            }
+    }
+    ~XdBuffers() {
+        if (owned.empty()) return;
         (void)hipStreamSynchronize(ctx->stream);
-        (void)hipFree(p);
+        free_all();
     }
-    XdScratch(const XdScratch&) = delete;
-    XdScratch& operator=(const XdScratch&) = delete;
+    void free_all() {
+        for (void* p : owned) (void)hipFree(p);
+        owned.clear();
+    }
+    XdBuffers(const XdBuffers&) = delete;
+    XdBuffers& operator=(const XdBuffers&) = delete;
+};
+
+// For plan constructors, which keep what they upload: the caller's device array itself (*own false), or a device copy of its host
+// array with the upload queued on the stream (*own true).  On failure nothing is left allocated and HIP's last error is cleared.
+inline int xd_upload_keep(xdemhip_ctx* ctx, const void* src, size_t bytes, int memspace, void** dptr, bool* own) {
+    *own = false;
+    if (memspace == XDEMHIP_DEVICE) { *dptr = const_cast<void*>(src); return XDEMHIP_OK; }
+    if (hipMalloc(dptr, bytes) != hipSuccess) { (void)hipGetLastError(); *dptr = nullptr; return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed"); }
+    if (hipMemcpyAsync(*dptr, src, bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
+        (void)hipFree(*dptr);
+        *dptr = nullptr;
+        return xd_fail(ctx, XDEMHIP_EHIP, "H2D copy failed");
+    }
+    *own = true;
+    return XDEMHIP_OK;
+}
+
+// "This selection is local": the reduction hook is off for the length of the scope (one process's values, a single-device helper).
+struct XdLocalSelection {
+    xdemhip_ctx* ctx;
+    xdemhip_allreduce_fn hook;
+    explicit XdLocalSelection(xdemhip_ctx* c) : ctx(c), hook(c->allreduce) { ctx->allreduce = nullptr; }
+    ~XdLocalSelection() { ctx->allreduce = hook; }
+    XdLocalSelection(const XdLocalSelection&) = delete;
+    XdLocalSelection& operator=(const XdLocalSelection&) = delete;
 };
 
 // Queue a small device-to-host copy whose destination is filled by the next xd_sync(ctx) (falls back to a plain copy when

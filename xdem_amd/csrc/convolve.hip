@@ -205,46 +205,16 @@ extern "C" int xdemhip_convolution(xdemhip_ctx* ctx, const void* imgs, int dtype
     }
     XD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     const size_t es = dtype == XDEMHIP_F32 ? 4 : 8, n = (size_t)H * (size_t)W;
-    const size_t ntap = yx.size() ? yx.size() : 1;
-    int2* d_yx = nullptr;
-    double *d_w = nullptr, *d_dense = nullptr;
-    unsigned long long* d_mask = nullptr;
-    int* d_start = nullptr;
-    void* d_img = nullptr;
-    double* d_out = nullptr;
-    auto release = [&]() {
-        if (d_yx) (void)hipFree(d_yx);
-        if (d_w) (void)hipFree(d_w);
-        if (d_start) (void)hipFree(d_start);
-        if (d_dense) (void)hipFree(d_dense);
-        if (d_mask) (void)hipFree(d_mask);
-        if (memspace == XDEMHIP_HOST) {
-            if (d_img) (void)hipFree(d_img);
-            if (d_out) (void)hipFree(d_out);
-        }
-    };
-    if (hipMalloc(reinterpret_cast<void**>(&d_yx), ntap * sizeof(int2)) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&d_w), ntap * sizeof(double)) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&d_start), start.size() * sizeof(int)) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&d_dense), dense.size() * sizeof(double)) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&d_mask), mask.size() * sizeof(unsigned long long)) != hipSuccess) {
-        release();
-        return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed");
-    }
-    if ((yx.size() && (hipMemcpy(d_yx, yx.data(), yx.size() * sizeof(int2), hipMemcpyHostToDevice) != hipSuccess ||
-                       hipMemcpy(d_w, wt.data(), wt.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)) ||
-        hipMemcpy(d_start, start.data(), start.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(d_dense, dense.data(), dense.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(d_mask, mask.data(), mask.size() * sizeof(unsigned long long), hipMemcpyHostToDevice) != hipSuccess) {
-        release();
-        return xd_fail(ctx, XDEMHIP_EHIP, "upload of the filter taps failed");
-    }
-    if (memspace == XDEMHIP_HOST) {   // one image and its n_f planes on the device at a time
-        if (hipMalloc(&d_img, n * es) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&d_out), n * 8 * (size_t)n_f) != hipSuccess) {
-            release();
-            return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed");
-        }
-    }
+    XdBuffers buf(ctx, "xdemhip_convolution");
+    const int2* d_yx = buf.input(yx.data(), yx.size() * sizeof(int2), XDEMHIP_HOST);
+    const double* d_w = buf.input(wt.data(), wt.size() * sizeof(double), XDEMHIP_HOST);
+    const int* d_start = buf.input(start.data(), start.size() * sizeof(int), XDEMHIP_HOST);
+    const double* d_dense = buf.input(dense.data(), dense.size() * sizeof(double), XDEMHIP_HOST);
+    const unsigned long long* d_mask = buf.input(mask.data(), mask.size() * sizeof(unsigned long long), XDEMHIP_HOST);
+    // host route: one image and its n_f planes on the device at a time
+    void* d_img = memspace == XDEMHIP_HOST ? buf.alloc(n * es) : nullptr;
+    double* d_out = memspace == XDEMHIP_HOST ? buf.alloc<double>(n * (size_t)n_f) : nullptr;
+    if (buf.rc) return buf.rc;
     CvArgs a;
     a.H = H; a.W = W; a.n_f = n_f;
     a.dy_min = dy_min; a.dx_min = dx_min; a.M1 = M1; a.M2 = M2; a.round_to_t = method == 0 ? 1 : 0;
@@ -287,8 +257,6 @@ extern "C" int xdemhip_convolution(xdemhip_ctx* ctx, const void* imgs, int dtype
     }
     (void)hipEventRecord(ctx->ev_stop, ctx->stream);
     ctx->timed = true;
-    // the tap lists are read by launches that may still run: wait for them before the lists go (hipFree would wait as well)
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == XDEMHIP_OK) rc = xd_fail(ctx, XDEMHIP_EHIP, "convolution kernel failed");
-    release();
-    return rc;
+    // the tap lists are read by launches that may still run: finish() waits for them before the lists go
+    return rc == XDEMHIP_OK ? buf.finish() : rc;
 }

@@ -110,45 +110,22 @@ extern "C" int xdemhip_cov_double_sum(xdemhip_ctx* ctx, const double* ax, const 
     M.inv_sill = 1.0 / sill;
     XD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     if (self) { bx = ax; by = ay; be = ae; nb = na; }
-    std::vector<void*> owned;
-    auto cleanup = [&]() { for (void* p : owned) (void)hipFree(p); };
-    auto up = [&](const double* src, int64_t n, const double** dst) -> int {
-        if (memspace == XDEMHIP_DEVICE) { *dst = src; return XDEMHIP_OK; }
-        void* d = nullptr;
-        if (hipMalloc(&d, (size_t)n * 8) != hipSuccess) return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed");
-        owned.push_back(d);
-        if (hipMemcpyAsync(d, src, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return xd_fail(ctx, XDEMHIP_EHIP, "H2D copy failed");
-        *dst = static_cast<const double*>(d);
-        return XDEMHIP_OK;
-    };
-    const double *dax, *day, *dae, *dbx, *dby, *dbe;
-    int rc = up(ax, na, &dax);
-    if (rc == XDEMHIP_OK) rc = up(ay, na, &day);
-    if (rc == XDEMHIP_OK) rc = up(ae, na, &dae);
-    if (self) { dbx = dax; dby = day; dbe = dae; }
-    else {
-        if (rc == XDEMHIP_OK) rc = up(bx, nb, &dbx);
-        if (rc == XDEMHIP_OK) rc = up(by, nb, &dby);
-        if (rc == XDEMHIP_OK) rc = up(be, nb, &dbe);
-    }
-    double* d_out = nullptr;
-    if (rc == XDEMHIP_OK && hipMalloc(reinterpret_cast<void**>(&d_out), 8) != hipSuccess) rc = xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed");
-    if (rc != XDEMHIP_OK) { cleanup(); return rc; }
-    owned.push_back(d_out);
+    XdBuffers buf(ctx, "xdemhip_cov_double_sum");
+    auto in = [&](const double* src, int64_t n) { return buf.input(src, (size_t)n * 8, memspace); };
+    const double *dax = in(ax, na), *day = in(ay, na), *dae = in(ae, na);
+    const double *dbx = self ? dax : in(bx, nb), *dby = self ? day : in(by, nb), *dbe = self ? dae : in(be, nb);
+    double* d_out = buf.alloc<double>(1);
+    if (buf.rc) return buf.rc;
     (void)hipMemsetAsync(d_out, 0, 8, ctx->stream);
     const int64_t n_wg = ((na + CV_NT - 1) / CV_NT) * ((nb + CV_CHUNK - 1) / CV_CHUNK);
-    if (n_wg * CV_NT >= ((int64_t)1 << 32)) {  // (total work-items of a HIP dispatch are a 32-bit quantity)
-        cleanup();
+    if (n_wg * CV_NT >= ((int64_t)1 << 32))  // (total work-items of a HIP dispatch are a 32-bit quantity)
         return xd_fail(ctx, XDEMHIP_EUNSUPPORTED, "too many point tiles for one launch");
-    }
     (void)hipEventRecord(ctx->ev_start, ctx->stream);
     hipLaunchKernelGGL(cov_sum_kernel, dim3((unsigned)n_wg), dim3(CV_NT), 0, ctx->stream, dax, day, dae, na, dbx, dby, dbe, nb, M, d_out);
     hipError_t e = hipGetLastError();
     (void)hipEventRecord(ctx->ev_stop, ctx->stream);
     ctx->timed = e == hipSuccess;
     if (e == hipSuccess) e = hipMemcpyAsync(out_sum, d_out, 8, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    cleanup();
     if (e != hipSuccess) return xd_fail(ctx, XDEMHIP_EHIP, std::string("covariance sum failed: ") + hipGetErrorString(e));
-    return XDEMHIP_OK;
+    return buf.finish();
 }

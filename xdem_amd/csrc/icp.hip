@@ -345,10 +345,8 @@ template <typename P> int icp_alloc(xdemhip_icp* I, P** p, size_t bytes, const c
 // exact np.median of d[0..n) (one local selection; a reduction hook on the context is suspended)
 int icp_median(xdemhip_ctx* ctx, const double* d, int64_t n, unsigned char* scratch, SelWorkspace* ws, double* out) {
     std::vector<SelResult<uint64_t>> r;
-    const xdemhip_allreduce_fn hook = ctx->allreduce;
-    ctx->allreduce = nullptr;
+    XdLocalSelection local(ctx);
     const int rc = run_select<double>(ctx, d, nullptr, n, 1, scratch, r, ws);
-    ctx->allreduce = hook;
     if (rc) return rc;
     *out = median_from<double>(r[0]);
     return XDEMHIP_OK;
@@ -535,27 +533,28 @@ int xdemhip_icp_create_plan(xdemhip_dh_plan* P, const double* transform6, int wi
     double* tmp = nullptr;
     { const int rc_ = icp_alloc(I, &scratch, scratch_size(1), "ICP selection"); if (rc_) return fail(rc_); }
     { const int rc_ = icp_alloc(I, &tmp, (size_t)n * 8, "ICP selection"); if (rc_) return fail(rc_); }
-    SelWorkspace ws;
-    if (n >= SEL_BRACKET_MIN_N) (void)sel_ws_create(ctx, n, 8, 1, ws);
     double* axis[3] = {I->rx, I->ry, I->rz};
     double nmads[3] = {0.0, 0.0, 0.0};
     int rc = XDEMHIP_OK;
-    for (int a = 0; a < 3 && rc == XDEMHIP_OK; ++a) {
-        double med = 0.0, med2 = 0.0, mad = 0.0;
-        rc = icp_median(ctx, axis[a], n, scratch, &ws, &med);
-        if (rc) break;
-        centroid3[a] = med;
-        hipLaunchKernelGGL(icp_sub_kernel, grid, dim3(256), 0, ctx->stream, axis[a], n, med);
-        if (a == 2) hipLaunchKernelGGL(icp_sub_kernel, grid, dim3(256), 0, ctx->stream, I->qz, n, med);
-        if (!standardize) continue;
-        rc = icp_median(ctx, axis[a], n, scratch, &ws, &med2);
-        if (rc) break;
-        hipLaunchKernelGGL(icp_absdev_kernel, grid, dim3(256), 0, ctx->stream, axis[a], n, med2, tmp);
-        rc = icp_median(ctx, tmp, n, scratch, &ws, &mad);
-        nmads[a] = 1.4826 * mad;
+    {   // (the workspace goes when the medians are done)
+        SelWorkspaceLocal lws(ctx);
+        SelWorkspace& ws = lws.ws;
+        if (n >= SEL_BRACKET_MIN_N) (void)sel_ws_create(ctx, n, 8, 1, ws);
+        for (int a = 0; a < 3 && rc == XDEMHIP_OK; ++a) {
+            double med = 0.0, med2 = 0.0, mad = 0.0;
+            rc = icp_median(ctx, axis[a], n, scratch, &ws, &med);
+            if (rc) break;
+            centroid3[a] = med;
+            hipLaunchKernelGGL(icp_sub_kernel, grid, dim3(256), 0, ctx->stream, axis[a], n, med);
+            if (a == 2) hipLaunchKernelGGL(icp_sub_kernel, grid, dim3(256), 0, ctx->stream, I->qz, n, med);
+            if (!standardize) continue;
+            rc = icp_median(ctx, axis[a], n, scratch, &ws, &med2);
+            if (rc) break;
+            hipLaunchKernelGGL(icp_absdev_kernel, grid, dim3(256), 0, ctx->stream, axis[a], n, med2, tmp);
+            rc = icp_median(ctx, tmp, n, scratch, &ws, &mad);
+            nmads[a] = 1.4826 * mad;
+        }
     }
-    (void)hipStreamSynchronize(ctx->stream);
-    sel_ws_free(ws);
     if (rc) return fail(rc);
     double f = 1.0;
     if (standardize) {
@@ -701,9 +700,9 @@ int xdemhip_icp_pairs(xdemhip_icp* I, int picky, int64_t* n_kept, int64_t* query
     *n_kept = I->k;
     if ((query_idx_out || ref_idx_out) && I->k > 0) {
         if (!query_idx_out || !ref_idx_out) return xd_fail(ctx, XDEMHIP_EINVAL, "xdemhip_icp_pairs: both index outputs or none");
-        XdScratch buf(ctx, (size_t)I->k * 16, "xdemhip_icp_pairs");
+        XdBuffers buf(ctx, "xdemhip_icp_pairs");
+        int64_t* d = buf.alloc<int64_t>((size_t)I->k * 2);
         if (buf.rc) return buf.rc;
-        int64_t* d = static_cast<int64_t*>(buf.p);
         hipLaunchKernelGGL(icp_values_kernel, dim3(grid_for(ctx, I->k, 256, 16)), dim3(256), 0, ctx->stream, pair_src(I), I->k, I->tx, I->ty, I->tz, I->rx, I->ry,
                            I->rz, I->nx, I->ny, I->nz, (double*)nullptr, d, d + I->k);
         int rc = launched(ctx, "icp_values_kernel");
@@ -749,9 +748,9 @@ int xdemhip_icp_values(xdemhip_icp* I, double* out9k) {
     if (I->k < 0) return xd_fail(ctx, XDEMHIP_EINVAL, "xdemhip_icp_values: call xdemhip_icp_pairs first");
     if (I->k == 0) return xd_fail(ctx, XDEMHIP_EINVAL, "no valid points");
     XD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    XdScratch buf(ctx, (size_t)I->k * 72, "xdemhip_icp_values");
+    XdBuffers buf(ctx, "xdemhip_icp_values");
+    double* d = buf.alloc<double>((size_t)I->k * 9);
     if (buf.rc) return buf.rc;
-    double* d = static_cast<double*>(buf.p);
     hipLaunchKernelGGL(icp_values_kernel, dim3(grid_for(ctx, I->k, 256, 16)), dim3(256), 0, ctx->stream, pair_src(I), I->k, I->tx, I->ty, I->tz, I->rx, I->ry, I->rz,
                        I->nx, I->ny, I->nz, d, (int64_t*)nullptr, (int64_t*)nullptr);
     int rc = launched(ctx, "icp_values_kernel");

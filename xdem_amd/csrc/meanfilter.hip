@@ -123,18 +123,11 @@ extern "C" int xdemhip_mean_filter_nan(xdemhip_ctx* ctx, const void* img, int dt
     }
     XD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     const size_t es = dtype == XDEMHIP_F32 ? 4 : 8, n = (size_t)H * (size_t)W;
-    void* d_img = const_cast<void*>(img);
-    double *d_mean = mean_out, *d_nv = nvalid_out;
-    if (memspace == XDEMHIP_HOST) {
-        d_img = nullptr; d_mean = d_nv = nullptr;
-        if (hipMalloc(&d_img, n * es) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&d_mean), n * 8) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void**>(&d_nv), n * 8) != hipSuccess) {
-            if (d_img) (void)hipFree(d_img);
-            if (d_mean) (void)hipFree(d_mean);
-            return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed");
-        }
-        (void)hipMemcpyAsync(d_img, img, n * es, hipMemcpyHostToDevice, ctx->stream);
-    }
+    XdBuffers buf(ctx, "xdemhip_mean_filter_nan");
+    const void* d_img = buf.input(img, n * es, memspace);
+    double* d_mean = buf.output(mean_out, n * 8, memspace);
+    double* d_nv = buf.output(nvalid_out, n * 8, memspace);
+    if (buf.rc) return buf.rc;
     const dim3 grid((unsigned)((W + MF_TX - 1) / MF_TX), (unsigned)((H + MF_TY - 1) / MF_TY));
     XD_HIP_CHECK(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
     if (dtype == XDEMHIP_F32)
@@ -143,16 +136,6 @@ extern "C" int xdemhip_mean_filter_nan(xdemhip_ctx* ctx, const void* img, int dt
         hipLaunchKernelGGL((mean_filter_kernel<double>), grid, dim3(256), 0, ctx->stream, static_cast<const double*>(d_img), H, W, taps, d_mean, d_nv);
     (void)hipEventRecord(ctx->ev_stop, ctx->stream);
     ctx->timed = true;
-    int rc = XDEMHIP_OK;
-    if (hipGetLastError() != hipSuccess) rc = xd_fail(ctx, XDEMHIP_EHIP, "mean filter kernel launch failed");
-    if (memspace == XDEMHIP_HOST) {
-        if (rc == XDEMHIP_OK && (hipMemcpyAsync(mean_out, d_mean, n * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-                                 hipMemcpyAsync(nvalid_out, d_nv, n * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-                                 hipStreamSynchronize(ctx->stream) != hipSuccess))
-            rc = xd_fail(ctx, XDEMHIP_EHIP, "mean filter kernel / D2H failed");
-        (void)hipFree(d_img);
-        (void)hipFree(d_mean);
-        (void)hipFree(d_nv);
-    }
-    return rc;
+    if (hipGetLastError() != hipSuccess) return xd_fail(ctx, XDEMHIP_EHIP, "mean filter kernel launch failed");
+    return buf.finish();
 }

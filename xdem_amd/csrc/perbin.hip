@@ -200,59 +200,21 @@ extern "C" int xdemhip_perbin_lookup(xdemhip_ctx* ctx, const void* const* vars, 
     if (n_missing) *n_missing = 0;
     if (n == 0) return XDEMHIP_OK;
     XD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    unsigned long long miss = 0;   // (the counter's destination: declared first, it outlives the buffers' synchronisation)
+    XdBuffers buf(ctx, "xdemhip_perbin_lookup");
     // small tables: edges, statistics, pass bytes, the counter
-    double *d_left = nullptr, *d_right = nullptr, *d_table = nullptr, *d_out = nullptr;
-    unsigned char* d_pass = nullptr;
-    unsigned long long* d_miss = nullptr;
-    void* d_var[PB_MAXVAR] = {};
-    auto release = [&]() {
-        if (d_left) (void)hipFree(d_left);
-        if (d_right) (void)hipFree(d_right);
-        if (d_table) (void)hipFree(d_table);
-        if (d_pass) (void)hipFree(d_pass);
-        if (d_miss) (void)hipFree(d_miss);
-        if (memspace == XDEMHIP_HOST) {
-            for (int k = 0; k < n_var; ++k)
-                if (d_var[k]) (void)hipFree(d_var[k]);
-            if (d_out) (void)hipFree(d_out);
-        }
-    };
-    bool ok = hipMalloc(reinterpret_cast<void**>(&d_left), n_edges * 8) == hipSuccess &&
-              hipMalloc(reinterpret_cast<void**>(&d_right), n_edges * 8) == hipSuccess &&
-              hipMalloc(reinterpret_cast<void**>(&d_table), n_bins * 8) == hipSuccess &&
-              hipMalloc(reinterpret_cast<void**>(&d_pass), n_bins) == hipSuccess &&
-              hipMalloc(reinterpret_cast<void**>(&d_miss), 8) == hipSuccess;
-    if (ok && memspace == XDEMHIP_HOST) {
-        for (int k = 0; k < n_var && ok; ++k) ok = hipMalloc(&d_var[k], (size_t)n * (var_dtypes[k] == XDEMHIP_F32 ? 4 : 8)) == hipSuccess;
-        ok = ok && hipMalloc(reinterpret_cast<void**>(&d_out), (size_t)n * 8) == hipSuccess;
-    }
-    if (!ok) {
-        release();
-        return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed");
-    }
-    ok = hipMemcpy(d_left, left, n_edges * 8, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(d_right, right, n_edges * 8, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(d_table, table, n_bins * 8, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(d_pass, pass, n_bins, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemsetAsync(d_miss, 0, 8, ctx->stream) == hipSuccess;
-    for (int k = 0; k < n_var && ok; ++k) {
-        if (memspace == XDEMHIP_HOST) {
-            ok = hipMemcpyAsync(d_var[k], vars[k], (size_t)n * (var_dtypes[k] == XDEMHIP_F32 ? 4 : 8), hipMemcpyHostToDevice, ctx->stream) == hipSuccess;
-            a.var[k] = d_var[k];
-        } else {
-            a.var[k] = vars[k];
-        }
-    }
-    if (!ok) {
-        release();
-        return xd_fail(ctx, XDEMHIP_EHIP, "upload failed");
-    }
+    a.left = buf.input(left, n_edges * 8, XDEMHIP_HOST);
+    a.right = buf.input(right, n_edges * 8, XDEMHIP_HOST);
+    a.table = buf.input(table, n_bins * 8, XDEMHIP_HOST);
+    a.pass = buf.input(pass, n_bins, XDEMHIP_HOST);
+    a.missing = buf.alloc<unsigned long long>(1);
+    for (int k = 0; k < n_var; ++k) a.var[k] = buf.input(vars[k], (size_t)n * (var_dtypes[k] == XDEMHIP_F32 ? 4 : 8), memspace);
+    a.out = buf.output(out, (size_t)n * 8, memspace);
+    if (buf.rc) return buf.rc;
+    if (hipMemsetAsync(a.missing, 0, 8, ctx->stream) != hipSuccess) return xd_fail(ctx, XDEMHIP_EHIP, "upload failed");
     a.n_var = n_var; a.n = n; a.n_bins = n_bins;
-    a.vec = ((uintptr_t)(memspace == XDEMHIP_HOST ? (void*)d_out : (void*)out) & 15) == 0;
+    a.vec = ((uintptr_t)a.out & 15) == 0;
     for (int k = 0; k < n_var; ++k) a.vec = a.vec && ((uintptr_t)a.var[k] & 15) == 0;
-    a.left = d_left; a.right = d_right; a.table = d_table; a.pass = d_pass;
-    a.out = memspace == XDEMHIP_HOST ? d_out : out;
-    a.missing = d_miss;
     const int64_t want = (n + 256 * PB_U - 1) / (256 * PB_U);
     const unsigned blocks = (unsigned)(want < (int64_t)ctx->num_cu * 16 ? want : (int64_t)ctx->num_cu * 16);
     (void)hipEventRecord(ctx->ev_start, ctx->stream);
@@ -275,13 +237,9 @@ extern "C" int xdemhip_perbin_lookup(xdemhip_ctx* ctx, const void* const* vars, 
     ctx->timed = true;
     int rc = XDEMHIP_OK;
     if (hipGetLastError() != hipSuccess) rc = xd_fail(ctx, XDEMHIP_EHIP, "per-bin lookup kernel launch failed");
-    unsigned long long miss = 0;
-    if (rc == XDEMHIP_OK && memspace == XDEMHIP_HOST && hipMemcpyAsync(out, d_out, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
-        rc = xd_fail(ctx, XDEMHIP_EHIP, "D2H failed");
-    if (rc == XDEMHIP_OK && (hipMemcpyAsync(&miss, d_miss, 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-                             hipStreamSynchronize(ctx->stream) != hipSuccess))
+    if (rc == XDEMHIP_OK && hipMemcpyAsync(&miss, a.missing, 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
         rc = xd_fail(ctx, XDEMHIP_EHIP, "per-bin lookup kernel failed");
+    if (rc == XDEMHIP_OK) rc = buf.finish();
     if (n_missing) *n_missing = (int64_t)miss;
-    release();
     return rc;
 }

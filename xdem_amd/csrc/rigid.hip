@@ -301,12 +301,12 @@ int xdemhip_dh_lzd_centroid(xdemhip_dh_plan* P, const double* transform6, double
     if (count) *count = k;
     if (k == 0) return xd_fail(ctx, XDEMHIP_EINVAL, "no valid points");
     const int nblocks = grid_for(ctx, k, 256, 4);
-    unsigned long long hi[2] = {0, 0};   // (the fetches' destinations: declared first, they outlive the scratch buffer's synchronisation)
+    unsigned long long hi[2] = {0, 0};   // (the fetches' destinations: declared first, they outlive the buffer's synchronisation)
     double hz = 0.0;
-    XdScratch buf(ctx, (size_t)(nblocks + 1) * 24, "xdemhip_dh_lzd_centroid");
-    if (buf.rc) return buf.rc;
+    XdBuffers buf(ctx, "xdemhip_dh_lzd_centroid");
     // layout: integer partials (2 per workgroup) and totals (2), then the float64 partials and total
-    unsigned long long* d_ip = static_cast<unsigned long long*>(buf.p);
+    unsigned long long* d_ip = buf.alloc<unsigned long long>((size_t)(nblocks + 1) * 3);
+    if (buf.rc) return buf.rc;
     unsigned long long* d_iout = d_ip + 2 * (size_t)nblocks;
     double* d_dp = reinterpret_cast<double*>(d_iout + 2);
     double* d_dout = d_dp + nblocks;
@@ -365,11 +365,11 @@ int xdemhip_dh_lzd_values(xdemhip_dh_plan* P, const double* transform6, const do
     const int64_t n = P->n_idx;
     if (n == 0) return xd_fail(ctx, XDEMHIP_EINVAL, "no valid points");
     { const int rc_ = ensure_gradients(P, transform6); if (rc_) return rc_; }
-    std::vector<double> h;          // (the copies' destinations: declared first, so that they outlive the scratch buffer's synchronisation)
+    std::vector<double> h;          // (the copies' destinations: declared first, so that they outlive the buffer's synchronisation)
     std::vector<uint8_t> keep;
-    XdScratch buf(ctx, (size_t)n * 49, "xdemhip_dh_lzd_values");   // six float64 rows, then the keep bytes
+    XdBuffers buf(ctx, "xdemhip_dh_lzd_values");
+    double* d_out = static_cast<double*>(buf.alloc((size_t)n * 49));   // six float64 rows, then the keep bytes
     if (buf.rc) return buf.rc;
-    double* d_out = static_cast<double*>(buf.p);
     uint8_t* d_keep = reinterpret_cast<uint8_t*>(d_out + 6 * n);
     const NkGeom g = lzd_geom(P);
     const Rigid R = make_rigid(transform6, matrix16, centroid3);
@@ -408,43 +408,24 @@ int xdemhip_apply_matrix_rst(xdemhip_ctx* ctx, const void* dem, int dtype, int64
     XD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     const int64_t n = H * W;
     const size_t bytes = (size_t)n * (dtype == XDEMHIP_F32 ? 4 : 8);
-    void *d_in = const_cast<void*>(dem), *d_out = out;
-    const bool own = memspace == XDEMHIP_HOST;
-    int rc = XDEMHIP_OK;
-    if (own) {
-        d_in = d_out = nullptr;
-        if (hipMalloc(&d_in, bytes) != hipSuccess || hipMalloc(&d_out, bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            rc = xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed (xdemhip_apply_matrix_rst)");
-        } else if (hipMemcpyAsync(d_in, dem, bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
-            rc = xd_fail(ctx, XDEMHIP_EHIP, "H2D copy failed");
-        }
-    }
-    if (rc == XDEMHIP_OK) {
-        const Rigid R = make_rigid(transform6, matrix16, centroid3_or_null);
-        const double tol_x = 1e-4 * fabs(transform6[0]), tol_y = 1e-4 * fabs(transform6[4]);
-        const dim3 grid(grid_for(ctx, n, 256, 16));
-        (void)hipEventRecord(ctx->ev_start, ctx->stream);
-        if (dtype == XDEMHIP_F32)
-            hipLaunchKernelGGL((apply_matrix_kernel<float>), grid, dim3(256), 0, ctx->stream, static_cast<const float*>(d_in), H, W, R, tol_x, tol_y,
-                               static_cast<float*>(d_out));
-        else
-            hipLaunchKernelGGL((apply_matrix_kernel<double>), grid, dim3(256), 0, ctx->stream, static_cast<const double*>(d_in), H, W, R, tol_x, tol_y,
-                               static_cast<double*>(d_out));
-        rc = launched(ctx, "apply_matrix_kernel");
-        (void)hipEventRecord(ctx->ev_stop, ctx->stream);
-        ctx->timed = (rc == XDEMHIP_OK);
-    }
-    if (rc == XDEMHIP_OK && own) {
-        if (hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = xd_fail(ctx, XDEMHIP_EHIP, "D2H copy failed");
-        if (rc == XDEMHIP_OK) rc = xd_sync(ctx);
-    }
-    if (own) {
-        (void)hipStreamSynchronize(ctx->stream);
-        if (d_in) (void)hipFree(d_in);
-        if (d_out) (void)hipFree(d_out);
-    }
-    return rc;
+    XdBuffers buf(ctx, "xdemhip_apply_matrix_rst");
+    const void* d_in = buf.input(dem, bytes, memspace);
+    void* d_out = buf.output(out, bytes, memspace);
+    if (buf.rc) return buf.rc;
+    const Rigid R = make_rigid(transform6, matrix16, centroid3_or_null);
+    const double tol_x = 1e-4 * fabs(transform6[0]), tol_y = 1e-4 * fabs(transform6[4]);
+    const dim3 grid(grid_for(ctx, n, 256, 16));
+    (void)hipEventRecord(ctx->ev_start, ctx->stream);
+    if (dtype == XDEMHIP_F32)
+        hipLaunchKernelGGL((apply_matrix_kernel<float>), grid, dim3(256), 0, ctx->stream, static_cast<const float*>(d_in), H, W, R, tol_x, tol_y,
+                           static_cast<float*>(d_out));
+    else
+        hipLaunchKernelGGL((apply_matrix_kernel<double>), grid, dim3(256), 0, ctx->stream, static_cast<const double*>(d_in), H, W, R, tol_x, tol_y,
+                           static_cast<double*>(d_out));
+    int rc = launched(ctx, "apply_matrix_kernel");
+    (void)hipEventRecord(ctx->ev_stop, ctx->stream);
+    ctx->timed = (rc == XDEMHIP_OK);
+    return rc == XDEMHIP_OK ? buf.finish() : rc;
 }
 
 }  // extern "C"

@@ -502,11 +502,26 @@ inline int sel_ws_create(xdemhip_ctx* ctx, int64_t n, size_t es, int nb_max, Sel
     if (hipMalloc(&w.s_vals, (size_t)w.s_cap * es) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&w.s_bins), (size_t)w.s_cap * 2) != hipSuccess ||
         hipMalloc(&w.c_vals, (size_t)w.c_cap * es) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&w.c_bins), (size_t)w.c_cap * 2) != hipSuccess ||
         hipMalloc(reinterpret_cast<void**>(&w.d_small), (size_t)(8 + 6 * nb_max) * 8) != hipSuccess) {
+        (void)hipGetLastError();   // (callers may go on with the plain selection: no stale error for their launch checks)
         sel_ws_free(w);
         return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc(selection workspace) failed");
     }
     return XDEMHIP_OK;
 }
+// A workspace for the length of one call: on every return path the queued work that uses it is waited for and it is freed.  (Plans
+// keep a plain SelWorkspace and free it in their destroy.)
+struct SelWorkspaceLocal {
+    xdemhip_ctx* ctx;
+    SelWorkspace ws;
+    explicit SelWorkspaceLocal(xdemhip_ctx* c) : ctx(c) {}
+    ~SelWorkspaceLocal() {
+        if (!ws.d_small) return;
+        (void)hipStreamSynchronize(ctx->stream);
+        sel_ws_free(ws);
+    }
+    SelWorkspaceLocal(const SelWorkspaceLocal&) = delete;
+    SelWorkspaceLocal& operator=(const SelWorkspaceLocal&) = delete;
+};
 
 // Stratified 1/64 sample of SEL_LINE-element lines: group g covers lines [64 g, 64 g + 64) and contributes the one line picked
 // by the top 6 bits of a multiplicative hash of g (no aliasing with the raster's row period, and sampled lines can be

@@ -168,61 +168,55 @@ static int texture_typed(xdemhip_ctx* ctx, const T* d_dem, int64_t H, int64_t W,
     FftApi& api = fft_api();
     if (!api.ok) return xd_fail(ctx, XDEMHIP_EUNSUPPORTED, "libhipfft.so could not be loaded (needed by texture shading only)");
     const int64_t n = H * W;
-    TexStats* d_stats = nullptr;   // [g1] per-workgroup partials, then the total
-    T *d_pad = nullptr, *d_spec = nullptr;
-    fft_handle fwd = nullptr, inv = nullptr;
-    auto cleanup = [&]() {
-        if (fwd) api.destroy(fwd);
-        if (inv) api.destroy(inv);
-        if (d_stats) (void)hipFree(d_stats);
-        if (d_pad) (void)hipFree(d_pad);
-        if (d_spec) (void)hipFree(d_spec);
-    };
     const int g1 = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
-    if (hipMalloc(reinterpret_cast<void**>(&d_stats), (size_t)(g1 + 1) * sizeof(TexStats)) != hipSuccess)
-        return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed");
+    // (the plans are declared before the buffers: on every return path the buffers' synchronisation comes first, then the plans go)
+    struct Plans {
+        FftApi& api;
+        fft_handle fwd = nullptr, inv = nullptr;
+        ~Plans() {
+            if (fwd) api.destroy(fwd);
+            if (inv) api.destroy(inv);
+        }
+    } plans{api};
+    TexStats st;   // (a copy's destination: declared before the buffers)
+    XdBuffers buf(ctx, "xdemhip_texture_shading");
+    TexStats* d_stats = buf.alloc<TexStats>((size_t)g1 + 1);   // [g1] per-workgroup partials, then the total
+    if (buf.rc) return buf.rc;
     hipLaunchKernelGGL((tex_stats_kernel<T>), dim3(g1), dim3(256), 0, ctx->stream, d_dem, n, d_stats);
     hipLaunchKernelGGL(tex_stats_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, d_stats, g1, d_stats + g1);
-    TexStats st;
     hipError_t e = hipMemcpyAsync(&st, d_stats + g1, sizeof(TexStats), hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { cleanup(); return xd_fail(ctx, XDEMHIP_EHIP, std::string("texture statistics failed: ") + hipGetErrorString(e)); }
+    if (e != hipSuccess) return xd_fail(ctx, XDEMHIP_EHIP, std::string("texture statistics failed: ") + hipGetErrorString(e));
     if (st.fin == 0) {  // no valid pixel: all NaN (freq.py:88-89)
         hipLaunchKernelGGL((tex_fill_nan_kernel<TOUT>), dim3(g1), dim3(256), 0, ctx->stream, d_out, n);
-        cleanup();
         return XDEMHIP_OK;
     }
     const T fill = (T)(st.sum / (double)st.nn);  // np.nanmean in the DEM dtype (accumulated in float64 here)
     const int64_t FH = nextprod_fft(H), FW = nextprod_fft(W), FC = FW / 2 + 1;
-    if (FH > 0x7fffffff || FW > 0x7fffffff) { cleanup(); return xd_fail(ctx, XDEMHIP_EUNSUPPORTED, "raster too large for the FFT"); }
+    if (FH > 0x7fffffff || FW > 0x7fffffff) return xd_fail(ctx, XDEMHIP_EUNSUPPORTED, "raster too large for the FFT");
     const int64_t pad_r = (FH - H) / 2, pad_c = (FW - W) / 2;
-    if (hipMalloc(reinterpret_cast<void**>(&d_pad), (size_t)FH * FW * sizeof(T)) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&d_spec), (size_t)FH * FC * 2 * sizeof(T)) != hipSuccess) {
-        cleanup();
-        return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc(FFT buffers) failed");
-    }
+    T* d_pad = buf.alloc<T>((size_t)FH * FW);
+    T* d_spec = buf.alloc<T>((size_t)FH * FC * 2);
+    if (buf.rc) return buf.rc;
     auto rows_grid = [&](int64_t cols, int64_t rows) {
         int64_t gy = rows < 1024 ? rows : 1024;
         return dim3((unsigned)((cols + 255) / 256), (unsigned)(gy < 1 ? 1 : gy));
     };
     hipLaunchKernelGGL((tex_pad_kernel<T>), rows_grid(FW, FH), dim3(256), 0, ctx->stream, d_dem, H, W, FH, FW, pad_r, pad_c, fill, d_pad);
     const bool f32 = sizeof(T) == 4;
-    if (api.plan2d(&fwd, (int)FH, (int)FW, f32 ? FFT_R2C : FFT_D2Z) != 0 || api.plan2d(&inv, (int)FH, (int)FW, f32 ? FFT_C2R : FFT_Z2D) != 0) {
-        cleanup();
+    if (api.plan2d(&plans.fwd, (int)FH, (int)FW, f32 ? FFT_R2C : FFT_D2Z) != 0 || api.plan2d(&plans.inv, (int)FH, (int)FW, f32 ? FFT_C2R : FFT_Z2D) != 0)
         return xd_fail(ctx, XDEMHIP_EHIP, "hipfftPlan2d failed");
-    }
-    api.set_stream(fwd, ctx->stream);
-    api.set_stream(inv, ctx->stream);
-    int rc = f32 ? api.exec_r2c(fwd, reinterpret_cast<float*>(d_pad), d_spec) : api.exec_d2z(fwd, reinterpret_cast<double*>(d_pad), d_spec);
+    api.set_stream(plans.fwd, ctx->stream);
+    api.set_stream(plans.inv, ctx->stream);
+    int rc = f32 ? api.exec_r2c(plans.fwd, reinterpret_cast<float*>(d_pad), d_spec) : api.exec_d2z(plans.fwd, reinterpret_cast<double*>(d_pad), d_spec);
     if (rc == 0) {
         hipLaunchKernelGGL((tex_filter_kernel<T>), rows_grid(FC, FH), dim3(256), 0, ctx->stream, d_spec, FH, FW, FC, alpha);
-        rc = f32 ? api.exec_c2r(inv, d_spec, reinterpret_cast<float*>(d_pad)) : api.exec_z2d(inv, d_spec, reinterpret_cast<double*>(d_pad));
+        rc = f32 ? api.exec_c2r(plans.inv, d_spec, reinterpret_cast<float*>(d_pad)) : api.exec_z2d(plans.inv, d_spec, reinterpret_cast<double*>(d_pad));
     }
-    if (rc != 0) { cleanup(); return xd_fail(ctx, XDEMHIP_EHIP, "hipFFT execution failed"); }
+    if (rc != 0) return xd_fail(ctx, XDEMHIP_EHIP, "hipFFT execution failed");
     hipLaunchKernelGGL((tex_crop_kernel<T, TOUT>), rows_grid(W, H), dim3(256), 0, ctx->stream, d_pad, d_dem, H, W, FW, pad_r, pad_c, d_out);
     e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    cleanup();
     if (e != hipSuccess) return xd_fail(ctx, XDEMHIP_EHIP, std::string("texture shading failed: ") + hipGetErrorString(e));
     return XDEMHIP_OK;
 }
@@ -242,18 +236,10 @@ extern "C" int xdemhip_texture_shading(xdemhip_ctx* ctx, const void* dem, int de
     XD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     const size_t in_es = dem_dtype == XDEMHIP_F32 ? 4 : 8, out_es = out_dtype == XDEMHIP_F32 ? 4 : 8;
     const size_t n = (size_t)H * (size_t)W;
-    void *d_dem = const_cast<void*>(dem), *d_out = out;
-    if (memspace == XDEMHIP_HOST) {
-        d_dem = d_out = nullptr;
-        if (hipMalloc(&d_dem, n * in_es) != hipSuccess || hipMalloc(&d_out, n * out_es) != hipSuccess) {
-            if (d_dem) (void)hipFree(d_dem);
-            return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed");
-        }
-        if (hipMemcpyAsync(d_dem, dem, n * in_es, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
-            (void)hipFree(d_dem); (void)hipFree(d_out);
-            return xd_fail(ctx, XDEMHIP_EHIP, "H2D copy failed");
-        }
-    }
+    XdBuffers buf(ctx, "xdemhip_texture_shading");
+    const void* d_dem = buf.input(dem, n * in_es, memspace);
+    void* d_out = buf.output(out, n * out_es, memspace);
+    if (buf.rc) return buf.rc;
     int rc;
     if (dem_dtype == XDEMHIP_F32)
         rc = out_dtype == XDEMHIP_F32 ? texture_typed<float, float>(ctx, static_cast<const float*>(d_dem), H, W, alpha, static_cast<float*>(d_out))
@@ -261,14 +247,5 @@ extern "C" int xdemhip_texture_shading(xdemhip_ctx* ctx, const void* dem, int de
     else
         rc = out_dtype == XDEMHIP_F32 ? texture_typed<double, float>(ctx, static_cast<const double*>(d_dem), H, W, alpha, static_cast<float*>(d_out))
                                       : texture_typed<double, double>(ctx, static_cast<const double*>(d_dem), H, W, alpha, static_cast<double*>(d_out));
-    if (memspace == XDEMHIP_HOST) {
-        if (rc == XDEMHIP_OK) {
-            hipError_t e = hipMemcpyAsync(out, d_out, n * out_es, hipMemcpyDeviceToHost, ctx->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-            if (e != hipSuccess) rc = xd_fail(ctx, XDEMHIP_EHIP, std::string("D2H copy failed: ") + hipGetErrorString(e));
-        }
-        (void)hipFree(d_dem);
-        (void)hipFree(d_out);
-    }
-    return rc;
+    return rc == XDEMHIP_OK ? buf.finish() : rc;
 }
