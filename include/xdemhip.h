@@ -137,7 +137,9 @@ int xdemhip_clock_probe(xdemhip_ctx* ctx, void* hip_stream, int sleeps, uint64_t
  *   "nk_predict"        1 (default) a settled one-pass step takes its brackets from the previous step's exact medians (see
  *                       xdemhip_nk_predict_counts), 0 every step samples.
  *   "pairs_launch_cap"  workgroups per launch of the variogram pair passes (0 = default 2^31 / workgroup size, the most a HIP dispatch
- *                       holds; a pass over more tiles goes out as several launches -- a small value exercises that path). */
+ *                       holds; a pass over more tiles goes out as several launches -- a small value exercises that path) and of the
+ *                       pair passes of CPD's E-step (0 = default: launches of at most 2^32 pair evaluations, 2^24 / slice length
+ *                       workgroups); the cut changes neither the layout of the partials nor a bit of the results. */
 int xdemhip_set_option(xdemhip_ctx* ctx, const char* name, int value);
 
 /* Multi-GPU hook for the accumulator-style paths (Nuth-Kaab reductions): one process per GPU, every rank works on its
@@ -486,6 +488,31 @@ int xdemhip_icp_pairs(xdemhip_icp* icp, int picky, int64_t* n_kept, int64_t* que
 int xdemhip_icp_sums(xdemhip_icp* icp, const double* step16, int method, double* sums_out, int64_t* count);
 int xdemhip_icp_values(xdemhip_icp* icp, double* out9k);
 void xdemhip_icp_destroy(xdemhip_icp* icp);
+
+/* ---- CPD coregistration (csrc/cpd.hip) -----------------------------------------------------------------------------------------
+ * The device passes of xdem.coreg.CPD (Myronenko & Song 2010; xdem/coreg/affine.py:1190-1409): the E-step over EVERY pair of a
+ * reference cloud x (N points) and a to-be-aligned cloud y (M points), and the sums of the M-step.  Float64 without contraction;
+ * nothing of size N M is stored; no float atomics, two calls return the same bits.
+ *  xdemhip_cpd_create_plan   the clouds (x, y, ref) and (x, y, tba) of the plan's selected pixels, centred and scaled exactly as
+ *                            xdemhip_icp_create_plan does without normals (the same code); no search grid.  *count = N = M.
+ *  xdemhip_cpd_create_points arbitrary clouds: ref3n (3 x n, rows x, y, z), tba3m (3 x m), host memory; N != M allowed; nothing is centred.
+ *  xdemhip_cpd_estep         ty_m = matrix y_m (rows 0..2 of the 4 x 4; NULL = identity).  sigma2 = the argument, or -- NaN -- the sum
+ *                            over all pairs of |x_n - ty_m|^2, added pair by pair, / (3 N M).  p_mn = exp(-((dx dx + dy dy) + dz dz) /
+ *                            (2 sigma2)), den_n = sum_m p_mn, c = (2 pi sigma2)^(3/2) weight / (1 - weight) M / N, inv_n = 1 /
+ *                            (max(den_n, 2^-52) + c), P_mn = p_mn inv_n; Pt1_n = den_n inv_n, P1_m = sum_n P_mn, PX_m = sum_n P_mn x_n.
+ *                            A workgroup of 256 lanes owns 256 points of one cloud and walks one slice of the other through LDS; a lane
+ *                            adds its slice in ascending index, slices are added in ascending order, and the slice length depends on N,
+ *                            M and the device only.  Then, in fixed-order sums: Np = sum P1, muX = sum PX / Np, muY = sum P1 y / Np,
+ *                            A = sum_m (PX_m - P1_m muX)(y_m - muY)^T, xPx = sum_n Pt1_n |x_n - muX|^2, YPY = sum_m P1_m |y_m - muY|^2.
+ *                            sums_out[18] = Np, muX (3), muY (3), A (9, row by row), xPx, YPY; *sigma2_used.  One fetch.  0 <= weight < 1.
+ *  xdemhip_cpd_terms         host copies of the last E-step's P1 (M), Pt1 (N) and PX (3 x M, rows x, y, z); any may be NULL. */
+typedef struct xdemhip_cpd xdemhip_cpd;
+int xdemhip_cpd_create_plan(xdemhip_dh_plan* plan, const double* transform6, int standardize, xdemhip_cpd** out, double* centroid3, double* std_fac,
+                            int64_t* count);
+int xdemhip_cpd_create_points(xdemhip_ctx* ctx, const double* ref3n, int64_t n, const double* tba3m, int64_t m, xdemhip_cpd** out);
+int xdemhip_cpd_estep(xdemhip_cpd* cpd, const double* matrix16_or_null, double sigma2_or_nan, double weight, double* sums_out, double* sigma2_used);
+int xdemhip_cpd_terms(xdemhip_cpd* cpd, double* p1_out, double* pt1_out, double* px_out);
+void xdemhip_cpd_destroy(xdemhip_cpd* cpd);
 
 /* out = cast(double(elev) + P(x, y)), P = np.polynomial.polynomial.polyval2d(x, y, c) with c[i, j] = coeffs[i * (order + 1) + j]
  * (the reference's fit_params reshaped), x = column, y = row_offset + row, evaluated in NumPy's order bit for bit: Horner in x for

@@ -202,6 +202,12 @@ def lib() -> ctypes.CDLL:
         L.xdemhip_icp_values.argtypes = [ctypes.c_void_p, c_dp]
         L.xdemhip_icp_destroy.argtypes = [ctypes.c_void_p]
         L.xdemhip_icp_destroy.restype = None
+        L.xdemhip_cpd_create_plan.argtypes = [ctypes.c_void_p, c_dp, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), c_dp, c_dp, c_i64p]
+        L.xdemhip_cpd_create_points.argtypes = [c_ctx, c_dp, ctypes.c_int64, c_dp, ctypes.c_int64, ctypes.POINTER(ctypes.c_void_p)]
+        L.xdemhip_cpd_estep.argtypes = [ctypes.c_void_p, c_dp, ctypes.c_double, ctypes.c_double, c_dp, c_dp]
+        L.xdemhip_cpd_terms.argtypes = [ctypes.c_void_p, c_dp, c_dp, c_dp]
+        L.xdemhip_cpd_destroy.argtypes = [ctypes.c_void_p]
+        L.xdemhip_cpd_destroy.restype = None
         L.xdemhip_apply_matrix_rst.argtypes = [c_ctx, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, c_dp, c_dp, c_dp,
                                                ctypes.c_void_p, ctypes.c_int]
         L.xdemhip_poly2d_apply.argtypes = [c_ctx, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, c_dp,

@@ -31,6 +31,7 @@ from .biascorr import Deramp, DhPlan, VerticalShift, _check_weights, polynomial_
 from .rigid import (LZD, apply_matrix, invert_matrix, matrix_from_translations_rotations,  # noqa: F401  (and these)
                     translations_rotations_from_matrix, _make_matrix_valid)
 from .icp import ICP, nearest  # noqa: F401
+from .cpd import CPD, cpd_expectation, cpd_update  # noqa: F401
 from .spatialstats import nmad
 
 

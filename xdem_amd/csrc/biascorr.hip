@@ -795,10 +795,13 @@ int FixedSums::reserve(xdemhip_ctx* ctx, int nt, const char* who) {
     cap = need;
     return XDEMHIP_OK;
 }
+int fixed_sums_reduce(xdemhip_ctx* ctx, double* part, int nblocks, int nt, const char* what) {
+    hipLaunchKernelGGL(fixed_sums_reduce_kernel, dim3((unsigned)nt), dim3(256), 0, ctx->stream, part, nblocks, nt, part + (int64_t)nblocks * nt);
+    return launched(ctx, what);
+}
 int fixed_sums_finish(xdemhip_ctx* ctx, const FixedSums& fs, int nblocks, int nt, const char* what, double* totals) {
     double* d_out = fs.part + (int64_t)nblocks * nt;
-    hipLaunchKernelGGL(fixed_sums_reduce_kernel, dim3((unsigned)nt), dim3(256), 0, ctx->stream, fs.part, nblocks, nt, d_out);
-    int rc = launched(ctx, what);
+    int rc = fixed_sums_reduce(ctx, fs.part, nblocks, nt, what);
     (void)hipEventRecord(ctx->ev_stop, ctx->stream);
     ctx->timed = (rc == XDEMHIP_OK);
     if (rc == XDEMHIP_OK) rc = xd_d2h(ctx, totals, d_out, (size_t)nt * 8);   // the one fetch of the call

@@ -21,7 +21,7 @@ struct xdemhip_ctx {
     void* stage_in[2] = {nullptr, nullptr};            // pinned staging of the host-buffer terrain path (double-buffered), kept between calls
     void* stage_out[2] = {nullptr, nullptr};
     size_t stage_in_bytes = 0, stage_out_bytes = 0;
-    int pairs_launch_cap = 0;                         // option "pairs_launch_cap": workgroups per pair-kernel launch (0 = 2^31 / NT)
+    int pairs_launch_cap = 0;                         // option "pairs_launch_cap": workgroups per pair-kernel launch (0 = 2^31 / NT; CPD: 2^32 pair evaluations)
     bool timed = false;
     int num_cu = 256;
     xdemhip_allreduce_fn allreduce = nullptr;  // multi-GPU hook (null: single process)

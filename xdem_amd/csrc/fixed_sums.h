@@ -1,5 +1,5 @@
 // fixed_sums.h -- float64 sums added in a fixed order, so that two calls return the same bits: the one home of what the moments of
-// Deramp (biascorr.hip), the normal equations of LZD (rigid.hip) and the sums of ICP (icp.hip) share.
+// Deramp (biascorr.hip), the normal equations of LZD (rigid.hip), the sums of ICP (icp.hip) and the M-step of CPD (cpd.hip) share.
 //
 // FOR TRANSLATION UNITS BUILT WITH -ffp-contract=off: the terms reproduce NumPy's arithmetic only without contraction.
 //
@@ -44,7 +44,7 @@ template <int N> __device__ __forceinline__ void block_sums_store(const double* 
 }
 
 // ---- host side (defined in biascorr.hip) -----------------------------------------------------------------------------------------
-// The partials of one owner (a dh plan, an ICP object) and the totals behind them: num_cu * 8 + 1 rows of nt doubles, made at the
+// The partials of one owner (a dh plan, an ICP or CPD object) and the totals behind them: num_cu * 8 + 1 rows of nt doubles, made at the
 // first call and kept (nothing is allocated per iteration); grows when a call has more terms.
 struct FixedSums {
     double* part = nullptr;
@@ -62,6 +62,9 @@ inline int fixed_sums_grid(const xdemhip_ctx* ctx, int64_t units) {
     if (nb > units) nb = units;
     return nb < 1 ? 1 : (int)nb;
 }
+// The reduce kernel alone, for sums whose totals the next kernel reads (the two stages of CPD's M-step): `part` holds `nblocks` rows of
+// `nt` partials, the totals land behind them at part + nblocks * nt; the check of both launches ("`what` launch failed").
+int fixed_sums_reduce(xdemhip_ctx* ctx, double* part, int nblocks, int nt, const char* what);
 // What follows a sums kernel that wrote `nblocks` rows of `nt` partials: the reduce kernel, the check of both launches ("`what` launch
 // failed"), ev_stop, ctx->timed, the one fetch of the nt totals, xd_sync.
 int fixed_sums_finish(xdemhip_ctx* ctx, const FixedSums& fs, int nblocks, int nt, const char* what, double* totals);

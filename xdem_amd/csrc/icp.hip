@@ -3,7 +3,7 @@
 //
 // Replaces, for raster-raster input (xdem/coreg/affine.py):
 //   _icp_norms                                                           affine.py:1062-1081 -> icp_normals_kernel (once per plan)
-//   _standardize_epc (np.median, nmad)                                   affine.py:296-328   -> exact selections (select_run.h)
+//   _standardize_epc (np.median, nmad)                                   affine.py:296-328   -> exact selections (cloud_front.h)
 //   scipy.spatial.KDTree(ref_epc.T).query(trans.T, k=1)                  affine.py:1013,1155 -> a uniform cell grid built by a counting
 //                                                                                              sort, icp_query_kernel walking rings
 //   picky duplicate removal (pandas groupby().idxmin())                  affine.py:1017-1021 -> three atomicMin passes, rank_select.h
@@ -23,6 +23,7 @@
 #include "rank_select.h"
 #include "rigid_geom.h"
 #include "dh_plan.h"
+#include "cloud_front.h"
 
 struct xdemhip_icp {
     xdemhip_ctx* ctx = nullptr;
@@ -84,32 +85,6 @@ __global__ __launch_bounds__(256) void icp_normals_kernel(const T* __restrict__ 
         pnx[p] = vx; pny[p] = vy; pnz[p] = vz;
         if (!(t_finite<T>(vx) && t_finite<T>(vy) && t_finite<T>(vz))) valid[p] = 0;
     }
-}
-
-// ---- clouds ----------------------------------------------------------------------------------------------------------------------
-template <typename T>
-__global__ __launch_bounds__(256) void icp_gather_kernel(const T* __restrict__ ref, const T* __restrict__ tba, const T* __restrict__ pnx,
-                                                         const T* __restrict__ pny, const T* __restrict__ pnz, const int64_t* __restrict__ idx, int64_t n,
-                                                         int64_t W, double ta, double tc, double te, double tf, double* __restrict__ x,
-                                                         double* __restrict__ y, double* __restrict__ zr, double* __restrict__ zt, double* __restrict__ nx,
-                                                         double* __restrict__ ny, double* __restrict__ nz) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t q = idx[i], r = q / W, c = q - r * W;
-        x[i] = tc + ((double)c + 0.5) * ta;
-        y[i] = tf + ((double)r + 0.5) * te;
-        zr[i] = (double)ref[q];
-        zt[i] = (double)tba[q];
-        if (pnx) { nx[i] = (double)pnx[q]; ny[i] = (double)pny[q]; nz[i] = (double)pnz[q]; }
-    }
-}
-__global__ __launch_bounds__(256) void icp_sub_kernel(double* __restrict__ v, int64_t n, double c) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) v[i] = v[i] - c;
-}
-__global__ __launch_bounds__(256) void icp_div_kernel(double* __restrict__ v, int64_t n, double f) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) v[i] = v[i] / f;
-}
-__global__ __launch_bounds__(256) void icp_absdev_kernel(const double* __restrict__ v, int64_t n, double c, double* __restrict__ out) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) out[i] = fabs(v[i] - c);
 }
 
 // ---- the cell grid ---------------------------------------------------------------------------------------------------------------
@@ -342,16 +317,6 @@ template <typename P> int icp_alloc(xdemhip_icp* I, P** p, size_t bytes, const c
     return XDEMHIP_OK;
 }
 
-// exact np.median of d[0..n) (one local selection; a reduction hook on the context is suspended)
-int icp_median(xdemhip_ctx* ctx, const double* d, int64_t n, unsigned char* scratch, SelWorkspace* ws, double* out) {
-    std::vector<SelResult<uint64_t>> r;
-    XdLocalSelection local(ctx);
-    const int rc = run_select<double>(ctx, d, nullptr, n, 1, scratch, r, ws);
-    if (rc) return rc;
-    *out = median_from<double>(r[0]);
-    return XDEMHIP_OK;
-}
-
 // The grid over the reference cloud: cells of side h with about ICP_OCCUPANCY points each, from the bounding box and n; an axis of
 // zero extent gets one row of cells, and h is never below what a one-dimensional cloud needs (so the cells number at most ~ n).
 int icp_build_grid(xdemhip_icp* I) {
@@ -511,60 +476,12 @@ int xdemhip_icp_create_plan(xdemhip_dh_plan* P, const double* transform6, int wi
     xdemhip_icp* I = new xdemhip_icp();
     I->ctx = ctx; I->n = n; I->m = n;
     auto fail = [&](int code) { icp_free(I); return code; };
-    double* base = nullptr;
-    { const int rc_ = icp_alloc(I, &base, (size_t)n * 8 * (with_normals ? 7 : 4), "ICP clouds"); if (rc_) return fail(rc_); }
-    I->rx = I->qx = base; I->ry = I->qy = base + n; I->rz = base + 2 * n; I->qz = base + 3 * n;
-    if (with_normals) { I->nx = base + 4 * n; I->ny = base + 5 * n; I->nz = base + 6 * n; }
-    const dim3 grid(grid_for(ctx, n, 256, 16));
-    if (P->dtype == XDEMHIP_F32)
-        hipLaunchKernelGGL((icp_gather_kernel<float>), grid, dim3(256), 0, ctx->stream, static_cast<const float*>(P->ref), static_cast<const float*>(P->tba),
-                           with_normals ? static_cast<const float*>(P->icp_n[0]) : nullptr, static_cast<const float*>(P->icp_n[1]),
-                           static_cast<const float*>(P->icp_n[2]), P->idx, n, P->W, transform6[0], transform6[2], transform6[4], transform6[5], I->rx, I->ry,
-                           I->rz, I->qz, I->nx, I->ny, I->nz);
-    else
-        hipLaunchKernelGGL((icp_gather_kernel<double>), grid, dim3(256), 0, ctx->stream, static_cast<const double*>(P->ref), static_cast<const double*>(P->tba),
-                           with_normals ? static_cast<const double*>(P->icp_n[0]) : nullptr, static_cast<const double*>(P->icp_n[1]),
-                           static_cast<const double*>(P->icp_n[2]), P->idx, n, P->W, transform6[0], transform6[2], transform6[4], transform6[5], I->rx, I->ry,
-                           I->rz, I->qz, I->nx, I->ny, I->nz);
-    { const int rc_ = launched(ctx, "icp_gather_kernel"); if (rc_) return fail(rc_); }
-    // standardisation: three medians for the centroid, three more (of the centred values, as np.median sees them) and three of the
-    // absolute deviations for the NMADs
-    unsigned char* scratch = nullptr;
-    double* tmp = nullptr;
-    { const int rc_ = icp_alloc(I, &scratch, scratch_size(1), "ICP selection"); if (rc_) return fail(rc_); }
-    { const int rc_ = icp_alloc(I, &tmp, (size_t)n * 8, "ICP selection"); if (rc_) return fail(rc_); }
-    double* axis[3] = {I->rx, I->ry, I->rz};
-    double nmads[3] = {0.0, 0.0, 0.0};
-    int rc = XDEMHIP_OK;
-    {   // (the workspace goes when the medians are done)
-        SelWorkspaceLocal lws(ctx);
-        SelWorkspace& ws = lws.ws;
-        if (n >= SEL_BRACKET_MIN_N) (void)sel_ws_create(ctx, n, 8, 1, ws);
-        for (int a = 0; a < 3 && rc == XDEMHIP_OK; ++a) {
-            double med = 0.0, med2 = 0.0, mad = 0.0;
-            rc = icp_median(ctx, axis[a], n, scratch, &ws, &med);
-            if (rc) break;
-            centroid3[a] = med;
-            hipLaunchKernelGGL(icp_sub_kernel, grid, dim3(256), 0, ctx->stream, axis[a], n, med);
-            if (a == 2) hipLaunchKernelGGL(icp_sub_kernel, grid, dim3(256), 0, ctx->stream, I->qz, n, med);
-            if (!standardize) continue;
-            rc = icp_median(ctx, axis[a], n, scratch, &ws, &med2);
-            if (rc) break;
-            hipLaunchKernelGGL(icp_absdev_kernel, grid, dim3(256), 0, ctx->stream, axis[a], n, med2, tmp);
-            rc = icp_median(ctx, tmp, n, scratch, &ws, &mad);
-            nmads[a] = 1.4826 * mad;
-        }
-    }
+    CloudFront C;   // the gather and the standardisation: cloud_front.h, shared with cpd.hip
+    int rc = cloud_front_build(P, transform6, with_normals != 0, standardize != 0, "ICP",
+                               [&](auto** p, size_t bytes, const char* what) { return icp_alloc(I, p, bytes, what); }, C, centroid3, std_fac);
     if (rc) return fail(rc);
-    double f = 1.0;
-    if (standardize) {
-        f = ((nmads[0] + nmads[1]) + nmads[2]) / 3.0;
-        if (!(f > 0.0) || !isfinite(f)) return fail(xd_fail(ctx, XDEMHIP_EINVAL, "ICP: the standardisation factor (mean NMAD of the reference cloud) is not positive"));
-        double* all[4] = {I->rx, I->ry, I->rz, I->qz};
-        for (int a = 0; a < 4; ++a) hipLaunchKernelGGL(icp_div_kernel, grid, dim3(256), 0, ctx->stream, all[a], n, f);
-    }
-    *std_fac = f;
-    { const int rc_ = launched(ctx, "ICP standardisation"); if (rc_) return fail(rc_); }
+    I->rx = I->qx = C.x; I->ry = I->qy = C.y; I->rz = C.zr; I->qz = C.zt;
+    I->nx = C.nx; I->ny = C.ny; I->nz = C.nz;
     rc = icp_build_grid(I);
     if (rc == XDEMHIP_OK) rc = icp_alloc_work(I);
     if (rc == XDEMHIP_OK) rc = xd_sync(ctx);

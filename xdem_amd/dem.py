@@ -128,7 +128,7 @@ class DEM:
         """Align this DEM to ``reference_elev`` (same grid) with ``coreg_method`` (upstream requires one and names Nuth and
         Kaab as the default in its docstring: ``None`` means ``NuthKaab(subsample=1)`` here).  ``random_state`` seeds the
         subsampling; ``resample`` (keyword, default True) as upstream.  ``coreg_method``: ``NuthKaab``, ``DhMinimize``, ``LZD``, ``ICP``,
-        ``Deramp``, ``VerticalShift`` or a ``CoregPipeline`` of them; ``bias_vars`` belongs to bias corrections with explicit variables, which are
+        ``CPD``, ``Deramp``, ``VerticalShift`` or a ``CoregPipeline`` of them; ``bias_vars`` belongs to bias corrections with explicit variables, which are
         not part of this package."""
         resample = kwargs.pop("resample", True)
         if bias_vars is not None:

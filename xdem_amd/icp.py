@@ -13,7 +13,7 @@ Every pass over the rasters and the clouds runs in ``csrc/icp.hip``:
   from the device and runs on the host exactly as ``_icp_fit`` calls it.
 
 The clouds' coordinates are pixel centres under the 6-tuple transform, as in ``xdem_amd.rigid``; NMAD is ``1.4826 * median|v - median v|``
-(geoutils' ``nmad`` is absent: **parity unpinned**).  ``CPD``, point-cloud inputs and ``initial_shift`` are not implemented.  The front
+(geoutils' ``nmad`` is absent: **parity unpinned**).  Point-cloud inputs and ``initial_shift`` are not implemented (``CPD`` is ``xdem_amd.cpd``).  The front
 of ``fit``, the iteration loop, ``apply`` and the accessors are ``rigid._RigidStep``'s; ``solve_scaled`` is ``rigid``'s."""
 from __future__ import annotations
 

@@ -18,7 +18,7 @@ The grid's coordinates are pixel centres under the 6-tuple transform ``(a, b, c,
 ``y = f + (row + 0.5) e`` -- geoutils' ``_coords`` / ``_interp_points`` / ``to_pointcloud`` are un-vendored and absent, **parity unpinned**;
 the convention is self-consistent (an identity matrix samples pixel (r, c) at (r, c)).
 
-``_RigidStep`` carries what LZD and ``xdem_amd.icp.ICP`` share: the front of ``fit``, the iteration loop, the outputs, ``apply`` and the accessors."""
+``_RigidStep`` carries what LZD, ``xdem_amd.icp.ICP`` and ``xdem_amd.cpd.CPD`` share: the front of ``fit``, the iteration loop, the outputs, ``apply`` and the accessors."""
 from __future__ import annotations
 
 import contextlib
@@ -244,22 +244,34 @@ def design_rows(arrays) -> np.ndarray:
 
 
 # ---- what LZD and ICP share ---------------------------------------------------------------------------------------------------------
-def _iterate(step_matrix: Callable[[np.ndarray], np.ndarray], max_iterations: int, tolerance: float) -> tuple[np.ndarray, list]:
-    """Upstream's ``_iterate_method`` (affine.py:102-147): ``step_matrix(matrix)`` makes an iteration's step from the transform so far.
-    Returns the transform and the ``(transform, statistic)`` of every iteration; the statistic is upstream's, |t1 + t2 + t3|."""
-    matrix, history = np.eye(4), []
+def _iterate_method(method: Callable[[Any], tuple[Any, float]], iterating_input: Any, tolerance: float, max_iterations: int) -> tuple[Any, list]:
+    """Upstream's ``_iterate_method`` (affine.py:102-147) in general: ``method(input)`` returns ``(new input, statistic)``; the loop stops
+    after an iteration with ``i > 1 and statistic < tolerance``.  (The constant inputs are the method's own, by closure.)  Returns the
+    last input and the ``(input, statistic)`` of every iteration."""
+    new_inputs, history = iterating_input, []
     for i in range(int(max_iterations)):
-        step = step_matrix(matrix)
-        matrix = step @ matrix
-        stat = float(np.sqrt(np.sum(step[:3, 3]) ** 2))
-        history.append((matrix.copy(), stat))
-        if i > 1 and stat < tolerance:
+        new_inputs, new_statistic = method(new_inputs)
+        history.append((new_inputs, new_statistic))
+        if i > 1 and new_statistic < tolerance:
             break
-    return matrix, history
+    return new_inputs, history
+
+
+def _iterate(step_matrix: Callable[[np.ndarray], np.ndarray], max_iterations: int, tolerance: float) -> tuple[np.ndarray, list]:
+    """``_iterate_method`` for the methods that compose step matrices (LZD, ICP): ``step_matrix(matrix)`` makes an iteration's step from
+    the transform so far.  Returns the transform and the ``(transform, statistic)`` of every iteration; the statistic is upstream's,
+    |t1 + t2 + t3|."""
+
+    def method(matrix: np.ndarray) -> tuple[np.ndarray, float]:
+        step = step_matrix(matrix)
+        return step @ matrix, float(np.sqrt(np.sum(step[:3, 3]) ** 2))
+
+    matrix, history = _iterate_method(method, np.eye(4), tolerance, max_iterations)
+    return matrix, [(m.copy(), stat) for m, stat in history]
 
 
 class _RigidStep(_Step):
-    """What the steps that estimate a rotation and a translation (LZD, ICP) share -- the counterpart of ``coreg._TranslationStep``: the
+    """What the steps that estimate a rotation and a translation (LZD, ICP, CPD) share -- the counterpart of ``coreg._TranslationStep``: the
     front of ``fit``, the writing of its outputs, ``apply`` through ``apply_matrix`` and the accessors of the stored transform."""
 
     def _check(self) -> None:   # (a step's own checks of its inputs, made before anything of the call is stored)
