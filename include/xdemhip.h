@@ -390,6 +390,52 @@ int xdemhip_dh_shift_values(xdemhip_dh_plan* plan, double shift_x, double shift_
                             int64_t* count);
 void xdemhip_dh_destroy(xdemhip_dh_plan* plan);
 
+/* ---- bias corrections with variables: BiasCorr, DirectionalBias, TerrainBias (csrc/bincorr.hip) --------------------------------
+ * The raster passes of xdem.coreg.BiasCorr / DirectionalBias / TerrainBias (xdem/coreg/biascorr.py:40-618) for two rasters on one
+ * grid.  A variable of a correction is described by its SOURCE, so that the two variables upstream materialises as whole-raster
+ * planes -- the rotated coordinate of DirectionalBias, the elevation of TerrainBias("elevation") -- are formed per pixel instead:
+ *   XDEMHIP_VAR_PLANE    `plane`: H x W values (`dtype` float32 / float64) in the call's memspace;
+ *   XDEMHIP_VAR_ROTATED  the along-track coordinate of a north-up grid, float64, every operation rounded on its own:
+ *                          x = (col * res_x) * cos_t + ((H - 1 - row) * res_y) * sin_t - offset
+ *                        (xdem_amd.bincorr.rotated_x is the same arithmetic on the host);
+ *   XDEMHIP_VAR_REF      the reference raster of the plan (xdemhip_corr_apply: the raster `elev` itself), in the raster dtype;
+ *   XDEMHIP_VAR_TBA      the to-be-aligned raster of the plan (xdemhip_dh_var_columns only).
+ *
+ *  xdemhip_dh_restrict_finite  narrows the plan's valid mask by isfinite(var) for a plane on the plan's grid -- upstream's valid mask
+ *                              of a bias correction is inlier & finite(ref) & finite(tba) & finite(every variable) (base.py:653-661),
+ *                              and the subsample ranks are drawn among exactly those pixels; *n_valid = the new count.  Only before
+ *                              xdemhip_dh_subsample or any call that lists the valid pixels: XDEMHIP_EINVAL afterwards.
+ *  xdemhip_dh_var_columns      for the selected pixels in raster order: dh (plan dtype) and the value of each of the n_var (<= 8)
+ *                              variables as columns of *count elements -- a plane's values in the plane's dtype, the rotated
+ *                              coordinate in float64, ref / tba in the plan dtype.  With XDEMHIP_DEVICE the columns are what
+ *                              xdemhip_binstats_create / _add_var take, without a host round trip (planes are then device planes too).
+ *  xdemhip_corr_apply          out = (raster dtype)((double)elev + corr(variables)) in one pass over the raster, corr being
+ *     XDEMHIP_CORR_GRID    the multilinear interpolant of xdemhip_interp_grid_linear (same code, same bits): n_tab[d] = points of
+ *                          axis d, `a` = the axes concatenated, `table` = the grid values in C order; 1 to 3 variables;
+ *     XDEMHIP_CORR_PERBIN  the lookup of xdemhip_perbin_lookup for disjoint intervals (same code): n_tab[d] = intervals of variable
+ *                          d, `a` / `b` = their left / right ends concatenated, `table` / `pass` over their product;
+ *                          *n_missing = pixels in a bin of kind 2; 1 to 3 variables;
+ *     XDEMHIP_CORR_POLY    sum c_i x^i by Horner's rule in float64 as np.polynomial.polynomial.polyval evaluates it
+ *                          (c0 = c[n-1] + x * 0, then c0 = c[n-i] + c0 * x); n_tab[0] = n <= 64, `table` = c; one variable;
+ *     XDEMHIP_CORR_SUMSIN  sum_k a_k sin(2 pi / b_k x + c_k), float64, terms added in index order (xdem/fit.py:87-112);
+ *                          n_tab[0] = 3 K <= 192, `table` = (a_0, b_0, c_0, a_1, ...); one variable.
+ *                          The tables are small and live in LDS: more than 3072 table entries (bins, or grid points) are refused
+ *                          with XDEMHIP_EINVAL.  float32 variables are widened to float64 first, as NumPy does. */
+enum { XDEMHIP_VAR_PLANE = 0, XDEMHIP_VAR_ROTATED = 1, XDEMHIP_VAR_REF = 2, XDEMHIP_VAR_TBA = 3 };
+enum { XDEMHIP_CORR_GRID = 0, XDEMHIP_CORR_PERBIN = 1, XDEMHIP_CORR_POLY = 2, XDEMHIP_CORR_SUMSIN = 3 };
+typedef struct xdemhip_varsrc {
+    int kind;           /* XDEMHIP_VAR_* */
+    int dtype;          /* XDEMHIP_VAR_PLANE: XDEMHIP_F32 / XDEMHIP_F64 */
+    const void* plane;  /* XDEMHIP_VAR_PLANE */
+    double cos_t, sin_t, res_x, res_y, offset;   /* XDEMHIP_VAR_ROTATED */
+} xdemhip_varsrc;
+int xdemhip_dh_restrict_finite(xdemhip_dh_plan* plan, const void* var, int dtype, int memspace, int64_t* n_valid);
+int xdemhip_dh_var_columns(xdemhip_dh_plan* plan, int n_var, const xdemhip_varsrc* vars, void* dh_out, void* const* var_out, int memspace,
+                           int64_t* count);
+int xdemhip_corr_apply(xdemhip_ctx* ctx, const void* elev, int dtype, int64_t H, int64_t W, int kind, int n_var, const xdemhip_varsrc* vars,
+                       const int* n_tab, const double* a, const double* b, const double* table, const unsigned char* pass, void* out,
+                       int64_t* n_missing, int memspace);
+
 /* ---- rigid coregistration: LZD and the rotation-capable raster apply (csrc/rigid.hip) ------------------------------------------
  * The grid passes of xdem.coreg.LZD (Rosenholm & Torlegard 1988; xdem/coreg/affine.py:1417-1776) on a dh plan, and
  * _iterate_affine_regrid_small_rotations (xdem/coreg/base.py:1389-1519) for resampling="linear".

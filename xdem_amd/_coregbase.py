@@ -222,12 +222,34 @@ class CoregPipeline(_Step):
                 del m.meta["inputs"]["affine"]["initial_shift"]
         return CoregPipeline(steps)
 
+    def _parse_bias_vars(self, step: int, bias_vars: dict | None) -> dict:
+        """The bias variables of one step that needs them, picked from the pipeline's (base.py:2930-2969, same messages)."""
+        nb_needs_vars = sum(bool(getattr(c, "_needs_vars", False)) for c in self.pipeline)
+        coreg = self.pipeline[step]
+        var_names = coreg.meta["inputs"]["fitorbin"]["bias_var_names"]
+        if bias_vars is None:
+            msg = f"No `bias_vars` passed to .fit() for bias correction step {coreg.__class__} of the pipeline."
+            if nb_needs_vars > 1:
+                msg += (" As you are using several bias correction steps requiring `bias_vars`, don't forget to "
+                        "explicitly define their `bias_var_names` during "
+                        "instantiation, e.g. {}(bias_var_names=['slope']).".format(coreg.__class__.__name__))
+            raise ValueError(msg)
+        if var_names is None and nb_needs_vars > 1:
+            raise ValueError("When using several bias correction steps requiring `bias_vars` in a pipeline,"
+                             "the `bias_var_names` need to be explicitly defined at each step's "
+                             "instantiation, e.g. {}(bias_var_names=['slope']).".format(coreg.__class__.__name__))
+        if var_names is None:   # (one step, names left open: it takes every variable and records their names at its fit)
+            return dict(bias_vars)
+        if not all(n in bias_vars.keys() for n in var_names):
+            raise ValueError("Not all keys of `bias_vars` in .fit() match the `bias_var_names` defined during "
+                             "instantiation of the bias correction step {}: {}.".format(coreg.__class__, var_names))
+        return {n: bias_vars[n] for n in var_names}
+
     def fit(self, reference_elev, to_be_aligned_elev, inlier_mask=None, bias_vars=None, weights=None, subsample=None, transform=None,
             crs=None, area_or_point=None, z_name=None, random_state=None, **kwargs: Any) -> "CoregPipeline":
         """Fit every step on the output of the previous step's ``apply`` (base.py:2967-3050); the last step is not applied.
-        ``resolution=`` (keyword) reaches every step's fit and apply, like ``transform``."""
-        if bias_vars is not None:
-            raise NotImplementedError("bias_vars: no step of this package takes bias variables.")
+        ``resolution=`` (keyword) reaches every step's fit and apply, like ``transform``.  ``bias_vars`` go to the steps that need
+        them (``BiasCorr``), to their fit and to their apply; the other steps never see them."""
         argspec = [inspect.getfullargspec(c.__class__) for c in self.pipeline]
         sub_meta = [c.meta["inputs"]["random"]["subsample"] for c in self.pipeline]
         sub_is_default = [argspec[i].defaults[argspec[i].args.index("subsample") - 1] == sub_meta[i] for i in range(len(argspec))]
@@ -243,10 +265,11 @@ class CoregPipeline(_Step):
         out_transform = transform
         for i, step in enumerate(self.pipeline):
             logging.debug("Running pipeline step: %d / %d", i + 1, len(self.pipeline))
+            step_vars = {"bias_vars": self._parse_bias_vars(i, bias_vars)} if getattr(step, "_needs_vars", False) else {}
             step.fit(reference_elev=reference_elev, to_be_aligned_elev=tba_mod, inlier_mask=inlier_mask, transform=out_transform, crs=crs,
-                     z_name=z_name, weights=weights, subsample=subsample, random_state=random_state, **extra, **kwargs)
+                     z_name=z_name, weights=weights, subsample=subsample, random_state=random_state, **step_vars, **extra, **kwargs)
             if i != len(self.pipeline) - 1:
-                res = step.apply(elev=tba_mod, transform=out_transform, crs=crs, z_name=z_name, **extra)
+                res = step.apply(elev=tba_mod, transform=out_transform, crs=crs, z_name=z_name, **step_vars, **extra)
                 if out_transform is None:
                     tba_mod = res
                 else:
@@ -259,13 +282,12 @@ class CoregPipeline(_Step):
         """Apply the steps in order (base.py:3106-3150).  With ``transform=`` returns ``(array, transform)``, else the array."""
         if not self._fit_called:
             raise AssertionError(".fit() does not seem to have been called yet")
-        if bias_vars is not None:
-            raise NotImplementedError("bias_vars: no step of this package takes bias variables.")
         elev_mod = elev
         out_transform = transform
-        for step in self.pipeline:
+        for i, step in enumerate(self.pipeline):
+            step_vars = {"bias_vars": self._parse_bias_vars(i, bias_vars)} if getattr(step, "_needs_vars", False) else {}
             res = step.apply(elev=elev_mod, transform=out_transform, crs=crs, z_name=z_name, resample=resample, resampling=resampling,
-                             **kwargs)
+                             **step_vars, **kwargs)
             if out_transform is None:
                 elev_mod = res
             else:

@@ -61,6 +61,18 @@ def host_library(required: bool = True):
         return None
 
 
+# variable sources and kinds of correction of the bias corrections with variables (include/xdemhip.h)
+VAR_PLANE, VAR_ROTATED, VAR_REF, VAR_TBA = 0, 1, 2, 3
+CORR_GRID, CORR_PERBIN, CORR_POLY, CORR_SUMSIN = 0, 1, 2, 3
+
+
+class VarSrc(ctypes.Structure):
+    """``xdemhip_varsrc``: where a variable of a bias correction comes from."""
+
+    _fields_ = [("kind", ctypes.c_int), ("dtype", ctypes.c_int), ("plane", ctypes.c_void_p), ("cos_t", ctypes.c_double),
+                ("sin_t", ctypes.c_double), ("res_x", ctypes.c_double), ("res_y", ctypes.c_double), ("offset", ctypes.c_double)]
+
+
 def lib() -> ctypes.CDLL:
     """Load (once) and return the shared library with argtypes declared."""
     global _lib
@@ -190,6 +202,11 @@ def lib() -> ctypes.CDLL:
         L.xdemhip_dh_lzd_centroid.argtypes = [ctypes.c_void_p, c_dp, c_dp, c_i64p]
         L.xdemhip_dh_lzd_normal.argtypes = [ctypes.c_void_p, c_dp, c_dp, c_dp, c_dp, c_i64p]
         L.xdemhip_dh_lzd_values.argtypes = [ctypes.c_void_p, c_dp, c_dp, c_dp, c_dp, c_i64p]
+        L.xdemhip_dh_restrict_finite.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_i64p]
+        L.xdemhip_dh_var_columns.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(VarSrc), ctypes.c_void_p,
+                                             ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, c_i64p]
+        L.xdemhip_corr_apply.argtypes = [c_ctx, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                         ctypes.POINTER(VarSrc), c_ip, c_dp, c_dp, c_dp, ctypes.c_char_p, ctypes.c_void_p, c_i64p, ctypes.c_int]
         L.xdemhip_dh_icp_normals.argtypes = [ctypes.c_void_p, c_dp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, c_i64p]
         L.xdemhip_icp_create_plan.argtypes = [ctypes.c_void_p, c_dp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), c_dp, c_dp, c_i64p]
         L.xdemhip_icp_create_points.argtypes = [c_ctx, c_dp, ctypes.c_int64, c_dp, ctypes.c_int64, c_dp, ctypes.POINTER(ctypes.c_void_p)]

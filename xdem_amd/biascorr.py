@@ -22,13 +22,14 @@ from __future__ import annotations
 import ctypes
 import logging
 import math
+import warnings
 from typing import Any, Callable
 
 import numpy as np
 import scipy.optimize
 
 from . import _lib
-from ._coregbase import CoregPipeline, _Plan, _Step, _with_transform, apply_translation, draw, raster_pair  # noqa: F401
+from ._coregbase import NO_VALID, CoregPipeline, _Plan, _Step, _with_transform, apply_translation, draw, raster_pair  # noqa: F401
 
 MAX_DEVICE_ORDER = 5
 
@@ -48,6 +49,30 @@ def _host_array(a):
     if a is None:
         return None
     return np.asarray(a.filled(np.nan) if isinstance(a, np.ma.MaskedArray) else a)
+
+
+def plane_in_space(plane, device):
+    """A float32 / float64 plane where a call reads it: on ``device`` (a torch device: a contiguous CUDA tensor, uploaded or moved
+    if need be, the current stream synchronised) or, with ``device`` None, on the host (a contiguous NumPy array).  Other dtypes
+    become float64.  Returns (pointer, dtype code, shape, the array to keep alive)."""
+    if device is not None:
+        import torch
+
+        if hasattr(plane, "is_cuda"):
+            t = plane
+        else:
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore", UserWarning)   # (a read-only array is only read)
+                t = torch.from_numpy(np.ascontiguousarray(_host_array(plane)))
+        if t.dtype not in (torch.float32, torch.float64):
+            t = t.to(torch.float64)
+        t = t.to(device).contiguous()
+        torch.cuda.current_stream(t.device).synchronize()
+        return t.data_ptr(), (_lib.F32 if t.dtype == torch.float32 else _lib.F64), tuple(t.shape), t
+    t = np.ascontiguousarray(plane.cpu().numpy() if hasattr(plane, "is_cuda") else _host_array(plane))
+    if t.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+        t = t.astype(np.float64)
+    return t.ctypes.data, (_lib.F32 if t.dtype == np.float32 else _lib.F64), tuple(t.shape), t
 
 
 # ---- the device plan --------------------------------------------------------------------------------------------------------
@@ -120,6 +145,64 @@ class DhPlan(_Plan):
         if int(cnt.value) != k:
             raise _lib.XdemHipError(f"xdemhip_dh_values returned {cnt.value} values, expected {k}")
         return (dh, col, row) if coords else dh
+
+    # ---- variables of the bias corrections (csrc/bincorr.hip; the sources are made by xdem_amd.bincorr) ----
+    def _on_device(self) -> bool:
+        return getattr(self, "_keep", None) is not None
+
+    def _plane(self, plane):
+        """A variable plane on the plan's grid, in the plan's memory space: (pointer, dtype code, the array kept alive)."""
+        ptr, code, shape, t = plane_in_space(plane, self._keep[0].device if self._on_device() else None)
+        if shape != tuple(self.shape):
+            raise ValueError(f"a bias variable has shape {shape}, the rasters {tuple(self.shape)}")
+        return ptr, code, t
+
+    def restrict_finite(self, plane) -> int:
+        """Narrow the valid pixels to those where ``plane`` (H x W) is finite -- upstream's valid mask of a bias correction is
+        ``inlier & finite(ref) & finite(tba) & finite(every variable)`` (base.py:653-661).  Before ``subsample`` / ``values`` only
+        (``xdemhip_dh_restrict_finite``).  Returns the new count."""
+        ptr, code, keep = self._plane(plane)
+        nv = ctypes.c_int64()
+        self.ctx.check(self.ctx._L.xdemhip_dh_restrict_finite(self.handle, ptr, code, _lib.DEVICE if self._on_device() else _lib.HOST,
+                                                              ctypes.byref(nv)))
+        del keep
+        self.n_valid = self.n_selected = int(nv.value)
+        return self.n_valid
+
+    def var_columns(self, sources: list):
+        """dh (plan dtype) and the value of every variable of ``sources`` (``_lib.VarSrc`` descriptions, their planes made by
+        ``_plane``) at the selected pixels in raster order (``xdemhip_dh_var_columns``): NumPy columns for a plan made of NumPy
+        rasters, 1-D CUDA tensors for a plan made of CUDA tensors -- those go into ``nd_binning`` without a host round trip.  A
+        plane's column has the plane's dtype, the rotated coordinate is float64, ref / tba have the plan's dtype."""
+        k = self.n_selected
+        if k == 0:
+            raise ValueError(NO_VALID)
+        n_var = len(sources)
+        dts = []
+        for s in sources:
+            if s.kind == _lib.VAR_PLANE:
+                dts.append(np.dtype(np.float32 if s.dtype == _lib.F32 else np.float64))
+            else:
+                dts.append(np.dtype(np.float64) if s.kind == _lib.VAR_ROTATED else np.dtype(self.dtype))
+        if self._on_device():
+            import torch
+
+            dev = self._keep[0].device
+            tdt = {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64}
+            dh = torch.empty(k, dtype=tdt[np.dtype(self.dtype)], device=dev)
+            cols = [torch.empty(k, dtype=tdt[d], device=dev) for d in dts]
+            ptrs, dh_ptr, space = [c.data_ptr() for c in cols], dh.data_ptr(), _lib.DEVICE
+        else:
+            dh = np.empty(k, dtype=self.dtype)
+            cols = [np.empty(k, dtype=d) for d in dts]
+            ptrs, dh_ptr, space = [c.ctypes.data for c in cols], dh.ctypes.data, _lib.HOST
+        arr = (_lib.VarSrc * max(n_var, 1))(*sources)
+        outs = (ctypes.c_void_p * max(n_var, 1))(*ptrs)
+        cnt = ctypes.c_int64()
+        self.ctx.check(self.ctx._L.xdemhip_dh_var_columns(self.handle, n_var, arr, dh_ptr, outs, space, ctypes.byref(cnt)))
+        if int(cnt.value) != k:
+            raise _lib.XdemHipError(f"xdemhip_dh_var_columns returned {cnt.value} values, expected {k}")
+        return dh, cols
 
     def shift_nmad(self, shift_x: float, shift_y: float, res, nfact: float = 1.4826) -> tuple[float, float, int]:
         """(median, nmad, count) of dh = ref - bilinear(tba)(row - shift_y / res_y, col + shift_x / res_x) over the selected pixels, the

@@ -28,6 +28,7 @@ from . import _lib
 from ._coregbase import NO_VALID, CoregPipeline, _Plan, _Step, apply_translation, draw, raster_pair  # noqa: F401
 from ._coregbase import subsample_ranks, subsample_valid_mask  # noqa: F401
 from .biascorr import Deramp, DhPlan, VerticalShift, _check_weights, polynomial_2d  # noqa: F401  (upstream's xdem.coreg offers them here)
+from .bincorr import BiasCorr, DirectionalBias, TerrainBias, rotated_x  # noqa: F401
 from .rigid import (LZD, apply_matrix, invert_matrix, matrix_from_translations_rotations,  # noqa: F401  (and these)
                     translations_rotations_from_matrix, _make_matrix_valid)
 from .icp import ICP, nearest  # noqa: F401

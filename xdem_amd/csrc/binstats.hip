@@ -20,6 +20,7 @@
 #include "common.h"
 #include "select.h"
 #include "select_run.h"
+#include "grid_interp.h"
 
 namespace xd {
 
@@ -132,12 +133,12 @@ __global__ __launch_bounds__(256) void absdev_kernel(const T* __restrict__ v, co
 // ---- multilinear interpolation on a regular grid (scipy.interpolate.RegularGridInterpolator, method="linear",
 // bounds_error=False, fill_value=None: linear extrapolation from the edge intervals; NaN in any coordinate -> NaN) ----
 struct GridDims {
-    int nd;
-    int n[BS_MAXDIM], off[BS_MAXDIM], stride[BS_MAXDIM];
+    GridShape s;
     const void* var[BS_MAXDIM];
     int var_f32[BS_MAXDIM];
 };
 
+// (the per-point arithmetic: grid_interp.h, shared with the fused correction pass of bincorr.hip)
 __global__ __launch_bounds__(256) void interp_grid_kernel(GridDims G, const double* __restrict__ axes, int n_axes_total,
                                                           const double* __restrict__ gv, int n_grid, int grid_in_lds, int64_t n,
                                                           double scale, double* __restrict__ out) {
@@ -150,37 +151,10 @@ __global__ __launch_bounds__(256) void interp_grid_kernel(GridDims G, const doub
     __syncthreads();
     const double* V = grid_in_lds ? vals : gv;
     for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (int64_t)gridDim.x * blockDim.x) {
-        int base = 0;
-        double y[BS_MAXDIM];
         bool isnan_any = false;
-#pragma unroll 1
-        for (int d = 0; d < G.nd; ++d) {
-            const double x = G.var_f32[d] ? (double)static_cast<const float*>(G.var[d])[p] : static_cast<const double*>(G.var[d])[p];
-            isnan_any |= (x != x);
-            const double* g = ax + G.off[d];
-            const int m = G.n[d];
-            // interval i with g[i] <= x < g[i+1], clipped to [0, m-2] (x == g[m-1] belongs to the last interval)
-            int lo = 0, hi = m - 1;
-            while (hi - lo > 1) {
-                const int mid = (lo + hi) >> 1;
-                if (g[mid] <= x) lo = mid; else hi = mid;
-            }
-            y[d] = (x - g[lo]) / (g[lo + 1] - g[lo]);
-            base += lo * G.stride[d];
-        }
-        // hypercube corners in itertools.product order (first dimension slowest), weights multiplied left to right
-        double value = 0.0;
-        const int corners = 1 << G.nd;
-        for (int c = 0; c < corners; ++c) {
-            double wgt = 1.0;
-            int idx = base;
-            for (int d = 0; d < G.nd; ++d) {
-                const int up = (c >> (G.nd - 1 - d)) & 1;
-                wgt = wgt * (up ? y[d] : (1.0 - y[d]));
-                idx += up * G.stride[d];
-            }
-            value = value + V[idx] * wgt;
-        }
+        const double value = grid_linear_eval<BS_MAXDIM>(G.s, ax, V, [&](int d) {
+            return G.var_f32[d] ? (double)static_cast<const float*>(G.var[d])[p] : static_cast<const double*>(G.var[d])[p];
+        }, &isnan_any);
         out[p] = isnan_any ? (double)NAN : scale * value;
     }
 }
@@ -476,17 +450,17 @@ int xdemhip_interp_grid_linear(xdemhip_ctx* ctx, int n_dims, const double* axes,
     XD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     GridDims G;
     memset(&G, 0, sizeof G);
-    G.nd = n_dims;
+    G.s.nd = n_dims;
     int tot = 0;
     int64_t ngrid = 1;
     for (int d = 0; d < n_dims; ++d) {
         if (n_axis[d] < 2) return xd_fail(ctx, XDEMHIP_EINVAL, "every grid axis needs at least 2 points");
         if (var_dtypes[d] != XDEMHIP_F32 && var_dtypes[d] != XDEMHIP_F64) return xd_fail(ctx, XDEMHIP_EINVAL, "bad variable dtype");
-        G.n[d] = n_axis[d]; G.off[d] = tot; tot += n_axis[d];
+        G.s.n[d] = n_axis[d]; G.s.off[d] = tot; tot += n_axis[d];
         ngrid *= n_axis[d];
         if (ngrid > (1 << 24)) return xd_fail(ctx, XDEMHIP_EUNSUPPORTED, "interpolation grid too large");
     }
-    for (int d = n_dims - 1, st = 1; d >= 0; --d) { G.stride[d] = st; st *= n_axis[d]; }
+    for (int d = n_dims - 1, st = 1; d >= 0; --d) { G.s.stride[d] = st; st *= n_axis[d]; }
     XdBuffers buf(ctx, "xdemhip_interp_grid_linear");
     for (int d = 0; d < n_dims; ++d) {
         G.var[d] = buf.input(vars[d], (size_t)n * (var_dtypes[d] == XDEMHIP_F32 ? 4 : 8), memspace);

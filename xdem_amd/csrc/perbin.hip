@@ -10,6 +10,7 @@
 // that overlap (a hand-made DataFrame): the product is walked in upstream's order per pixel and the last bin that writes wins,
 // as the overwriting masks do.  A NaN variable lies in no interval: NaN out.  HBM traffic: the L variables read once, 8 B out.
 #include "common.h"
+#include "perbin_locate.h"
 
 #include <math.h>
 
@@ -93,36 +94,14 @@ __global__ __launch_bounds__(256) void perbin_kernel(PbArgs a) {
         }
         double res[PB_U];
         if (DISJOINT) {
-            // sorted disjoint intervals: the only candidate is the last one whose left end is <= v.  Branch-free binary search
-            // with a wave-uniform trip count (a NaN compares false everywhere and finds none).
+            // sorted disjoint intervals: one containing interval per variable (perbin_locate.h, shared with the fused correction pass)
             int64_t idx[PB_U];
             bool in[PB_U];
 #pragma unroll
             for (int u = 0; u < PB_U; ++u) { idx[u] = 0; in[u] = true; }
 #pragma unroll
             for (int k = 0; k < NV; ++k) {
-                if (k < a.n_var) {
-                    const int base = a.off[k], n = a.n_int[k];
-                    int top = 1;
-                    while (top <= n) top <<= 1;   // (uniform)
-                    int pos[PB_U];
-#pragma unroll
-                    for (int u = 0; u < PB_U; ++u) pos[u] = 0;
-                    for (int len = top >> 1; len > 0; len >>= 1) {
-#pragma unroll
-                        for (int u = 0; u < PB_U; ++u) {
-                            const int cand = pos[u] + len;
-                            const int at = cand <= n ? cand : n;   // (stay inside the table; the result is discarded when cand > n)
-                            pos[u] = (cand <= n && lo_of(base + at - 1) <= v[u][k]) ? cand : pos[u];
-                        }
-                    }
-#pragma unroll
-                    for (int u = 0; u < PB_U; ++u) {
-                        const int j = pos[u] - 1;
-                        in[u] = in[u] && j >= 0 && v[u][k] < hi_of(base + (j < 0 ? 0 : j));
-                        idx[u] = idx[u] * n + (j < 0 ? 0 : j);
-                    }
-                }
+                if (k < a.n_var) pb_locate<PB_U>([&](int u) { return v[u][k]; }, a.off[k], a.n_int[k], lo_of, hi_of, in, idx);
             }
 #pragma unroll
             for (int u = 0; u < PB_U; ++u) {

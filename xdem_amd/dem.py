@@ -128,11 +128,10 @@ class DEM:
         """Align this DEM to ``reference_elev`` (same grid) with ``coreg_method`` (upstream requires one and names Nuth and
         Kaab as the default in its docstring: ``None`` means ``NuthKaab(subsample=1)`` here).  ``random_state`` seeds the
         subsampling; ``resample`` (keyword, default True) as upstream.  ``coreg_method``: ``NuthKaab``, ``DhMinimize``, ``LZD``, ``ICP``,
-        ``CPD``, ``Deramp``, ``VerticalShift`` or a ``CoregPipeline`` of them; ``bias_vars`` belongs to bias corrections with explicit variables, which are
-        not part of this package."""
+        ``CPD``, ``Deramp``, ``VerticalShift``, ``BiasCorr``, ``DirectionalBias``, ``TerrainBias`` or a ``CoregPipeline`` of them;
+        ``bias_vars`` ({name: array on this grid}) goes to the steps that take variables (``BiasCorr``) and is refused where the
+        method has none."""
         resample = kwargs.pop("resample", True)
-        if bias_vars is not None:
-            raise NotImplementedError("bias_vars is only used by bias-correction methods (not part of xdem_amd).")
         if random_state is not None:
             kwargs["random_state"] = random_state
         method = coreg_method if coreg_method is not None else _coreg.NuthKaab(subsample=1)
@@ -143,12 +142,20 @@ class DEM:
         mask = None if inlier_mask is None else np.asarray(getattr(inlier_mask, "data", inlier_mask), dtype=bool)
         # (a step that rotates works about a centroid in the grid's coordinates: it gets the transform; the others read the resolution)
         steps = getattr(method, "pipeline", [method])
+        vars_kw = {}
+        if bias_vars is not None:
+            if not any(getattr(step, "_needs_vars", False) for step in steps):
+                raise NotImplementedError("bias_vars is only used by bias-correction methods that take variables (BiasCorr); "
+                                          "no step of this method does.")
+            vars_kw = {"bias_vars": {k: np.asarray(getattr(v, "data", v)) for k, v in bias_vars.items()}}
         if any(getattr(step, "_needs_transform", False) for step in steps):
             kwargs["transform"] = self.transform
-        method.fit(reference_elev.data, self.data, mask, resolution=self.res, **kwargs)
+        method.fit(reference_elev.data, self.data, mask, resolution=self.res, **vars_kw, **kwargs)
         # array interface with transform=: for resample=False the horizontal shift moves the geotransform and only the
         # vertical shift touches the data (xdem/coreg/base.py:1567-1570, _apply_matrix_rst case 2)
-        out, out_transform = method.apply(self.data, resample=resample, transform=self.transform)
+        if any(isinstance(step, _coreg.BiasCorr) for step in steps):   # (these read the resolution at apply too: rotated coordinate, terrain)
+            vars_kw["resolution"] = self.res
+        out, out_transform = method.apply(self.data, resample=resample, transform=self.transform, **vars_kw)
         return DEM(out, out_transform, self.crs, self.nodata)
 
     # ---- uncertainty forwarder (xdem/dem.py:667-780) ---------------------------------------------------------------

@@ -1041,6 +1041,7 @@ def _scipy_edges(sample_cols: list[np.ndarray], mins: list[float], maxs: list[fl
             e = np.linspace(smin, smax, int(bins[i]) + 1, dtype=edges_dtype)
         else:
             e = np.asarray(np.asarray(bins[i], float), edges_dtype)
+            len(e)   # (a 0-d array -- BiasCorr's dict of INTEGER bin sizes -- is no scalar to SciPy either: its TypeError, `nbin = len(edges) + 1`)
         d = np.diff(e)
         dmin = d.min()
         if dmin == 0:
@@ -1050,11 +1051,34 @@ def _scipy_edges(sample_cols: list[np.ndarray], mins: list[float], maxs: list[fl
     return edges, decimals, edges_dtype
 
 
-class BinStatsPlan:
-    """Device-resident values + explanatory variables of one ``nd_binning`` call (``xdemhip_binstats``)."""
+class _DeviceColumn:
+    """A 1-D float32 / float64 CUDA tensor as a column of ``BinStatsPlan``: what the plan reads of a NumPy column (``dtype``,
+    ``size``) without the values leaving the device; ``host()`` fetches them once if a host-evaluated statistic needs them."""
 
-    def __init__(self, values: np.ndarray, list_var: list[np.ndarray], ctx: _lib.Context | None = None):
-        self.ctx = ctx or _lib.default_context()
+    def __init__(self, tensor):
+        import torch
+
+        if not (tensor.is_cuda and tensor.dim() == 1 and tensor.is_contiguous() and tensor.dtype in (torch.float32, torch.float64)):
+            raise ValueError("device columns must be contiguous 1-D float32 / float64 CUDA tensors")
+        self.tensor = tensor
+        self.dtype = np.dtype(np.float32 if tensor.dtype == torch.float32 else np.float64)
+        self.size = int(tensor.numel())
+        self._host = None
+
+    def host(self) -> np.ndarray:
+        if self._host is None:
+            self._host = self.tensor.cpu().numpy()
+        return self._host
+
+
+class BinStatsPlan:
+    """Device-resident values + explanatory variables of one ``nd_binning`` call (``xdemhip_binstats``).  ``values`` / ``list_var``:
+    NumPy arrays (uploaded), or 1-D CUDA tensors of one length (read in place and kept alive by the plan: the columns a dh plan
+    gathers on the device, ``DhPlan.var_columns``)."""
+
+    def __init__(self, values, list_var: list, ctx: _lib.Context | None = None):
+        device = hasattr(values, "is_cuda")
+        self.ctx = ctx or (_lib.default_context(values.device.index) if device else _lib.default_context())
         self.ctx.adopt(self)
         L = self.ctx._L
 
@@ -1064,18 +1088,34 @@ class BinStatsPlan:
                 a = a.astype(np.float64)
             return np.ascontiguousarray(a)
 
-        self.values = prep(values)
-        self.vars = [prep(v) for v in list_var]
-        n = self.values.size
+        if device:
+            if not all(hasattr(v, "is_cuda") for v in list_var):
+                raise ValueError("values on the device need every explanatory variable on the device")
+            import torch
+
+            torch.cuda.current_stream(values.device).synchronize()   # (the library reads the columns on the context's stream)
+            self._dev_values = _DeviceColumn(values)
+            self.vars = [_DeviceColumn(v) for v in list_var]
+            n = self._dev_values.size
+            space = _lib.DEVICE
+            ptr = lambda a: a.tensor.data_ptr()  # noqa: E731
+        else:
+            self._dev_values = None
+            self._values = prep(values)
+            self.vars = [prep(v) for v in list_var]
+            n = self._values.size
+            space = _lib.HOST
+            ptr = lambda a: a.ctypes.data  # noqa: E731
+        first = self._dev_values if device else self._values
         if any(v.size != n for v in self.vars):
             raise ValueError("values and explanatory variables must have the same number of elements")
+        self.size = n
         h = ctypes.c_void_p()
         code = lambda a: _lib.F32 if a.dtype == np.float32 else _lib.F64  # noqa: E731
-        self.ctx.check(L.xdemhip_binstats_create(self.ctx.handle, self.values.ctypes.data, code(self.values), n, _lib.HOST,
-                                                 ctypes.byref(h)))
+        self.ctx.check(L.xdemhip_binstats_create(self.ctx.handle, ptr(first), code(first), n, space, ctypes.byref(h)))
         self.handle = h
         for v in self.vars:
-            rc = L.xdemhip_binstats_add_var(self.handle, v.ctypes.data, code(v), _lib.HOST)
+            rc = L.xdemhip_binstats_add_var(self.handle, ptr(v), code(v), space)
             if rc < 0:
                 self.ctx.check(rc)
         nv = ctypes.c_int64()
@@ -1085,6 +1125,11 @@ class BinStatsPlan:
         self.ctx.check(L.xdemhip_binstats_finalize(self.handle, ctypes.byref(nv), vmin.ctypes.data_as(dp), vmax.ctypes.data_as(dp)))
         self.n_valid = int(nv.value)
         self.var_min, self.var_max = vmin, vmax
+
+    @property
+    def values(self) -> np.ndarray:
+        """The values on the host (device columns: fetched on first use -- only a host-evaluated statistic asks)."""
+        return self._values if self._dev_values is None else self._dev_values.host()
 
     def run(self, var_ids: list[int], bins: list, want_nmad: bool = True, nfact: float = 1.4826, ranges=None):
         """One binning over the given variables -> (count int64, median f64, nmad f64 | None, edges) in C order.  ``ranges`` =
@@ -1111,7 +1156,7 @@ class BinStatsPlan:
     def bin_numbers(self) -> np.ndarray:
         """uint16 flat bin number (C order over the dimensions of the last ``run``) of every sample, 0xFFFF = dropped by the joint
         finiteness filter or in no bin: for statistics evaluated on the host (``xdemhip_binstats_bin_numbers``)."""
-        out = np.empty(self.values.size, dtype=np.uint16)
+        out = np.empty(self.size, dtype=np.uint16)
         if self.n_valid > 0:
             self.ctx.check(self.ctx._L.xdemhip_binstats_bin_numbers(self.handle, out.ctypes.data))
         else:
@@ -1142,7 +1187,9 @@ def nd_binning(values, list_var, list_var_names, list_var_bins=None, statistics=
     statistic upstream would pass on to SciPy -- ``"mean"`` / ``"std"`` / ``"sum"`` / ``"min"`` / ``"max"``, the NumPy function
     objects of those names, any callable of a 1-D array (``np.nanmean``, ``np.nanstd``, a lambda ...) -- is applied on the HOST to
     the values of each bin, from the bin numbers the device computed (``xdemhip_binstats_bin_numbers``), exactly as
-    ``scipy.stats.binned_statistic_dd`` does (``xdem_amd/_binstat_host.py``): a Python callable cannot run anywhere else.  ``list_ranges`` goes to every binning exactly as
+    ``scipy.stats.binned_statistic_dd`` does (``xdem_amd/_binstat_host.py``): a Python callable cannot run anywhere else.  ``values``
+    and ``list_var`` may also be 1-D CUDA tensors of one length (the columns ``DhPlan.var_columns`` gathers): they are binned in place,
+    the DataFrame is the one the same values give from the host.  ``list_ranges`` goes to every binning exactly as
     upstream hands it to SciPy's ``range=`` (a (start, stop) pair or a one-element list of pairs for ONE variable; with several
     variables SciPy's own ValueError / TypeError comes out, as upstream).
     """
@@ -1171,7 +1218,10 @@ def nd_binning(values, list_var, list_var_names, list_var_bins=None, statistics=
         kinds.append(_GPU_STATS[name] if on_device else None)
     want_nmad = "nmad" in kinds
 
-    plan = BinStatsPlan(np.asarray(values), [np.asarray(v) for v in list_var], ctx)
+    if hasattr(values, "is_cuda"):   # device columns (a dh plan's gather): binned where they are
+        plan = BinStatsPlan(values, list(list_var), ctx)
+    else:
+        plan = BinStatsPlan(np.asarray(values), [np.asarray(v) for v in list_var], ctx)
     try:
         def stats_df(var_ids, bins, one_d=False):
             rng = None if list_ranges is None else _scipy_range(list_ranges, len(var_ids), one_d)
@@ -1304,6 +1354,52 @@ def _edge_as_numpy_compares(dtype: np.dtype, edge) -> float:
     return float(np.asarray(edge).astype(np.result_type(dtype, edge)))
 
 
+def _perbin_tables(df, var_dtypes: list, list_var_names: list, statistic_name: str, min_count: int | None):
+    """The host tables of ``xdemhip_perbin_lookup`` for the rows of `df` that bin exactly `list_var_names`, whose arrays have
+    `var_dtypes`: (intervals per variable, left ends, right ends -- as NumPy compares them against those dtypes --, the statistic
+    and the decision byte per bin of the product of the intervals, whether the intervals are disjoint, the count column)."""
+    import pandas as pd
+
+    rows = df.copy()
+    if "nd" in rows.columns:
+        rows = rows[rows.nd == len(list_var_names)]
+    for name in list_var_names:
+        cells = rows[name].values
+        if any(isinstance(x, pd.Interval) for x in cells):
+            continue
+        parsed = [_pandas_str_to_interval(x) for x in cells]
+        if not any(isinstance(x, pd.Interval) for x in parsed):
+            raise ValueError("The bin intervals of the dataframe should be pandas.Interval.")
+        rows[name] = parsed
+    n_var = len(list_var_names)
+    uniques = [np.unique(rows[name].values) for name in list_var_names]
+    counts = [len(u) for u in uniques]
+    n_bins = int(np.prod(counts, dtype=np.int64)) if all(counts) else 0
+    count_col = rows["count"].values if "count" in rows.columns else None
+    if n_bins == 0:
+        return counts, None, None, None, None, True, count_col
+    left = np.array([_edge_as_numpy_compares(var_dtypes[k], iv.left) for k in range(n_var) for iv in uniques[k]], dtype=np.float64)
+    right = np.array([_edge_as_numpy_compares(var_dtypes[k], iv.right) for k in range(n_var) for iv in uniques[k]], dtype=np.float64)
+    # the bin table over the product of the intervals (itertools.product order); the FIRST row of a bin counts (`.values[0]`)
+    table = np.full(n_bins, np.nan, dtype=np.float64)
+    decided = np.full(n_bins, 2, dtype=np.uint8)   # 2 = the DataFrame has no row for this bin
+    place = [{iv: j for j, iv in enumerate(u)} for u in uniques]
+    stat_col = rows[statistic_name].values
+    cols = [rows[name].values for name in list_var_names]
+    for r in range(len(rows)):
+        flat = 0
+        for k in range(n_var):
+            flat = flat * counts[k] + place[k][cols[k][r]]
+        if decided[flat] != 2:
+            continue
+        table[flat] = stat_col[r]
+        if min_count is None:
+            continue   # stays "undecidable": upstream's `count > None` raises as soon as a pixel lies in a bin
+        decided[flat] = 1 if count_col[r] > min_count else 0
+    disjoint = all(all(uniques[k][j].right <= uniques[k][j + 1].left for j in range(counts[k] - 1)) for k in range(n_var))
+    return counts, left, right, table, decided, disjoint, count_col
+
+
 def get_perbin_nd_binning(df, list_var, list_var_names, statistic=np.nanmedian, min_count: int | None = 0,
                           ctx: _lib.Context | None = None) -> np.ndarray:
     """Per-pixel value of a binned statistic: every element of the explanatory variables receives the statistic of the bin of
@@ -1340,21 +1436,10 @@ def get_perbin_nd_binning(df, list_var, list_var_names, statistic=np.nanmedian, 
         raise ValueError('Statistic "count" is not in the provided dataframe, necessary to use the min_count argument.')
     if df.empty:
         raise ValueError("Dataframe is empty.")
-    rows = df.copy()
-    if "nd" in rows.columns:
-        rows = rows[rows.nd == len(list_var_names)]
-    for name in list_var_names:
-        cells = rows[name].values
-        if any(isinstance(x, pd.Interval) for x in cells):
-            continue
-        parsed = [_pandas_str_to_interval(x) for x in cells]
-        if not any(isinstance(x, pd.Interval) for x in parsed):
-            raise ValueError("The bin intervals of the dataframe should be pandas.Interval.")
-        rows[name] = parsed
     n_var = len(list_var)
     if n_var > 8:
         raise NotImplementedError("get_perbin_nd_binning: at most 8 explanatory variables")
-    arrays, uniques = [], []
+    arrays = []
     for k, name in enumerate(list_var_names):
         a = np.ascontiguousarray(list_var[k])
         if a.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
@@ -1362,32 +1447,11 @@ def get_perbin_nd_binning(df, list_var, list_var_names, statistic=np.nanmedian, 
         if a.shape != shape:
             raise ValueError(f"variable {name!r} has shape {a.shape}, the first variable {shape}")   # (upstream: a boolean-index error)
         arrays.append(a.reshape(-1))
-        uniques.append(np.unique(rows[name].values))
-    counts = [len(u) for u in uniques]
-    n_bins = int(np.prod(counts, dtype=np.int64)) if all(counts) else 0
+    counts, left, right, table, decided, disjoint, count_col = _perbin_tables(df, [a.dtype for a in arrays], list_var_names, statistic_name,
+                                                                              min_count)
     out = np.full(int(np.prod(shape, dtype=np.int64)), np.nan, dtype=np.float64)
-    if n_bins == 0 or out.size == 0:
+    if table is None or out.size == 0:
         return out.reshape(shape)
-    left = np.array([_edge_as_numpy_compares(arrays[k].dtype, iv.left) for k in range(n_var) for iv in uniques[k]], dtype=np.float64)
-    right = np.array([_edge_as_numpy_compares(arrays[k].dtype, iv.right) for k in range(n_var) for iv in uniques[k]], dtype=np.float64)
-    # the bin table over the product of the intervals (itertools.product order); the FIRST row of a bin counts (`.values[0]`)
-    table = np.full(n_bins, np.nan, dtype=np.float64)
-    decided = np.full(n_bins, 2, dtype=np.uint8)   # 2 = the DataFrame has no row for this bin
-    place = [{iv: j for j, iv in enumerate(u)} for u in uniques]
-    stat_col = rows[statistic_name].values
-    count_col = rows["count"].values if "count" in rows.columns else None
-    cols = [rows[name].values for name in list_var_names]
-    for r in range(len(rows)):
-        flat = 0
-        for k in range(n_var):
-            flat = flat * counts[k] + place[k][cols[k][r]]
-        if decided[flat] != 2:
-            continue
-        table[flat] = stat_col[r]
-        if min_count is None:
-            continue   # stays "undecidable": upstream's `count > None` raises as soon as a pixel lies in a bin (below)
-        decided[flat] = 1 if count_col[r] > min_count else 0
-    disjoint = all(all(uniques[k][j].right <= uniques[k][j + 1].left for j in range(counts[k] - 1)) for k in range(n_var))
     ctx = ctx or _lib.default_context()
     ptrs = (ctypes.c_void_p * n_var)(*[a.ctypes.data for a in arrays])
     dts = (ctypes.c_int * n_var)(*[_lib.F32 if a.dtype == np.float32 else _lib.F64 for a in arrays])

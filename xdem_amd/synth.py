@@ -80,3 +80,60 @@ def c5_variogram_blocks(device, runs: int = 100, samples: int = 9091, size: int 
     blocks = ss.equidistant_blocks_from_raster(None, 1.0, runs, samples, ratio, rng, values_of=values_of, shape=(size, size))
     edges = np.geomspace(math.sqrt(2.0), maxdist, 50)
     return blocks, edges
+
+
+def _hash01(n: int, salt: int) -> np.ndarray:
+    """n reproducible numbers in [0, 1): a 64-bit integer mix of the index (wrapping uint64 arithmetic, exact on every platform and
+    NumPy version -- unlike a generator's stream, which NumPy does not pin across releases)."""
+    with np.errstate(over="ignore"):
+        x = (np.arange(n, dtype=np.uint64) + np.uint64(salt)) * np.uint64(0x9E3779B97F4A7C15)
+        x ^= x >> np.uint64(29)
+        x *= np.uint64(0xBF58476D1CE4E5B9)
+        x ^= x >> np.uint64(32)
+    return (x >> np.uint64(11)).astype(np.float64) / float(2**53)
+
+
+def bias_case(H: int, W: int, dtype=np.float32) -> dict:
+    """Inputs of the bias-correction fixtures and tests (tools/gen_golden_bincorr.py records the reference's results on exactly
+    these): a DEM pair whose difference depends on three variables, NaNs in both rasters and in one variable plane, a patchy
+    inlier mask, and the planes the corrections are applied with -- values exactly on bin edges, on the rightmost edge, outside the
+    binned range and NaN.  Only exactly rounded operations (+, -, *, /, sqrt) on hashed integers: the same bits everywhere, so
+    nothing of it needs storing.  The float64 pair is the float32 pair widened and perturbed below float32 resolution."""
+    n = H * W
+    row, col = np.divmod(np.arange(n), W)
+    u = [_hash01(n, 1000 * k + 17) for k in range(8)]
+    v1 = (10.0 * u[0]).astype(np.float32)                                   # uniform in [0, 10)
+    v2 = 2.0 * (0.7 * u[1] + 0.3 * (row / max(H - 1, 1))) - 1.0              # float64 in [-1, 1)
+    v3 = (30.0 * np.sqrt(u[2])).astype(np.float32)
+    v3[(v3 >= 10.0) & (v3 < 14.0)] += np.float32(4.0)                       # a gap: empty bins
+    ref = 800.0 + 0.5 * col + 0.3 * row + 25.0 * (u[3] - 0.5)
+    bias = 0.3 * v1.astype(np.float64) - 0.02 * v1.astype(np.float64) ** 2 + 1.5 * v2 + 0.05 * v3.astype(np.float64)
+    tba = ref - bias + 0.4 * (u[4] - 0.5)
+    ref32, tba32 = ref.astype(np.float32), tba.astype(np.float32)
+    if np.dtype(dtype) == np.float64:
+        ref_o, tba_o = ref32.astype(np.float64) + 0.1, tba32.astype(np.float64) * 1.000000123
+    else:
+        ref_o, tba_o = ref32, tba32
+    ref_o[u[5] < 0.03] = np.nan
+    tba_o[u[6] < 0.03] = np.nan
+    v1[u[7] < 0.02] = np.nan
+    inlier = (_hash01(n, 9001) >= 0.02)
+    out = {"v1": v1.reshape(H, W), "v2": v2.reshape(H, W), "v3": v3.reshape(H, W)}
+    ref_o, tba_o, inlier = ref_o.reshape(H, W), tba_o.reshape(H, W), inlier.reshape(H, W)
+    if H > 12 and W > 30:
+        tba_o[5:9, 20:31] = np.nan
+        inlier[H // 2:H // 2 + 6, W // 3:W // 3 + 15] = False
+    # the planes of apply: the fit's planes with special values planted
+    a1, a2, a3 = out["v1"].copy().reshape(-1), out["v2"].copy().reshape(-1), out["v3"].copy().reshape(-1)
+    k = np.arange(n)
+    for value, phase in ((2.5, 0), (5.0, 1), (10.0, 2), (-3.0, 3), (14.0, 4), (0.0, 5), (7.5, 6)):
+        a1[k % 37 == phase] = np.float32(value)
+    a2[k % 41 == 0] = 1.0
+    a2[k % 41 == 1] = -1.0
+    a2[k % 41 == 2] = 1.0 / 3.0
+    a2[k % 41 == 3] = 2.5
+    a2[k % 43 == 7] = np.nan
+    a3[k % 47 == 0] = np.float32(12.0)    # inside the gap
+    a3[k % 47 == 1] = np.float32(45.0)    # beyond the binned range
+    out.update(ref=ref_o, tba=tba_o, inlier=inlier, a1=a1.reshape(H, W), a2=a2.reshape(H, W), a3=a3.reshape(H, W))
+    return out
