@@ -720,6 +720,45 @@ int xdemhip_cov_double_sum(xdemhip_ctx* ctx, const double* ax, const double* ay,
                            const double* by, const double* be, int64_t nb, int n_models, const int* model_type, const double* range,
                            const double* psill, const double* smooth, double* out_sum, int memspace);
 
+/* ---- hypsometric binning and gap filling (xdem/volume.py) -----------------------------------------------------------
+ * A plan over one (dDEM, reference DEM) pair of n pixels, float32 or float64 each, with an optional int32 label map (a glacier
+ * index map: label 0 = no glacier, labels in [1, 2^20)) OR an optional byte mask (non-zero = "label 1"); neither: every pixel has
+ * label 1.  Host arrays are uploaded once and kept; device arrays are used in place and must outlive the plan.  An INLIER is a
+ * pixel of a non-zero label with a finite dDEM and a finite reference.
+ *  label_stats  one pass: for every label that occurs (at most `cap`, in no particular order) its id, counts[2] = (pixels, inliers)
+ *               and extremes[4] = min, max of the reference over its pixels with a finite reference, min, max over its inliers
+ *               (NaN where there is none).  n_bad_labels: pixels whose label lies outside [0, 2^20); n_ref_invalid: pixels of the
+ *               whole raster with a non-finite reference.
+ *  segments     for the n_kept labels `ids` (rank r = position in the list), each with its own nb + 1 increasing bin edges
+ *               (edges[r * (nb + 1) ..]): every inlier's bin i = np.digitize(ref, edges) (right=False, the comparison in float64
+ *               on the exactly widened values), kept for 1 <= i <= nb; group = r * nb + (i - 1).  Per group: the count, the exact
+ *               median of the dDEM (np.median: the mean of the two middle values in the dDEM's dtype for an even count; NaN for an
+ *               empty group) and, with want_std, np.nanstd (ddof 0) in float64 -- the mean, then the squared deviations, both summed
+ *               in one fixed order over the segment sorted by value: the same bits from every run.
+ *  groups       the group of every pixel in the last segments call (-1: in none), for statistics the device does not evaluate.
+ *  fill         out[p] = fill(p) ? model_r(ref[p]) : ddem[p], r = rank of the pixel's label in `ids`; model_r = SciPy's
+ *               interp1d(xs[r * m ..], ys[r * m ..], kind="linear", fill_value="extrapolate") in float64.  mode 0: fill = label
+ *               kept and dDEM not finite; mode 1: fill = label kept.  round_to_ref: the model's value is rounded to the reference's
+ *               dtype before it is stored (hypsometric_interpolation writes it into such a plane).  out_dtype: the dDEM's dtype, or
+ *               float64.  `out` in `memspace`.
+ * A context serialises these calls like all others. */
+typedef struct xdemhip_hypso xdemhip_hypso;
+int xdemhip_hypso_create(xdemhip_ctx* ctx, const void* ddem, int ddem_dtype, const void* ref, int ref_dtype, const int32_t* labels,
+                         const unsigned char* mask, int64_t n, int memspace, xdemhip_hypso** out);
+int xdemhip_hypso_label_stats(xdemhip_hypso* plan, int64_t cap, int32_t* ids, int64_t* counts, double* extremes, int64_t* n_found,
+                              int64_t* n_bad_labels, int64_t* n_ref_invalid);
+int xdemhip_hypso_segments(xdemhip_hypso* plan, int n_kept, const int32_t* ids, int nb, const double* edges, int want_std,
+                           int64_t* counts, double* medians, double* stds);
+int xdemhip_hypso_groups(xdemhip_hypso* plan, int32_t* groups_out, int memspace);
+int xdemhip_hypso_fill(xdemhip_hypso* plan, int mode, int n_kept, const int32_t* ids, int m, const double* xs, const double* ys,
+                       int round_to_ref, void* out, int out_dtype, int memspace);
+void xdemhip_hypso_destroy(xdemhip_hypso* plan);
+/* calculate_hypsometry_area (volume.py:239-299): counts[i] = pixels whose elevation e lies in [edges[i], edges[i + 1]) -- the last
+ * bin closed on the right, np.histogram -- with e = ref (timeframe 0), ref - f(ref) (1) or ref - f(ref) / 2 (2) in float64,
+ * f = interp1d(xs, ys, fill_value="extrapolate") of m points. */
+int xdemhip_hypso_area(xdemhip_ctx* ctx, const void* ref, int dtype, int64_t n, int timeframe, int m, const double* xs,
+                       const double* ys, int nb, const double* edges, int64_t* counts, int memspace);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,7 +10,9 @@
  *   "nk_narrow"          -1 (default) sample brackets of the one-pass step narrowed by the measured rank offsets, 0 / 1 / 2 fixed.
  *   "vario_grid"         1 (default) raster-sampled points run the integer-lattice pair kernels, 0 always the float64-coordinate ones.
  *   "vario_runs"         1 (default) run-length counting pass of the exact-Dowd route on the Morton-ordered copy, 0 per-pair counters.
- *   "vario_sort"         1 (default) the host side uploads a Morton-ordered copy of every pair block, 0 one copy in the caller's order. */
+ *   "vario_sort"         1 (default) the host side uploads a Morton-ordered copy of every pair block, 0 one copy in the caller's order.
+ *   "hypso_seg_lds"      0 (default: 8192) the longest segment of xdemhip_hypso_segments that one workgroup sorts in LDS; a longer one takes
+ *                        the radix selection over its slice of global memory (1 .. 16384: a test sends a 40-value segment down it). */
 #pragma once
 #include "xdemhip.h"
 #ifdef __cplusplus

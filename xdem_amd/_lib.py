@@ -229,6 +229,18 @@ def lib() -> ctypes.CDLL:
                                                ctypes.c_void_p, ctypes.c_int]
         L.xdemhip_poly2d_apply.argtypes = [c_ctx, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, c_dp,
                                            ctypes.c_int, ctypes.c_void_p, ctypes.c_int]
+        c_i32p = ctypes.POINTER(ctypes.c_int32)
+        L.xdemhip_hypso_create.argtypes = [c_ctx, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]
+        L.xdemhip_hypso_label_stats.argtypes = [ctypes.c_void_p, ctypes.c_int64, c_i32p, c_i64p, c_dp, c_i64p, c_i64p, c_i64p]
+        L.xdemhip_hypso_segments.argtypes = [ctypes.c_void_p, ctypes.c_int, c_i32p, ctypes.c_int, c_dp, ctypes.c_int, c_i64p, c_dp, c_dp]
+        L.xdemhip_hypso_groups.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+        L.xdemhip_hypso_fill.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_i32p, ctypes.c_int, c_dp, c_dp, ctypes.c_int,
+                                         ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
+        L.xdemhip_hypso_destroy.argtypes = [ctypes.c_void_p]
+        L.xdemhip_hypso_destroy.restype = None
+        L.xdemhip_hypso_area.argtypes = [c_ctx, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, c_dp, c_dp, ctypes.c_int,
+                                         c_dp, c_i64p, ctypes.c_int]
         _lib = L
         return L
 
@@ -497,7 +509,7 @@ class Context:
             self._L.xdemhip_device_free(self.handle, ctypes.c_void_p(p))
 
     TEST_SWITCHES = frozenset(("terrain_stream", "terrain_order", "terrain_ring_wait", "terrain_window_lds", "nk_narrow",
-                               "vario_grid", "vario_runs", "vario_sort"))
+                               "vario_grid", "vario_runs", "vario_sort", "hypso_seg_lds"))
 
     def set_option(self, name: str, value: int) -> None:
         """Option of the library (``xdemhip_set_option``: the fourteen names of include/xdemhip.h), e.g. ``("selection", 1)`` -- or,

@@ -137,3 +137,74 @@ def bias_case(H: int, W: int, dtype=np.float32) -> dict:
     a3[k % 47 == 1] = np.float32(45.0)    # beyond the binned range
     out.update(ref=ref_o, tba=tba_o, inlier=inlier, a1=a1.reshape(H, W), a2=a2.reshape(H, W), a3=a3.reshape(H, W))
     return out
+
+
+VOLUME_LABELS = {"plain": (3, 7, 77, 1000, (1 << 20) - 1), "tiny": 5, "no_valid": 11, "below_signal_coverage": 13,
+                 "below_interp_coverage": 17, "flat": 19, "on_edges": 23, "sparse_bins": 29}
+
+
+def volume_case(H: int, W: int, dtype=np.float32) -> dict:
+    """Inputs of the xdem_amd.volume fixtures and tests (tools/gen_golden_volume.py records the reference's results on exactly these):
+    a tilted reference DEM with relief (multiples of 1/8 m), a dDEM with an elevation trend and ties among its values, NaN voids and
+    a few +-inf, a copy of the reference with voids, and a glacier index map (VOLUME_LABELS): non-contiguous ids up to 2^20 - 1,
+    label 0, an outline of 6 pixels, one without a valid dDEM, one just below each coverage threshold (4 and 9 valid pixels of 100),
+    one of constant elevation, one whose elevations are the bin edges themselves, one that leaves bins with 0, 1, 2 and 3 samples.
+    Rasters too small for that layout (below 50 x 80) get runs of five labels along the flattened raster.  Only exactly rounded
+    operations on hashed integers: the same bits everywhere.  The float64 pair is the float32 pair widened and moved by multiples of
+    2^-10 / 2^-12, below what float32 resolves there."""
+    n = H * W
+    k = np.arange(n)
+    row, col = np.divmod(k, W)
+    u = [_hash01(n, 2000 * j + 31) for j in range(5)]
+    ref = (8000.0 + 64.0 * row + 16.0 * col + np.floor(240.0 * u[0])) / 8.0
+    ddem = -(ref - 1000.0) / 64.0 + (np.floor(64.0 * u[1]) - 32.0) / 16.0
+    if np.dtype(dtype) == np.float64:
+        ref = ref + np.floor(8.0 * u[3]) / 1024.0
+        ddem = ddem + np.floor(8.0 * u[4]) / 4096.0
+    finite_ddem = ddem.copy()
+    ddem[u[2] < 0.2] = np.nan
+    ddem[k % 997 == 3] = np.inf
+    ddem[k % 997 == 5] = -np.inf
+    ref, ddem, finite_ddem = ref.reshape(H, W), ddem.reshape(H, W), finite_ddem.reshape(H, W)
+    lab = np.zeros((H, W), dtype=np.int32)
+    if H >= 50 and W >= 80:
+        ddem[H // 4:H // 4 + 5, W // 5:W // 5 + 9] = np.nan
+        a, b, c = W // 3, 2 * W // 3, H // 2
+        lab[2:c, 2:a] = 3
+        lab[2:c, a + 2:b] = 7
+        lab[c + 2:H - 2, 2:a] = 77
+        lab[c + 2:H - 2, a + 2:b] = 1000
+        lab[2:H // 3, b + 2:W - 2] = (1 << 20) - 1
+        r0, xa, xb = H // 3 + 1, b + 2, b + 13
+
+        def place(label, r, x, h, w, ref_values=None, n_valid=None):
+            sl = (slice(r, r + h), slice(x, x + w))
+            lab[sl] = label
+            if ref_values is not None:
+                ref[sl] = np.asarray(ref_values, dtype=np.float64).reshape(h, w)
+            d = finite_ddem[sl].copy()
+            if n_valid is not None:
+                d.reshape(-1)[n_valid:] = np.nan
+            ddem[sl] = d
+
+        place(13, r0, xa, 10, 10, n_valid=4)
+        place(17, r0 + 11, xa, 10, 10, n_valid=9)
+        sparse = [1500.0, 1700.0, 1525.0, 1545.0, 1546.0, 1565.0, 1566.0, 1567.0] + [1620.0 + 2.5 * j for j in range(32)]
+        place(29, r0 + 22, xa, 4, 10, ref_values=sparse)
+        place(5, r0, xb, 2, 3)
+        place(11, r0 + 3, xb, 4, 5, n_valid=0)
+        place(19, r0 + 8, xb, 4, 5, ref_values=[1111.0] * 20)
+        place(23, r0 + 13, xb, 3, 7, ref_values=[1200.0 + 5.0 * j for j in range(21)])
+    else:
+        flat = lab.reshape(-1)
+        for label, lo, hi in ((3, n // 10, 4 * n // 10), (5, 4 * n // 10, 4 * n // 10 + 6), (7, 9 * n // 20, 13 * n // 20),
+                              (11, 13 * n // 20, 15 * n // 20), (1000, 15 * n // 20, n)):
+            flat[lo:hi] = label
+        ddem.reshape(-1)[13 * n // 20:15 * n // 20] = np.nan
+    ref_voids = ref.copy()
+    ref_voids.reshape(-1)[k % 211 == 7] = np.nan
+    mask = (lab == 3) | (lab == 7) | (lab == 77) | (lab == 1000)
+    if not (H >= 50 and W >= 80):
+        mask = lab > 0
+    dt = np.dtype(dtype)
+    return {"ddem": ddem.astype(dt), "ref": ref.astype(dt), "ref_voids": ref_voids.astype(dt), "labels": lab, "mask": mask}
