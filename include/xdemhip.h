@@ -477,6 +477,62 @@ int xdemhip_dh_lzd_values(xdemhip_dh_plan* plan, const double* transform6, const
 int xdemhip_apply_matrix_rst(xdemhip_ctx* ctx, const void* dem, int dtype, int64_t H, int64_t W, const double* transform6, const double* matrix16,
                              const double* centroid3_or_null, void* out, int memspace);
 
+/* ---- raster-point coregistration (csrc/ptsplan.hip) -------------------------------------------------------------------------------
+ * NuthKaab, DhMinimize and VerticalShift when one elevation dataset is a point cloud (xdem/coreg/affine.py:150-243 with
+ * base.py:624-706).  A raster-point plan holds one raster (H x W, `dtype`), an optional inlier mask (0 / 1 bytes), the north-up
+ * `transform6` and the cloud's columns x, y (float64) and z (`dtype`), n_pts values each, all in `memspace`; `pts_is_ref` says which side
+ * is the reference.  A point lies at (row, col) = ((y - f) / e - 0.5, (x - c) / a - 0.5), every float64 operation rounded on its own;
+ * the raster is sampled there with the bilinear taps and the nodata rule of the Nuth-Kaab step (option "nk_nan_rule": float64 weights,
+ * the value rounded to the raster dtype).
+ *
+ *  xdemhip_pts_create        the validity plane of the raster is inlier & isfinite(raster), with `with_nk_aux` also isfinite of the slope
+ *                            tangent and the aspect, built as xdemhip_nk_create builds them.  A point is valid iff x, y, z are finite and
+ *                            the tap rule accepts the validity plane -- 1 / NaN as float32 -- at its unshifted position
+ *                            (base.py:679, 697-701).  *n_valid = their number; the selection is every valid point, in cloud order.  With
+ *                            `with_nk_aux` slope tangent and aspect are interpolated at every point, once, at zero shift
+ *                            (affine.py:234-239: the aspect plane as it is, its 0 / 2 pi jump included).
+ *  xdemhip_pts_subsample     as xdemhip_dh_subsample: `k` distinct ranks among the valid points in cloud order; the selection becomes
+ *                            flatnonzero(valid)[ranks], kept in cloud order.
+ *  xdemhip_pts_selection     the cloud indexes of the selected points (host array of *count values; may be NULL for the count alone).
+ *  xdemhip_pts_nk_step       one iteration of Nuth & Kaab at the offsets (shift_x, shift_y), in georeferenced units, over the selected
+ *                            points: dh = z - raster(x + shift_x, y + shift_y) for a point reference, raster(x - shift_x, y - shift_y) - z
+ *                            for a raster reference (affine.py:217-231), the difference taken in the raster dtype, non-finite values
+ *                            dropped.  Outputs as xdemhip_nk_step: *vshift = np.nanmedian(dh) (exact), *n_valid = the points that have a dh,
+ *                            y = (dh - vshift) / slope_tan, SciPy's automatic bin edges from the aspect of those points (or the explicit
+ *                            ones), per-bin counts and exact medians, *y_mean / *y_std = np.nanmean / np.nanstd of y from float64 sums
+ *                            added in a fixed order (the same bits every call).  One fetch per step.  XDEMHIP_EINVAL ("The subsample
+ *                            contains no more valid values.") where no point is left.
+ *  xdemhip_pts_step_y        the y column of the last xdemhip_pts_nk_step: one value per selected point in cloud order (raster dtype), NaN where
+ *                            the point had no dh.  Upstream forms the start of its curve fit from np.nanmean(y) and np.nanstd(y) in y's own
+ *                            dtype (affine.py:381-384), NumPy's pairwise sums, which no sum in another order reproduces to the bit; the
+ *                            host takes them from this column.  XDEMHIP_EINVAL before a step or after the selection changed.
+ *  xdemhip_pts_set_bin_edges as xdemhip_nk_set_bin_edges (NULL: automatic edges again); at most 1024 bins.
+ *  xdemhip_pts_shift_nmad    as xdemhip_dh_shift_nmad with the dh above: median and NMAD at a trial shift, two exact selections, one fetch.
+ *  xdemhip_pts_shift_values  the dh column of the selected points in cloud order, NaN kept, and (non-NULL outputs, `with_nk_aux` plans) their
+ *                            slope tangent and aspect columns: what a host loss function or bin statistic receives.
+ *  xdemhip_apply_matrix_pts  p' = M (p - centroid) + centroid for n points (float64 columns), the products as explicit sums
+ *                            ((m0 x + m1 y) + m2 z) + m3 without contraction; no centroid is subtracted when it is NULL; `invert`: the
+ *                            inverse R^T, -(R^T t) is formed first, as xdemhip_apply_matrix_rst forms it.
+ * The gather of one evaluation walks the selected points in cloud order, or by raster tile of their unshifted position (test switch
+ * "pts_tile_order", include/xdemhip_test.h); it writes dh at the point's own index and every later pass reads cloud order, so both
+ * orders and every run return the same bits.  Single-process plans: a reduction hook on the context is suspended for the calls. */
+typedef struct xdemhip_pts_plan xdemhip_pts_plan;
+int xdemhip_pts_create(xdemhip_ctx* ctx, const void* raster, const uint8_t* inlier_mask_or_null, int dtype, int64_t H, int64_t W,
+                       const double* transform6, const double* x, const double* y, const void* z, int64_t n_pts, int pts_is_ref, int with_nk_aux,
+                       int memspace, xdemhip_pts_plan** out_plan, int64_t* n_valid);
+int xdemhip_pts_subsample(xdemhip_pts_plan* plan, const int64_t* ranks, int64_t k, int memspace, int64_t* n_selected);
+int xdemhip_pts_selection(xdemhip_pts_plan* plan, int64_t* idx_out_or_null, int64_t* count);
+int xdemhip_pts_set_bin_edges(xdemhip_pts_plan* plan, const double* edges_or_null, int n_edges, int decimal);
+int xdemhip_pts_nk_step(xdemhip_pts_plan* plan, double shift_x, double shift_y, int n_bins, double* vshift, int64_t* n_valid, double* y_mean,
+                        double* y_std, double* edges, int64_t* counts, double* medians);
+int xdemhip_pts_step_y(xdemhip_pts_plan* plan, void* y_out, int memspace, int64_t* count);
+int xdemhip_pts_shift_nmad(xdemhip_pts_plan* plan, double shift_x, double shift_y, double nfact, double* median, double* nmad, int64_t* count);
+int xdemhip_pts_shift_values(xdemhip_pts_plan* plan, double shift_x, double shift_y, void* dh_out, void* slope_out_or_null,
+                             void* aspect_out_or_null, int memspace, int64_t* count);
+void xdemhip_pts_destroy(xdemhip_pts_plan* plan);
+int xdemhip_apply_matrix_pts(xdemhip_ctx* ctx, const double* x, const double* y, const double* z, int64_t n, const double* matrix16,
+                             const double* centroid3_or_null, int invert, double* x_out, double* y_out, double* z_out, int memspace);
+
 /* ---- ICP coregistration (csrc/icp.hip) -----------------------------------------------------------------------------------------
  * The device passes of xdem.coreg.ICP (Besl & McKay 1992, Chen & Medioni 1992; xdem/coreg/affine.py:296-328, 773-1182) for two rasters
  * on one grid, and an exact 3-D nearest-neighbour search for any two clouds.  Everything is float64 without contraction.

@@ -270,7 +270,9 @@ class CoregPipeline(_Step):
                      z_name=z_name, weights=weights, subsample=subsample, random_state=random_state, **step_vars, **extra, **kwargs)
             if i != len(self.pipeline) - 1:
                 res = step.apply(elev=tba_mod, transform=out_transform, crs=crs, z_name=z_name, **step_vars, **extra)
-                if out_transform is None:
+                if hasattr(tba_mod, "geometry"):   # (a cloud on the to-be-aligned side is moved by the step's matrix and has no transform)
+                    tba_mod = res
+                elif out_transform is None:
                     tba_mod = res
                 else:
                     tba_mod, out_transform = res
@@ -288,11 +290,13 @@ class CoregPipeline(_Step):
             step_vars = {"bias_vars": self._parse_bias_vars(i, bias_vars)} if getattr(step, "_needs_vars", False) else {}
             res = step.apply(elev=elev_mod, transform=out_transform, crs=crs, z_name=z_name, resample=resample, resampling=resampling,
                              **step_vars, **kwargs)
-            if out_transform is None:
+            if hasattr(elev_mod, "geometry"):
+                elev_mod = res
+            elif out_transform is None:
                 elev_mod = res
             else:
                 elev_mod, out_transform = res
-        return _with_transform(elev_mod, out_transform)
+        return elev_mod if hasattr(elev_mod, "geometry") else _with_transform(elev_mod, out_transform)
 
     @property
     def is_affine(self) -> bool:

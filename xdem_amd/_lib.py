@@ -227,6 +227,22 @@ def lib() -> ctypes.CDLL:
         L.xdemhip_cpd_destroy.restype = None
         L.xdemhip_apply_matrix_rst.argtypes = [c_ctx, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, c_dp, c_dp, c_dp,
                                                ctypes.c_void_p, ctypes.c_int]
+        L.xdemhip_pts_create.argtypes = [c_ctx, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, c_dp,
+                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                         ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), c_i64p]
+        L.xdemhip_pts_subsample.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, c_i64p]
+        L.xdemhip_pts_selection.argtypes = [ctypes.c_void_p, ctypes.c_void_p, c_i64p]
+        L.xdemhip_pts_set_bin_edges.argtypes = [ctypes.c_void_p, c_dp, ctypes.c_int, ctypes.c_int]
+        L.xdemhip_pts_nk_step.argtypes = [ctypes.c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_int, c_dp, c_i64p, c_dp, c_dp, c_dp,
+                                          c_i64p, c_dp]
+        L.xdemhip_pts_step_y.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, c_i64p]
+        L.xdemhip_pts_shift_nmad.argtypes = [ctypes.c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_dp, c_dp, c_i64p]
+        L.xdemhip_pts_shift_values.argtypes = [ctypes.c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_void_p, ctypes.c_int, c_i64p]
+        L.xdemhip_pts_destroy.argtypes = [ctypes.c_void_p]
+        L.xdemhip_pts_destroy.restype = None
+        L.xdemhip_apply_matrix_pts.argtypes = [c_ctx, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, c_dp, c_dp,
+                                               ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
         L.xdemhip_poly2d_apply.argtypes = [c_ctx, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, c_dp,
                                            ctypes.c_int, ctypes.c_void_p, ctypes.c_int]
         c_i32p = ctypes.POINTER(ctypes.c_int32)
@@ -509,7 +525,7 @@ class Context:
             self._L.xdemhip_device_free(self.handle, ctypes.c_void_p(p))
 
     TEST_SWITCHES = frozenset(("terrain_stream", "terrain_order", "terrain_ring_wait", "terrain_window_lds", "nk_narrow",
-                               "vario_grid", "vario_runs", "vario_sort", "hypso_seg_lds"))
+                               "vario_grid", "vario_runs", "vario_sort", "hypso_seg_lds", "pts_tile_order"))
 
     def set_option(self, name: str, value: int) -> None:
         """Option of the library (``xdemhip_set_option``: the fourteen names of include/xdemhip.h), e.g. ``("selection", 1)`` -- or,

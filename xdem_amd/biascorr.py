@@ -444,6 +444,23 @@ class VerticalShift(_Step):
             self.meta["inputs"]["random"]["random_state"] = random_state
         func = self.meta["inputs"]["affine"]["vshift_reduc_func"]
         logging.info("Running vertical shift coregistration")
+        from . import epc as _epc
+
+        if _epc.is_cloud(reference_elev) or _epc.is_cloud(to_be_aligned_elev):
+            # one raster and one cloud (base.py:747-772): dh at the points at zero shift, reference minus to-be-aligned
+            if _epc.is_cloud(reference_elev) and _epc.is_cloud(to_be_aligned_elev):
+                raise TypeError("This pre-processing function is only intended for raster-point or raster-raster methods, "
+                                "not point-point methods.")
+            raster, cloud, pts_is_ref = _epc.split_pair(reference_elev, to_be_aligned_elev)
+            with _epc.PtsPlan(raster, *_epc.cloud_columns(cloud, z_name), transform, pts_is_ref, inlier_mask) as plan:
+                n = draw(plan, self.meta["inputs"]["random"]["subsample"], self.meta["inputs"]["random"]["random_state"])
+                if func is np.median or func is np.nanmedian:
+                    vshift = float(plan.shift_nmad(0.0, 0.0)[0])
+                else:
+                    vshift = float(func(plan.shift_values(0.0, 0.0)))
+            self.meta["outputs"]["affine"] = {"shift_z": vshift}
+            self.meta["outputs"]["random"] = {"subsample_final": int(n)}
+            return self
         with DhPlan(reference_elev, to_be_aligned_elev, inlier_mask) as plan:
             n = draw(plan, self.meta["inputs"]["random"]["subsample"], self.meta["inputs"]["random"]["random_state"])
             if func is np.median or func is np.nanmedian:
@@ -462,6 +479,10 @@ class VerticalShift(_Step):
             raise AssertionError(".fit() does not seem to have been called yet")
         if bias_vars is not None:
             raise NotImplementedError("bias_vars is not used by VerticalShift.")
+        from . import epc as _epc
+
+        if _epc.is_cloud(elev):
+            return _epc.apply_matrix_cloud(elev, self.to_matrix(), z_name=z_name)
         res = resolution if resolution is not None else 1.0
         out = apply_translation(elev, 0.0, 0.0, self.meta["outputs"]["affine"]["shift_z"], res, resample=False)
         return _with_transform(out, transform)

@@ -12,7 +12,11 @@ Scope: two rasters on the same grid given as arrays (+ resolution); ``bin_before
 callable (the GPU hands y and the bin ids of every pixel back and the callable runs on the host per bin, exactly as
 ``scipy.stats.binned_statistic`` calls it upstream -- single-process fits only).  ``subsample=1`` uses all valid pixels (the
 BASELINE configuration); any other value a random subset drawn once by the restated rule of geoutils' ``subsample_array``
-(``subsample_valid_mask``).  Point-cloud inputs are outside the hot path and raise ``NotImplementedError``.
+(``subsample_valid_mask``).
+
+One of the two elevation datasets may be a point cloud (``xdem_amd.EPC`` or anything that answers a GeoDataFrame's calls) for
+``NuthKaab``, ``DhMinimize`` and ``VerticalShift``: ``transform=`` is then required, every pass over the points runs in
+``csrc/ptsplan.hip`` through ``xdem_amd.epc.PtsPlan``, and ``apply`` moves a cloud by the step's matrix and returns an ``EPC``.
 """
 from __future__ import annotations
 
@@ -25,6 +29,7 @@ import numpy as np
 import scipy.optimize
 
 from . import _lib
+from . import epc as _epc
 from ._coregbase import NO_VALID, CoregPipeline, _Plan, _Step, apply_translation, draw, raster_pair  # noqa: F401
 from ._coregbase import subsample_ranks, subsample_valid_mask  # noqa: F401
 from .biascorr import Deramp, DhPlan, VerticalShift, _check_weights, polynomial_2d  # noqa: F401  (upstream's xdem.coreg offers them here)
@@ -33,7 +38,11 @@ from .rigid import (LZD, apply_matrix, invert_matrix, matrix_from_translations_r
                     translations_rotations_from_matrix, _make_matrix_valid)
 from .icp import ICP, nearest  # noqa: F401
 from .cpd import CPD, cpd_expectation, cpd_update  # noqa: F401
+from .epc import EPC  # noqa: F401
 from .spatialstats import nmad
+
+TWO_CLOUDS = ("This pre-processing function is only intended for raster-point or raster-raster methods, "
+              "not point-point methods.")   # (base.py:643-647)
 
 
 def _nuth_kaab_fit_func(xx, *params):
@@ -391,6 +400,32 @@ def nuth_kaab(ref_elev: np.ndarray, tba_elev: np.ndarray, inlier_mask: np.ndarra
         plan.close()
 
 
+def nuth_kaab_pts(reference_elev, to_be_aligned_elev, inlier_mask, transform, z_name: str | None = None, tolerance: float = 0.001,
+                  max_iterations: int = 10, bin_sizes=72, fit_optimizer: Callable[..., Any] | None = None, subsample: float | int = 1,
+                  random_state=None, bin_statistic=np.nanmedian, bin_before_fit: bool = True,
+                  initial_offsets: tuple[float, float] = (0.0, 0.0)):
+    """``nuth_kaab`` (affine.py:539-609) for one raster and one point cloud, either as the reference: the same iteration around a
+    raster-point plan.  Slope tangent and aspect come from the raster and are interpolated at the points once (affine.py:463-472,
+    234-239).  Returns ((easting, northing, vertical) offsets in georeferenced units, subsample_final)."""
+    import scipy.optimize
+
+    if _epc.is_cloud(reference_elev) and _epc.is_cloud(to_be_aligned_elev):
+        raise TypeError("The Nuth and Kääb (2011) coregistration does not support two point clouds, one elevation "
+                        "dataset in the pair must be a DEM.")   # (affine.py:450-455)
+    _check_unbinned_optimizer(fit_optimizer, bin_before_fit)
+    fit_optimizer = fit_optimizer or scipy.optimize.curve_fit
+    logging.info("Running Nuth and Kääb (2011) coregistration")
+    raster, cloud, pts_is_ref = _epc.split_pair(reference_elev, to_be_aligned_elev)
+    x, y, z = _epc.cloud_columns(cloud, z_name)
+    with _epc.PtsPlan(raster, x, y, z, transform, pts_is_ref, inlier_mask, with_nk_aux=True) as plan:
+        n = draw(plan, subsample, random_state)
+        plan.set_statistic(bin_statistic)
+        if not isinstance(bin_sizes, (int, np.integer)):
+            plan.set_bin_edges(bin_sizes)
+        offsets = _iterate(plan, plan.res, tolerance, max_iterations, bin_sizes, fit_optimizer, bin_before_fit, initial_offsets)
+        return offsets, int(n)
+
+
 def _check_initial_shift(initial_shift):
     """The checks of ``AffineCoreg.__init__`` (affine.py:1813-1829): a tuple of two or three numbers; a vertical part is dropped."""
     if not (isinstance(initial_shift, tuple) and len(initial_shift) in (2, 3)
@@ -427,6 +462,8 @@ class _TranslationStep(_Step):
         array; with ``resolution=`` it returns the array alone."""
         if bias_vars is not None:
             raise NotImplementedError(f"bias_vars is not used by {type(self).__name__}.")
+        if _epc.is_cloud(elev):   # (a cloud is moved by the matrix and comes back as an EPC: _apply_matrix_pts)
+            return _epc.apply_matrix_cloud(elev, self.to_matrix(), z_name=z_name)
         if resampling != "bilinear":
             raise NotImplementedError("the GPU resampler is bilinear (the reference default).")
         a = self.meta["outputs"]["affine"]
@@ -519,16 +556,27 @@ class NuthKaab(_TranslationStep):
             self.meta["inputs"]["random"]["subsample"] = subsample
         if random_state is not None:
             self.meta["inputs"]["random"]["random_state"] = random_state
+        it = self.meta["inputs"]["iterative"]
+        fb = self.meta["inputs"]["fitorbin"]
+        init = self.meta["inputs"]["affine"].get("initial_shift")
+        if _epc.is_cloud(reference_elev) or _epc.is_cloud(to_be_aligned_elev):
+            (east, north, vert), n_final = nuth_kaab_pts(reference_elev, to_be_aligned_elev, inlier_mask, transform, z_name,
+                                                         tolerance=it["tolerance"], max_iterations=it["max_iterations"],
+                                                         bin_sizes=fb["bin_sizes"], fit_optimizer=fb["fit_optimizer"],
+                                                         subsample=self.meta["inputs"]["random"]["subsample"],
+                                                         random_state=self.meta["inputs"]["random"]["random_state"],
+                                                         bin_statistic=fb["bin_statistic"], bin_before_fit=fb["fit_or_bin"] == "bin_and_fit",
+                                                         initial_offsets=(-init[0], -init[1]) if init is not None else (0.0, 0.0))
+            self.meta["outputs"]["affine"] = {"shift_x": -east, "shift_y": -north, "shift_z": vert * self.vertical_shift}
+            self.meta["outputs"]["random"] = {"subsample_final": n_final}
+            return self
         res = self._resolution(resolution, transform)
         ref = np.asarray(reference_elev.filled(np.nan) if isinstance(reference_elev, np.ma.MaskedArray) else reference_elev)
         tba = np.asarray(to_be_aligned_elev.filled(np.nan) if isinstance(to_be_aligned_elev, np.ma.MaskedArray) else to_be_aligned_elev)
-        it = self.meta["inputs"]["iterative"]
-        fb = self.meta["inputs"]["fitorbin"]
         # initial_shift (base.py:2307-2313, 2358-2366): upstream translates the reference by (-sx, -sy), fits, and adds (sx, sy)
         # back to the estimated shift -- i.e. the search starts from shift_x = sx.  Here the iteration itself starts from
         # the offsets (-sx, -sy), which samples the to-be-aligned DEM once at the shifted position instead of resampling
         # it onto the translated grid first.
-        init = self.meta["inputs"]["affine"].get("initial_shift")
         (east, north, vert), n_final = nuth_kaab(ref, tba, inlier_mask, res, tolerance=it["tolerance"],
                                                  max_iterations=it["max_iterations"], bin_sizes=fb["bin_sizes"],
                                                  fit_optimizer=fb["fit_optimizer"],
@@ -539,6 +587,14 @@ class NuthKaab(_TranslationStep):
         self.meta["outputs"]["affine"] = {"shift_x": -east, "shift_y": -north, "shift_z": vert * self.vertical_shift}
         self.meta["outputs"]["random"] = {"subsample_final": n_final}
         return self
+
+
+def _pts_plan(reference_elev, to_be_aligned_elev, inlier_mask, transform, z_name):
+    """The raster-point plan of DhMinimize's fit: valid points by the raster and the mask alone (base.py:689-701)."""
+    if _epc.is_cloud(reference_elev) and _epc.is_cloud(to_be_aligned_elev):
+        raise TypeError(TWO_CLOUDS)
+    raster, cloud, pts_is_ref = _epc.split_pair(reference_elev, to_be_aligned_elev)
+    return _epc.PtsPlan(raster, *_epc.cloud_columns(cloud, z_name), transform, pts_is_ref, inlier_mask)
 
 
 class DhMinimize(_TranslationStep):
@@ -579,14 +635,16 @@ class DhMinimize(_TranslationStep):
             self.meta["inputs"]["random"]["subsample"] = subsample
         if random_state is not None:
             self.meta["inputs"]["random"]["random_state"] = random_state
-        res = self._resolution(resolution, transform)
+        pts = _epc.is_cloud(reference_elev) or _epc.is_cloud(to_be_aligned_elev)
+        res = None if pts else self._resolution(resolution, transform)   # (a raster-point plan reads its transform)
         fb = self.meta["inputs"]["fitorbin"]
         loss_func, minimizer = fb["fit_loss_func"], fb["fit_minimizer"]
         # initial_shift (base.py:2307-2313, 2358-2366): the search runs around (sx, sy), as NuthKaab starts its iteration there
         init = self.meta["inputs"]["affine"].get("initial_shift") or (0.0, 0.0, 0.0)
         logging.info("Running dh minimization coregistration.")
         n_eval = 0
-        with DhPlan(reference_elev, to_be_aligned_elev, inlier_mask) as plan:
+        with (_pts_plan(reference_elev, to_be_aligned_elev, inlier_mask, transform, z_name) if pts
+              else DhPlan(reference_elev, to_be_aligned_elev, inlier_mask)) as plan:
             n = draw(plan, self.meta["inputs"]["random"]["subsample"], self.meta["inputs"]["random"]["random_state"])
 
             def fit_func(coords_offsets):

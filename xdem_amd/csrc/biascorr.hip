@@ -26,6 +26,7 @@
 #include "rank_select.h"
 #include "nk_geom.h"
 #include "dh_plan.h"
+#include "dh_eval.h"
 
 namespace xd {
 namespace {
@@ -260,21 +261,7 @@ __device__ __forceinline__ T dh_shift_pixel(const T* __restrict__ tba, const NkG
     return ok ? t_sub(refv, val) : (T)NAN;   // (a difference that overflows stays +-inf, as in NumPy: nanmedian keeps it)
 }
 
-// leading-digit counters of a workgroup: DH_HIST_COPIES privatised tables (copy = lane % copies, an odd stride apart: float keys
-// share their sign and exponent bits, every lane of a wave would otherwise hit one counter), flushed with one global add per
-// non-empty counter
-constexpr int DH_HIST_COPIES = 16, DH_HIST_STRIDE = SEL_RADIX + 1;
-template <typename T> __device__ __forceinline__ void dh_hist_count(uint32_t* hc, T v) {
-    if (v == v) atomicAdd(&hc[(int)(key_of(v) >> (8 * (KeyT<T>::passes - 1)))], 1u);
-}
-__device__ __forceinline__ void dh_hist_flush(const uint32_t* h, uint64_t* __restrict__ hist) {
-    __syncthreads();
-    for (int k = threadIdx.x; k < SEL_RADIX; k += blockDim.x) {
-        unsigned long long c = 0;
-        for (int q = 0; q < DH_HIST_COPIES; ++q) c += h[q * DH_HIST_STRIDE + k];
-        if (c) atomicAdd(reinterpret_cast<unsigned long long*>(&hist[k]), c);
-    }
-}
+// (the leading-digit counters of a workgroup, dh_hist_count / dh_hist_flush: dh_eval.h)
 
 // dense route: the tiles of dh_valid_kernel (lane l of a tile: pixels g * 1024 + 4 l .. + 3, g = 0..3), 16-byte loads of ref and
 // stores of dh and a 4-byte load of the mask where the rasters allow (VEC), one pixel at a time in the last, partial group
@@ -345,77 +332,7 @@ __global__ __launch_bounds__(256) void dh_shift_list_kernel(const T* __restrict_
     if (HIST) dh_hist_flush(h, hist);
 }
 
-__device__ __forceinline__ float dh_abs(float v) { return fabsf(v); }
-__device__ __forceinline__ double dh_abs(double v) { return fabs(v); }
-
-// |dh - median| of the staging buffer as an element source of the bracketed selection (select_run.h): nothing is materialised
-template <typename T> struct AbsDevSource {
-    const T* vals;
-    const T* med;    // device slot the first selection's finish kernel wrote
-    T m;
-    struct Raw { T v; };
-    struct Acc {};
-    static size_t lds_bytes(int) { return 0; }
-    __device__ __forceinline__ void setup(unsigned char*, int) { m = *med; }
-    __device__ __forceinline__ void fetch(int64_t p, Raw& r) const { r.v = vals[p]; }
-    __device__ __forceinline__ void blank(Raw& r) const { r.v = (T)NAN; }
-    template <bool ACC> __device__ __forceinline__ bool eval(const Raw& r, int, T& v, uint16_t& b, Acc&) const {
-        v = dh_abs(t_sub(r.v, m));
-        b = 0;
-        return v == v;
-    }
-    __device__ __forceinline__ void finish(Acc&) const {}
-    static constexpr bool HAS_LEAN = false;
-};
-// the same in place, for the plain digit passes (they read an array)
-template <typename T>
-__global__ __launch_bounds__(256) void dh_absdev_kernel(T* __restrict__ stage, int64_t n, const T* __restrict__ med) {
-    const T m = *med;
-    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (int64_t)gridDim.x * blockDim.x) stage[p] = dh_abs(t_sub(stage[p], m));
-}
-
-// What one evaluation hands back (a block behind the selection scratch): filled by the two finish kernels, fetched once.
-struct DhEvalOut {
-    double median, mad;             // in the value dtype, widened
-    unsigned long long count, fail; // values that are not NaN; a bracket of either selection missed or a candidate buffer overflowed
-    double slot;                    // the median in the value dtype: what the second selection subtracts
-};
-// np.nanmedian from a finished selection, on the device (median_from's rule).  `small` = the workspace block of a bracketed selection
-// (select_bracketed_enqueue: flags, rebase shift, low key, counters), nullptr after the plain passes.
-template <typename T>
-__global__ void dh_sel_finish_kernel(const SelState<typename KeyT<T>::type>* st, const uint64_t* succ, const uint64_t* small, int nb_max, int which,
-                                     DhEvalOut* out) {
-    typedef typename KeyT<T>::type K;
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    SelState<K> s = st[0];
-    uint64_t sc = succ[0];
-    if (small) {
-        if (small[2] != 0 || small[3] != 0) out->fail = 1ull;
-        const int rbs = (int)(uint32_t)small[4];
-        const K klo = reinterpret_cast<const K*>(small + 8)[0];
-        const uint64_t* cnt = small + 8 + 3 * nb_max;
-        s.count = cnt[0];
-        s.n_le += cnt[1];
-        s.prefix = (K)((K)(s.prefix >> rbs) + klo);
-        if (sc != ~(uint64_t)0) sc = (uint64_t)(K)((K)((K)sc >> rbs) + klo);
-    }
-    T m = (T)NAN;
-    if (s.count) {
-        const T lo = val_of(s.prefix);
-        if (s.count & 1) m = lo;
-        else {
-            const T hi = (s.n_le > s.count / 2) ? lo : val_of((K)sc);
-            m = (T)((T)(lo + hi) / (T)2);
-        }
-    }
-    if (which == 0) {
-        out->median = (double)m;
-        out->count = s.count;
-        *reinterpret_cast<T*>(&out->slot) = m;
-    } else {
-        out->mad = (double)m;
-    }
-}
+// (|dh - median| as a source, the finish kernel of a selection and the block one evaluation hands back: dh_eval.h)
 
 // ---- apply: out = cast(double(elev) + polyval2d(x, y, c)) ---------------------------------------------------------------------
 // NumPy's evaluation order (numpy/polynomial/polynomial.py polyval / polyval2d), no contraction (-ffp-contract=off):
@@ -697,61 +614,17 @@ int launch_shift(xdemhip_dh_plan* P, const NkGeom& g, bool with_hist, uint64_t* 
     return launched(ctx, "dh_shift kernel");
 }
 
-// One evaluation: the data pass, the median's selection, |dh - median|'s selection, ONE fetch.  Inputs of SEL_BRACKET_MIN_N values
-// and more take the bracketed route of select_run.h for both selections (a sample, one counting pass, the candidates) with the
-// decoding done by dh_sel_finish_kernel; should a bracket miss -- the integer counts of the counting pass tell -- the evaluation is
-// run again with the plain digit passes, which cannot miss.  Nothing is allocated here once the plan's buffers exist.
+// One evaluation (dh_eval.h: the data pass, two selections, one fetch) over the plan's selection; nothing is allocated here once the
+// plan's buffers exist.
 template <typename T>
 int shift_nmad_typed(xdemhip_dh_plan* P, const NkGeom& g, double nfact, double* median, double* nmad, int64_t* count) {
-    typedef typename KeyT<T>::type K;
     xdemhip_ctx* ctx = P->ctx;
     const int64_t n = P->drawn ? P->n_idx : P->H * P->W;
     int rc = ensure_stage(P, n);
     if (rc == XDEMHIP_OK) rc = ensure_selection(P, n);
     if (rc) return rc;
-    unsigned char* scratch = P->sel_scratch;
-    DhEvalOut* d_out = reinterpret_cast<DhEvalOut*>(scratch + scratch_size(1));
-    const SelState<K>* d_st = reinterpret_cast<const SelState<K>*>(scratch + OFF_STATE);
-    const uint64_t* d_succ = reinterpret_cast<const uint64_t*>(scratch + off_succ(1));
-    T* stage = static_cast<T*>(P->stage);
-    const T* d_med = reinterpret_cast<const T*>(&d_out->slot);
-    DhEvalOut h;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        const bool plain = attempt == 1 || n < SEL_BRACKET_MIN_N;
-        XD_HIP_CHECK(ctx, hipMemsetAsync(d_out, 0, sizeof(DhEvalOut), ctx->stream));
-        bool queued = false;
-        if (plain) {
-            uint64_t* hist = select_reset<K>(ctx, scratch, 1);
-            rc = launch_shift<T>(P, g, true, hist);
-            if (rc == XDEMHIP_OK) rc = select_enqueue<T>(ctx, stage, nullptr, n, n, nullptr, 1, scratch, SEL_MEDIAN, nullptr, 0, true, nullptr, nullptr, true);
-        } else {
-            rc = launch_shift<T>(P, g, false, nullptr);
-            if (rc == XDEMHIP_OK) rc = select_bracketed_enqueue<T, ArraySource<T>>(ctx, ArraySource<T>{stage, nullptr}, n, 1, scratch, &P->sel_ws, &queued);
-            if (rc == XDEMHIP_OK && !queued) rc = select_enqueue<T>(ctx, stage, nullptr, n, n, nullptr, 1, scratch, SEL_MEDIAN, nullptr);
-        }
-        if (rc) return rc;
-        hipLaunchKernelGGL((dh_sel_finish_kernel<T>), dim3(1), dim3(1), 0, ctx->stream, d_st, d_succ, queued ? P->sel_ws.d_small : (const uint64_t*)nullptr,
-                           P->sel_ws.nb_max, 0, d_out);
-        bool queued2 = false;
-        if (!plain) rc = select_bracketed_enqueue<T, AbsDevSource<T>>(ctx, AbsDevSource<T>{stage, d_med, (T)0}, n, 1, scratch, &P->sel_ws, &queued2);
-        if (rc == XDEMHIP_OK && !queued2) {
-            hipLaunchKernelGGL((dh_absdev_kernel<T>), dim3(grid_for(ctx, n, 256, 16)), dim3(256), 0, ctx->stream, stage, n, d_med);
-            rc = select_enqueue<T>(ctx, stage, nullptr, n, n, nullptr, 1, scratch, SEL_MEDIAN, nullptr);
-        }
-        if (rc) return rc;
-        hipLaunchKernelGGL((dh_sel_finish_kernel<T>), dim3(1), dim3(1), 0, ctx->stream, d_st, d_succ, queued2 ? P->sel_ws.d_small : (const uint64_t*)nullptr,
-                           P->sel_ws.nb_max, 1, d_out);
-        if (launched(ctx, "dh selection kernel")) return XDEMHIP_EHIP;
-        rc = xd_d2h(ctx, &h, d_out, sizeof h);
-        if (rc == XDEMHIP_OK) rc = xd_sync(ctx);
-        if (rc) return rc;
-        if (!h.fail) break;
-    }
-    *count = (int64_t)h.count;
-    if (h.count == 0) return xd_fail(ctx, XDEMHIP_EINVAL, "no valid points");
-    *median = h.median;
-    *nmad = (double)(T)((T)nfact * (T)h.mad);   // nfact * np.nanmedian(...): the Python float is a weak scalar (xdemhip_nmad's rule)
-    return XDEMHIP_OK;
+    return dh_eval_median_nmad<T>(ctx, static_cast<T*>(P->stage), n, P->sel_scratch, &P->sel_ws, nfact,
+                                  [&](bool with_hist, uint64_t* hist) { return launch_shift<T>(P, g, with_hist, hist); }, median, nmad, count);
 }
 
 inline void norm_axis(int64_t n_global, double* a, double* b) {

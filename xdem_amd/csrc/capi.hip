@@ -319,6 +319,7 @@ const XdOpt kTestSwitches[] = {
     {"vario_grid", 0, 1, &xdemhip_ctx::vario_grid, "vario_grid: 0 or 1"},
     {"vario_runs", 0, 1, &xdemhip_ctx::vario_runs, "vario_runs: 0 or 1"},
     {"vario_sort", 0, 1, &xdemhip_ctx::vario_sort, "vario_sort: 0 or 1"},
+    {"pts_tile_order", 0, 1, &xdemhip_ctx::pts_tile_order, "pts_tile_order: 0 or 1"},
     {"hypso_seg_lds", 0, 16384, &xdemhip_ctx::hypso_seg_lds, "hypso_seg_lds: 0 (default: 8192) or 1 to 16384 values"},
 };
 int xd_set_from(xdemhip_ctx* ctx, const XdOpt* tab, size_t n, const char* name, int value, bool* found) {

@@ -25,13 +25,7 @@ namespace xd {
 // and m bounds |y(v) - y^| for every v in [v_lo, v_hi] including the roundings of both evaluations (slack terms below).
 // nanmean / nanstd of y (the p0 of the 72-point curve fit only) come from sums of y^ and the first-order correction in
 // (v^ - vshift): sum y = sum y^ + (v^ - v) sum r, sum y^2 = sum y^^2 + 2 (v^ - v) sum y^ r + (v^ - v)^2 sum r^2, r = 1 / st.
-// np.linspace(smin, smax, nb + 1) in double (k * step + start, end point forced), cast to T -- SciPy's _bin_edges
-template <typename T> __host__ __device__ inline void make_edges_into(double smin, double smax, int nb, T* e) {
-    if (smin == smax) { smin -= 0.5; smax += 0.5; }
-    const double step = (smax - smin) / nb;
-    for (int k = 0; k <= nb; ++k) e[k] = (T)((double)k * step + smin);
-    e[nb] = (T)smax;
-}
+// (SciPy's bin edges, make_edges_into: nk_aux.h)
 // Lane masks as 64-bit scalars: compares that deliver the mask itself (a C++ `bool` that also feeds a ballot is legalised into a
 // 0/1 register and compared again), and selects that take such a mask as their condition
 __device__ __forceinline__ unsigned long long cm_nlt(float a, float b) { unsigned long long m; asm("v_cmp_nlt_f32_e64 %0, %1, %2" : "=s"(m) : "v"(a), "v"(b)); return m; }

@@ -20,53 +20,13 @@
 #include "select.h"
 #include "select_run.h"
 #include "nk_geom.h"
+#include "nk_aux.h"
 #include "rank_select.h"
 
 namespace xd {
 
-// ---- aux: gradient -> slope tangent, aspect, valid mask --------------------------------------------------------
-template <typename T>
-__global__ __launch_bounds__(256) void nk_aux_kernel(const T* __restrict__ ref, const T* __restrict__ tba,
-                                                     const uint8_t* __restrict__ inlier, NkGeom g,
-                                                     T* __restrict__ slope_tan, T* __restrict__ aspect,
-                                                     uint8_t* __restrict__ valid, unsigned long long* n_valid,
-                                                     int64_t row0, int64_t row1) {
-    // raster rows [row0, row1): blockIdx.x tiles the columns, blockIdx.y strides over the rows
-    unsigned long long local = 0;
-    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t H = g.H, W = g.W;
-    if (j < W)
-    for (int64_t i = row0 + blockIdx.y; i < row1; i += gridDim.y) {
-        const int64_t p = (i - g.roff) * W + j;
-        const T c = ref[p];
-        T gy, gx;
-        // np.gradient, unit spacing: central differences inside, one-sided on the borders of the RASTER
-        if (i == 0) gy = t_sub(ref[p + W], c);
-        else if (i == H - 1) gy = t_sub(c, ref[p - W]);
-        else gy = t_div(t_sub(ref[p + W], ref[p - W]), (T)2);
-        if (j == 0) gx = t_sub(ref[p + 1], c);
-        else if (j == W - 1) gx = t_sub(c, ref[p - 1]);
-        else gx = t_div(t_sub(ref[p + 1], ref[p - 1]), (T)2);
-        T st = t_sqrt(t_add(t_mul(gx, gx), t_mul(gy, gy)));
-        // aspect = arctan2(-gx, gy) + pi: correctly rounded to the DEM dtype from the float64 arctangent
-        T as = (T)atan2(-(double)gx, (double)gy);
-        as = t_add(as, (T)3.14159265358979323846);
-        if (fabs((double)st) <= 1e-8) st = (T)NAN;  // np.isclose(slope_tan, 0) -> NaN (affine.py:578-579)
-        const bool ok = (inlier ? inlier[p] != 0 : true) && t_finite(c) && t_finite(tba[p]) && t_finite(st) && t_finite(as);
-        slope_tan[p] = st;
-        aspect[p] = as;
-        valid[p] = ok ? 1 : 0;
-        local += ok ? 1 : 0;
-    }
-    // wave reduction then one atomic per wave
-    for (int off = 32; off > 0; off >>= 1) local += __shfl_down(local, off);
-    if ((threadIdx.x & 63) == 0 && local) atomicAdd(n_valid, local);
-}
-
 // ---- dh at a shifted position + min / max aspect over its finite pixels -------------------------------------------
-struct DhStats {
-    uint64_t asp_min, asp_max;  // order-preserving keys (widened to 64 bit) of min / max aspect among finite dh
-};
+// (DhStats: nk_aux.h)
 static __global__ void nk_stats_init_kernel(DhStats* s) {
     if (threadIdx.x == 0) { s->asp_min = ~(uint64_t)0; s->asp_max = 0; }
 }
@@ -249,19 +209,7 @@ __global__ __launch_bounds__(256) void shift_bilinear_kernel(const T* __restrict
     }
 }
 
-// SciPy's rule for samples at or beyond the rightmost edge (_binned_statistic.py:_bin_numbers): such a sample joins the last
-// bin iff np.around(x, decimal) == np.around(last_edge, decimal), decimal = int(-log10(min edge spacing)) + 6, evaluated in
-// the sample dtype.  With the automatic edges the largest sample IS the last edge (decimal = NK_AUTO_EDGES: always true);
-// explicit edges carry their decimal (computed by the caller exactly like SciPy).
-constexpr int NK_AUTO_EDGES = -100000;
-template <typename T> __device__ __forceinline__ bool on_last_edge(T x, T last, int decimal) {
-    if (decimal == NK_AUTO_EDGES) return true;
-    const T p10 = (T)pow(10.0, (double)(decimal < 0 ? -decimal : decimal));
-    const T rx = decimal >= 0 ? rint(x * p10) / p10 : rint(x / p10) * p10;
-    const T rl = decimal >= 0 ? rint(last * p10) / p10 : rint(last / p10) * p10;
-    return rx == rl;
-}
-
+// (SciPy's rule for samples on the last edge, on_last_edge, and the digitize step aspect_bin: nk_aux.h)
 // ---- y = (dh - vshift) / slope_tan, aspect bin id, sums for nanmean / nanstd --------------------------------
 template <typename T>
 __global__ __launch_bounds__(256) void nk_y_kernel(const T* __restrict__ dh, const T* __restrict__ slope_tan,
@@ -283,15 +231,7 @@ __global__ __launch_bounds__(256) void nk_y_kernel(const T* __restrict__ dh, con
         uint16_t b = 0xFFFF;
         if (d == d) {  // dh is NaN wherever the pixel is unusable
             yv = t_div(t_sub(d, vshift), st);
-            // np.digitize(x, edges) - 1 = (number of edges <= x) - 1: arithmetic guess on the uniform grid, then an exact
-            // walk against the dtype-rounded edges (a step or two); a sample equal to the last edge goes to the last bin
-            int idx = (int)(((double)x - (double)e[0]) * inv_width);
-            idx = idx < 0 ? 0 : (idx > nb ? nb : idx);
-            while (idx > 0 && !(e[idx] <= x)) --idx;
-            while (idx < nb && e[idx + 1] <= x) ++idx;
-            if (!(e[0] <= x)) idx = -1;
-            if (idx == nb && on_last_edge<T>(x, e[nb], last_decimal)) idx = nb - 1;
-            b = (idx >= 0 && idx < nb) ? (uint16_t)idx : 0xFFFF;
+            b = aspect_bin<T>(x, e, nb, inv_width, last_decimal);
             s1 += (double)yv;
             s2 += (double)yv * (double)yv;
         }

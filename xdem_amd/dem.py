@@ -137,6 +137,13 @@ class DEM:
         method = coreg_method if coreg_method is not None else _coreg.NuthKaab(subsample=1)
         if not isinstance(method, _Step):
             raise ValueError("Argument `coreg_method` must be an xdem_amd.coreg instance (e.g. xdem_amd.coreg.NuthKaab()).")
+        if hasattr(reference_elev, "geometry"):   # an elevation point cloud as reference: NuthKaab, DhMinimize, VerticalShift and their pipelines
+            mask = None if inlier_mask is None else np.asarray(getattr(inlier_mask, "data", inlier_mask), dtype=bool)
+            if bias_vars is not None:
+                raise NotImplementedError("bias_vars is not used by the methods that take a point cloud.")
+            method.fit(reference_elev, self.data, mask, transform=self.transform, **kwargs)
+            out, out_transform = method.apply(self.data, resample=resample, transform=self.transform)
+            return DEM(out, out_transform, self.crs, self.nodata)
         if reference_elev.shape != self.shape or reference_elev.transform != self.transform:
             raise NotImplementedError("reference and to-be-aligned DEM must share one grid (reprojection is geoutils' job).")
         mask = None if inlier_mask is None else np.asarray(getattr(inlier_mask, "data", inlier_mask), dtype=bool)

@@ -10,7 +10,7 @@ Every pass over the grids runs in ``csrc/rigid.hip``:
   the optimum ``least_squares`` converges to from zeros, as Deramp's moments replace ``curve_fit``.  Any other minimiser / loss gets
   the six arrays ``x, y, z, dh, gradx, grady`` from the device (``xdemhip_dh_lzd_values``) and runs on the host exactly as ``_lzd_fit``
   calls it.
-* ``apply_matrix`` regrids a DEM after a rigid transform with rotations below 20 degrees (``xdemhip_apply_matrix_rst``); pure
+* ``apply_matrix`` moves a point cloud by any 4 x 4 matrix (``xdemhip_apply_matrix_pts``, returns an ``EPC``) and regrids a DEM after a rigid transform with rotations below 20 degrees (``xdemhip_apply_matrix_rst``); pure
   translations go through ``apply_translation``.  Larger rotations (Delaunay ``griddata`` upstream) and resamplings other than linear
   are not implemented.
 
@@ -139,8 +139,12 @@ def apply_matrix(elev, matrix, invert: bool = False, centroid=None, resample: bo
     array case; returns ``(array, transform)``): a z-only matrix adds the shift, a translation goes through ``apply_translation``
     (``resample=False`` moves the transform instead), rotations below 20 degrees about every axis are regridded on the device by
     upstream's fixed-point iteration with SciPy's linear ``RegularGridInterpolator``.  Output dtype = input dtype."""
-    if hasattr(elev, "geometry"):
-        raise NotImplementedError("point clouds are not supported: pass a 2-D array with its transform")
+    if hasattr(elev, "geometry"):   # a cloud: every point moved by the matrix, any rotation (_apply_matrix_pts, base.py:1290-1325)
+        from . import epc as _epc
+
+        if invert:
+            invert_matrix(np.asarray(matrix, dtype=np.float64))   # (its checks; the device forms R^T and -(R^T t) itself)
+        return _epc.apply_matrix_cloud(elev, matrix, invert, centroid, z_name)
     matrix = np.asarray(matrix, dtype=np.float64)
     if invert:
         matrix = invert_matrix(matrix)

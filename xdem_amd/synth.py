@@ -208,3 +208,57 @@ def volume_case(H: int, W: int, dtype=np.float32) -> dict:
         mask = lab > 0
     dt = np.dtype(dtype)
     return {"ddem": ddem.astype(dt), "ref": ref.astype(dt), "ref_voids": ref_voids.astype(dt), "labels": lab, "mask": mask}
+
+
+CLOUD_SHIFT = (7.5, -4.0, 2.25)   # the offsets (easting, northing, vertical) a Nuth-Kaab fit of cloud_case finds with the cloud as reference
+
+
+def cloud_surface(x, y, t6, shape):
+    """The smooth surface of ``cloud_case`` at georeferenced (x, y): a bowl with a cross term and a cubic, so that every aspect occurs and
+    the slope tangent is a few tenths over most of the raster and passes 1 at its rim: the signal of the shift, slope times 8.5 m, stands
+    well above the 0.3 m of noise everywhere but within a few pixels of the bowl's floor.  Only +, -, * on float64."""
+    H, W = shape
+    u = (x - (t6[2] + 0.5 * W * t6[0])) * 1e-3          # kilometres from the raster's centre
+    v = (y - (t6[5] + 0.5 * H * t6[4])) * 1e-3
+    return 1000.0 + 720.0 * u * u + 1040.0 * v * v + 360.0 * u * v + 600.0 * u * u * u - 480.0 * u * v * v
+
+
+def cloud_case(H: int, W: int, n: int, dtype=np.float32) -> dict:
+    """Inputs of the raster-point fixtures and tests (tools/gen_golden_rstpts.py records the reference's results on exactly these): a
+    raster of ``cloud_surface`` on a 10 m grid with a NaN block and an outlier-mask region, and a cloud of about ``n`` points of the
+    same surface displaced by ``CLOUD_SHIFT`` with 0.3 m of noise.  Of the points, some lie off the raster by less and by more than
+    one pixel, some exactly on pixel centres (the last row and column included, where the four tap rules differ), some are duplicated,
+    some have a NaN or infinite z and some a NaN coordinate; about a tenth is invalid.  Hashed integers and exactly rounded operations
+    only: the same bits everywhere, nothing of it needs storing."""
+    dt = np.dtype(dtype)
+    t6 = (10.0, 0.0, 500000.0, 0.0, -10.0, 4200000.0 + 10.0 * H)
+    rows, cols = np.divmod(np.arange(H * W), W)
+    px, py = t6[2] + (cols + 0.5) * t6[0], t6[5] + (rows + 0.5) * t6[4]
+    raster = cloud_surface(px, py, t6, (H, W)).astype(np.float32)
+    raster = (raster.astype(np.float64) + 1e-5 * (_hash01(H * W, 77) - 0.5) if dt == np.float64 else raster).reshape(H, W)
+    raster[H // 5:H // 5 + 6, W // 2:W // 2 + 9] = np.nan
+    inlier = np.ones((H, W), dtype=bool)
+    inlier[H // 2:H // 2 + 7, W // 6:W // 6 + 11] = False
+    m = n - 24   # the random points; the 24 others are planted below
+    u = [_hash01(m, 5000 * k + 31) for k in range(4)]
+    # positions over the raster's extent widened by 1.6 pixels on every side
+    x = t6[2] + (u[0] * (W + 3.2) - 1.6) * t6[0]
+    y = t6[5] + (u[1] * (H + 3.2) - 1.6) * t6[4]
+    noise = 0.3 * ((u[2] + u[3] + _hash01(m, 20031)) * 2.0 - 3.0)   # sum of three uniforms: standard deviation 0.3 * 2 * 0.5 = 0.3
+    sx, sy, sz = CLOUD_SHIFT
+    # planted points: pixel centres (corners, last row / column, interior), then duplicates of the first random points
+    pr = np.array([0, 0, H - 1, H - 1, H - 1, H // 3, 1, H - 2], dtype=np.float64)
+    pc = np.array([0, W - 1, 0, W - 1, W // 2, W - 1, 1, W - 2], dtype=np.float64)
+    x = np.concatenate([x, t6[2] + (pc + 0.5) * t6[0], x[:8], x[8:16]])
+    y = np.concatenate([y, t6[5] + (pr + 0.5) * t6[4], y[:8], y[8:16]])
+    z = cloud_surface(x + sx, y + sy, t6, (H, W)) + sz
+    z[:m] += noise
+    z[m + 8:m + 16] = z[:8]
+    # non-finite entries among the last eight (copies of random points 8..15)
+    z[m + 16] = np.nan
+    z[m + 17] = np.inf
+    z[m + 18] = -np.inf
+    x[m + 19] = np.nan
+    y[m + 20] = np.nan
+    return {"raster": raster.astype(dt), "inlier": inlier, "transform": t6, "x": x, "y": y, "z": z, "shift": CLOUD_SHIFT,
+            "res": (10.0, 10.0)}
