@@ -666,6 +666,32 @@ int xdemhip_perbin_lookup(xdemhip_ctx* ctx, const void* const* vars, const int* 
 int xdemhip_shift_bilinear(xdemhip_ctx* ctx, const void* src, int dtype, int64_t H, int64_t W, double shift_row_px,
                            double shift_col_px, double dz, void* out, int memspace);
 
+/* ---- xdem.coreg.BlockwiseCoreg (xdem/coreg/blockwise.py): one Nuth-Kaab fit per tile of a tiling, all tiles together --------------
+ * A plan copies the two rasters into tile-major buffers (tiles4: row0, row1, col0, col1 of each of the n_tiles <= 65535 tiles, every tile
+ * inside the raster, at least 2 x 2 and fewer than 2^31 pixels); every tile is then an independent raster: np.gradient is one-sided
+ * on ITS borders and no bilinear tap or nodata neighbourhood ("nk_nan_rule", read at creation) leaves it.  n_valid_per_tile[t] = the
+ * valid pixels of tile t (the valid mask of xdemhip_nk_create, per tile).  The caller's arrays are not referenced after the call.
+ * xdemhip_bw_nk_step runs ONE iteration step of every tile whose active[t] is non-zero, at that tile's own (shift_x[t], shift_y[t]), in
+ * a number of launches that does not depend on n_tiles, with one copy back.  Per active tile: what xdemhip_nk_step returns for the
+ * tile as a raster of its own -- vshift, n_valid (finite dh; 0: the tile has no valid value left, every other entry of it is NaN / 0),
+ * y_mean / y_std (float64, summed in a fixed order), edges[t][n_bins + 1], counts[t][n_bins], medians[t][n_bins], n_bins <= 128.  The
+ * entries of inactive tiles are left as they are.  Automatic edges and the median statistic only.
+ * xdemhip_bw_apply is the warp of BlockwiseCoreg.apply for shift fields affine in (x, y): coeff_* = (a, b, d) of shift = a x + b y + d in
+ * the georeferenced coordinates of transform6 = (a, b, c, d, e, f) (x = a col + c, y = e row + f at pixel corners; b = d = 0).  With
+ * M = I + [[a_x, b_x], [a_y, b_y]]: out(p') = (dtype)(bilinear(dem)(row(p), col(p)) + a_z x + b_z y + d_z) at p = M^-1 (p' - (d_x, d_y)),
+ * p' the output pixel's centre; float64, nodata by "nk_nan_rule".  XDEMHIP_EINVAL if M is singular. */
+typedef struct xdemhip_bw_plan xdemhip_bw_plan;
+int xdemhip_bw_create(xdemhip_ctx* ctx, const void* ref, const void* tba, const unsigned char* inlier_or_null, int dtype, int64_t H, int64_t W,
+                      int n_tiles, const int64_t* tiles4, int memspace, xdemhip_bw_plan** plan, int64_t* n_valid_per_tile);
+int xdemhip_bw_nk_step(xdemhip_bw_plan* plan, const unsigned char* active, const double* shift_x, const double* shift_y, double res_x,
+                       double res_y, int n_bins, double* vshift, int64_t* n_valid, double* y_mean, double* y_std, double* edges,
+                       int64_t* counts, double* medians);
+/* (slope tangent, aspect, valid mask) of every tile copied to the host, tile after tile, each tile row-major (tests / debugging) */
+int xdemhip_bw_get_aux(xdemhip_bw_plan* plan, void* slope_tan, void* aspect, unsigned char* valid);
+void xdemhip_bw_destroy(xdemhip_bw_plan* plan);
+int xdemhip_bw_apply(xdemhip_ctx* ctx, const void* dem, int dtype, int64_t H, int64_t W, const double* transform6, const double* coeff_x3,
+                     const double* coeff_y3, const double* coeff_z3, void* out, int memspace);
+
 /* ---- path 3: empirical variogram, pairwise lag binning -----------------------------------------------
  * Replaces the pairwise work sample_empirical_variogram delegates to scikit-gstat:
  *   skg.Variogram(coordinates, values, bin_func=<right edges>, maxlag=, estimator=)      xdem/spatialstats.py:1091  (pdist)

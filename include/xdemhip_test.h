@@ -13,6 +13,8 @@
  *   "vario_sort"         1 (default) the host side uploads a Morton-ordered copy of every pair block, 0 one copy in the caller's order.
  *   "hypso_seg_lds"      0 (default: 8192) the longest segment of xdemhip_hypso_segments that one workgroup sorts in LDS; a longer one takes
  *                        the radix selection over its slice of global memory (1 .. 16384: a test sends a 40-value segment down it).
+ *   "bw_seg_lds"         0 (default: 4096) the longest (tile, bin) segment of xdemhip_bw_nk_step that one workgroup sorts in LDS; a longer one
+ *                        takes the radix selection over its slice of global memory (1 .. 4096: a test sends 20-value segments down it).
  *   "pts_tile_order"     0 (default) the 4-tap gather of a raster-point plan walks the selected points in cloud order, 1 ordered by raster
  *                        tile (32 x 32 pixels) of their unshifted position; read when a selection is made (create / subsample). */
 #pragma once

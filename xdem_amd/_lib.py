@@ -142,6 +142,15 @@ def lib() -> ctypes.CDLL:
         L.xdemhip_perbin_lookup.argtypes = [c_ctx, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int64,
                                             ctypes.POINTER(ctypes.c_int), c_dp, c_dp, c_dp, ctypes.c_char_p, ctypes.c_int, ctypes.c_void_p,
                                             c_i64p, ctypes.c_int]
+        L.xdemhip_bw_create.argtypes = [c_ctx, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
+                                        ctypes.c_int, c_i64p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), c_i64p]
+        L.xdemhip_bw_nk_step.argtypes = [ctypes.c_void_p, ctypes.c_void_p, c_dp, c_dp, ctypes.c_double, ctypes.c_double, ctypes.c_int,
+                                         c_dp, c_i64p, c_dp, c_dp, c_dp, c_i64p, c_dp]
+        L.xdemhip_bw_get_aux.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        L.xdemhip_bw_destroy.argtypes = [ctypes.c_void_p]
+        L.xdemhip_bw_destroy.restype = None
+        L.xdemhip_bw_apply.argtypes = [c_ctx, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, c_dp, c_dp, c_dp, c_dp,
+                                       ctypes.c_void_p, ctypes.c_int]
         L.xdemhip_shift_bilinear.argtypes = [c_ctx, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_double,
                                              ctypes.c_double, ctypes.c_double, ctypes.c_void_p, ctypes.c_int]
         L.xdemhip_set_allreduce.argtypes = [c_ctx, ctypes.c_void_p, ctypes.c_void_p]
@@ -525,7 +534,7 @@ class Context:
             self._L.xdemhip_device_free(self.handle, ctypes.c_void_p(p))
 
     TEST_SWITCHES = frozenset(("terrain_stream", "terrain_order", "terrain_ring_wait", "terrain_window_lds", "nk_narrow",
-                               "vario_grid", "vario_runs", "vario_sort", "hypso_seg_lds", "pts_tile_order"))
+                               "vario_grid", "vario_runs", "vario_sort", "hypso_seg_lds", "pts_tile_order", "bw_seg_lds"))
 
     def set_option(self, name: str, value: int) -> None:
         """Option of the library (``xdemhip_set_option``: the fourteen names of include/xdemhip.h), e.g. ``("selection", 1)`` -- or,

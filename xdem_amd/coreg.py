@@ -39,6 +39,7 @@ from .rigid import (LZD, apply_matrix, invert_matrix, matrix_from_translations_r
 from .icp import ICP, nearest  # noqa: F401
 from .cpd import CPD, cpd_expectation, cpd_update  # noqa: F401
 from .epc import EPC  # noqa: F401
+from .blockwise import BlockwiseCoreg, tiling_grid  # noqa: F401
 from .spatialstats import nmad
 
 TWO_CLOUDS = ("This pre-processing function is only intended for raster-point or raster-raster methods, "

@@ -320,6 +320,7 @@ const XdOpt kTestSwitches[] = {
     {"vario_runs", 0, 1, &xdemhip_ctx::vario_runs, "vario_runs: 0 or 1"},
     {"vario_sort", 0, 1, &xdemhip_ctx::vario_sort, "vario_sort: 0 or 1"},
     {"pts_tile_order", 0, 1, &xdemhip_ctx::pts_tile_order, "pts_tile_order: 0 or 1"},
+    {"bw_seg_lds", 0, 4096, &xdemhip_ctx::bw_seg_lds, "bw_seg_lds: 0 (default: 4096) or 1 to 4096 values"},
     {"hypso_seg_lds", 0, 16384, &xdemhip_ctx::hypso_seg_lds, "hypso_seg_lds: 0 (default: 8192) or 1 to 16384 values"},
 };
 int xd_set_from(xdemhip_ctx* ctx, const XdOpt* tab, size_t n, const char* name, int value, bool* found) {

@@ -51,6 +51,7 @@ struct xdemhip_ctx {
     int nk_nan_rule = 0;     // option "nk_nan_rule": nodata spreading of the bilinear taps (nuthkaab.hip): 0 4tap, 1 weighted, 2 dilate3x3, 3 dilate_cross
     int pts_tile_order = 0;  // test switch "pts_tile_order": 1 the gather of a raster-point plan walks its points by raster tile, 0 in cloud order (ptsplan.hip)
     int hypso_seg_lds = 0;   // test switch "hypso_seg_lds": longest segment of xdemhip_hypso_segments sorted in LDS (values; 0 = 8192), longer ones take the radix selection
+    int bw_seg_lds = 0;      // test switch "bw_seg_lds": longest (tile, bin) segment of xdemhip_bw_nk_step sorted in LDS (values; 0 = 4096), longer ones take the radix selection
     int selection_mode = 0;  // 0 auto (bracketed for large inputs), 1 plain digit passes only, 2 degenerate brackets (tests the
                              // fallback), 3 bracketed whatever the per-bin sample size (2 and 3: test switches)
     // Deferred device-to-host results (xd_d2h / xd_sync below): small result blocks land in one pinned staging buffer with

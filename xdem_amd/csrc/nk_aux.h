@@ -12,6 +12,28 @@
 namespace xd {
 
 // ---- aux: gradient -> slope tangent, aspect, valid mask --------------------------------------------------------
+// One pixel (i, j) of an H x W raster held row-major in `ref`, the pixel at index p (rows W apart): slope tangent and aspect from np.gradient
+// with unit spacing, and whether the pixel is valid.  `tv` is the to-be-aligned sample of the pixel, `inl` its inlier flag.
+template <typename T>
+__device__ __forceinline__ bool nk_aux_pixel(const T* __restrict__ ref, int64_t p, int64_t i, int64_t j, int64_t H, int64_t W, T tv, bool inl,
+                                             T& st, T& as) {
+    const T c = ref[p];
+    T gy, gx;
+    // np.gradient, unit spacing: central differences inside, one-sided on the borders of the RASTER
+    if (i == 0) gy = t_sub(ref[p + W], c);
+    else if (i == H - 1) gy = t_sub(c, ref[p - W]);
+    else gy = t_div(t_sub(ref[p + W], ref[p - W]), (T)2);
+    if (j == 0) gx = t_sub(ref[p + 1], c);
+    else if (j == W - 1) gx = t_sub(c, ref[p - 1]);
+    else gx = t_div(t_sub(ref[p + 1], ref[p - 1]), (T)2);
+    st = t_sqrt(t_add(t_mul(gx, gx), t_mul(gy, gy)));
+    // aspect = arctan2(-gx, gy) + pi: correctly rounded to the DEM dtype from the float64 arctangent
+    as = (T)atan2(-(double)gx, (double)gy);
+    as = t_add(as, (T)3.14159265358979323846);
+    if (fabs((double)st) <= 1e-8) st = (T)NAN;  // np.isclose(slope_tan, 0) -> NaN (affine.py:578-579)
+    return inl && t_finite(c) && t_finite(tv) && t_finite(st) && t_finite(as);
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void nk_aux_kernel(const T* __restrict__ ref, const T* __restrict__ tba,
                                                      const uint8_t* __restrict__ inlier, NkGeom g,
@@ -25,21 +47,8 @@ __global__ __launch_bounds__(256) void nk_aux_kernel(const T* __restrict__ ref, 
     if (j < W)
     for (int64_t i = row0 + blockIdx.y; i < row1; i += gridDim.y) {
         const int64_t p = (i - g.roff) * W + j;
-        const T c = ref[p];
-        T gy, gx;
-        // np.gradient, unit spacing: central differences inside, one-sided on the borders of the RASTER
-        if (i == 0) gy = t_sub(ref[p + W], c);
-        else if (i == H - 1) gy = t_sub(c, ref[p - W]);
-        else gy = t_div(t_sub(ref[p + W], ref[p - W]), (T)2);
-        if (j == 0) gx = t_sub(ref[p + 1], c);
-        else if (j == W - 1) gx = t_sub(c, ref[p - 1]);
-        else gx = t_div(t_sub(ref[p + 1], ref[p - 1]), (T)2);
-        T st = t_sqrt(t_add(t_mul(gx, gx), t_mul(gy, gy)));
-        // aspect = arctan2(-gx, gy) + pi: correctly rounded to the DEM dtype from the float64 arctangent
-        T as = (T)atan2(-(double)gx, (double)gy);
-        as = t_add(as, (T)3.14159265358979323846);
-        if (fabs((double)st) <= 1e-8) st = (T)NAN;  // np.isclose(slope_tan, 0) -> NaN (affine.py:578-579)
-        const bool ok = (inlier ? inlier[p] != 0 : true) && t_finite(c) && t_finite(tba[p]) && t_finite(st) && t_finite(as);
+        T st, as;
+        const bool ok = nk_aux_pixel<T>(ref, p, i, j, H, W, tba[p], inlier ? inlier[p] != 0 : true, st, as);
         slope_tan[p] = st;
         aspect[p] = as;
         valid[p] = ok ? 1 : 0;
