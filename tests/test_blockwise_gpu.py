@@ -152,6 +152,20 @@ def test_long_segments_take_the_radix_selection(mods, dtype):
     assert max(int(w["counts"].max()) for w in want) > 20 > min(int(w["counts"].min()) for w in want)
 
 
+@pytest.mark.parametrize("dtype", ["float32", "float64"])
+def test_segments_on_both_sides_of_the_default_lds_limit(mods, dtype):
+    """150 x 200 as ONE tile in 6 aspect bins, no switch set: segments of 3795 to 4902 values, so some are sorted in LDS filled past half
+    of BW_SEG_LDS = 4096 keys and some are longer than it and take the radix selection over global memory at the limit the product
+    runs with (tests/test_blockwise_host.py checks the counts without a GPU)."""
+    _lib, blockwise, _ = mods
+    ref, tba, _ = _case("B", dtype)
+    assert bo.tiling_grid(ref.shape, 256).reshape(-1, 4).shape[0] == 1
+    assert _lib.default_context().options.get("bw_seg_lds", 0) == 0
+    _, want = _check_step(blockwise, ref, tba, None, 256, decided("nk_nan_rule"), np.ones(1, dtype=np.uint8), n_bins=6)
+    counts = want[0]["counts"]
+    assert counts.max() > 4096 >= counts.min() > 2048
+
+
 def _deviation(b, want):
     h = max(np.nanmax(np.abs(b.shifts_x - want["shift_x"])), np.nanmax(np.abs(b.shifts_y - want["shift_y"]))) / bc.RES
     return h, np.nanmax(np.abs(b.shifts_z - want["shift_z"]))

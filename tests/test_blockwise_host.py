@@ -203,3 +203,16 @@ def test_route_eligibility_is_decided_from_the_step():
     assert not cand(coreg.NuthKaab(subsample=0.5))
     assert not cand(coreg.NuthKaab(initial_shift=(1.0, 2.0)))
     assert not cand(coreg.VerticalShift()) and not cand(coreg.DhMinimize())
+
+
+@pytest.mark.parametrize("dtype", ["float32", "float64"])
+def test_single_tile_case_crosses_the_lds_limit_of_the_segment_sort(dtype):
+    """tests/test_blockwise_gpu.py::test_segments_on_both_sides_of_the_default_lds_limit: 150 x 200 as one tile in 6 aspect bins has
+    segments on both sides of BW_SEG_LDS = 4096 (csrc/blockwise.hip), all past half of it."""
+    ref, tba = bc.fit_case(150, 200, np.dtype(dtype).type)
+    tiles = bo.tiling_grid(ref.shape, 256).reshape(-1, 4)
+    assert tiles.tolist() == [[0, 150, 0, 200]]
+    (w,) = bo.step_tiles(ref, tba, None, tiles, np.ones(1, dtype=np.uint8), np.zeros(1), np.zeros(1), (bc.RES, bc.RES), 6)
+    counts = w["counts"]
+    assert counts.tolist() == [4640, 3828, 3919, 4902, 3795, 3927]   # (at zero offsets under the decided NaN rule, either dtype)
+    assert counts.max() > 4096 >= counts.min() > 2048

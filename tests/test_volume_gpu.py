@@ -6,7 +6,9 @@ glacier's skip decision, counts and medians, and the fill pass fed the recorded 
 float64 on the device and float32, summed pairwise in sample order, upstream: its largest deviation from the fixtures, relative to
 the bin's standard deviation, and through it the largest deviation of the fitted coefficients, the model tables and the filled
 pixels, relative to the glacier's largest model value, were measured on an MI355X (volume_cases.MEASURED: float32 1.2e-7 and
-1.5e-6, float64 2.2e-16 and 9.6e-8); each bar is 4 x its figure."""
+1.5e-6, float64 2.2e-16 and 9.6e-8); each bar is 4 x its figure.  The figures of the two mixed pairs (float32 dDEM with a float64
+reference and the reverse, 61 x 83) are those of the NumPy restatement against the pairs' fixtures, computed on the CPU
+(volume_cases.regional_bars)."""
 import numpy as np
 import pytest
 
@@ -15,7 +17,7 @@ import volume_oracle as vo
 
 pytestmark = pytest.mark.gpu
 
-CASES = [(H, W, dt) for (H, W) in vc.SHAPES for dt in vc.DTYPES]
+CASES = [(H, W, dt) for (H, W) in vc.SHAPES for dt in vc.DTYPES] + [(61, 83, dt) for dt in vc.MIXED]
 
 
 @pytest.fixture(scope="module")
@@ -33,7 +35,7 @@ def _put(a):
 
 def _check_regional(got, ref, c, dtype):
     std_dev, model_dev = vc.regional_deviations(got, ref, c)
-    std_bar, model_bar = (4 * f for f in vc.MEASURED[dtype])
+    std_bar, model_bar = vc.regional_bars(dtype, ref)
     print(f"std deviation {std_dev:.3e} (bar {std_bar:.3e}), model deviation {model_dev:.3e} (bar {model_bar:.3e})")
     assert std_dev <= std_bar and model_dev <= model_bar
 
@@ -61,7 +63,7 @@ def test_fill_pass_fed_the_recorded_tables(vol, H, W, dtype):
     xs, ys = [g[f"glacier_{i}_x"] for i in ids], [g[f"glacier_{i}_y"] for i in ids]
     with vol.HypsoPlan(c["ddem"], c["ref"], labels=c["labels"]) as plan:
         for mode, name in ((0, "regional_filled"), (1, "regional_idealized")):
-            out = plan.fill(mode, ids, xs, ys, False, np.dtype(dtype)).reshape(H, W)
+            out = plan.fill(mode, ids, xs, ys, False, vc.ddem_dtype(dtype)).reshape(H, W)
             vc.assert_same_bits({name: out}, g)
 
 
@@ -104,6 +106,33 @@ def test_device_input_gives_the_host_input_bits_on_the_device(vol, dtype):
     for lab in (_put(c["labels"].astype(np.int64)), _put(c["labels"].astype(np.float64))):
         again = vol.norm_regional_hypsometric_interpolation(_put(c["ddem"]), _put(c["ref"]), lab, regional_signal=vc.signal_frame(g))
         assert torch.equal(torch.nan_to_num(again, nan=1e30), torch.nan_to_num(out, nan=1e30))
+
+
+@pytest.mark.parametrize("dtype", vc.MIXED)
+def test_mixed_dtype_pairs_on_device_tensors(vol, dtype):
+    """A float32 dDEM with a float64 reference and the reverse, as device tensors, against the fixtures of the pair: the
+    (float, double) and (double, float) instances of the statistics, grouping and fill kernels.  hypsometric_interpolation promotes
+    its output to float64 for both pairs (the model's value rounded to the reference's dtype first); the regional fill keeps the
+    dDEM's dtype."""
+    import torch
+
+    c, g = vc.case(61, 83, dtype), vc.golden(61, 83, dtype)
+    assert (c["ddem"].dtype, c["ref"].dtype, c["ref_voids"].dtype) == (vc.ddem_dtype(dtype), vc.ref_dtype(dtype), vc.ref_dtype(dtype))
+    hi = vol.hypsometric_interpolation(_put(c["ddem"]), _put(c["ref_voids"]), _put(c["mask"]))
+    assert isinstance(hi, torch.Tensor) and hi.is_cuda and hi.dtype == torch.float64 and tuple(hi.shape) == (61, 83)
+    data = hi.cpu().numpy()
+    vc.assert_same_bits({"hypso_interp_data": data, "hypso_interp_mask": ~np.isfinite(data)}, g)
+    masked = vol.hypsometric_interpolation(c["ddem"], c["ref_voids"], c["mask"])
+    assert isinstance(masked, np.ma.MaskedArray) and masked.dtype == np.float64
+    vc.assert_same_bits({"hypso_interp_data": np.asarray(masked.data), "hypso_interp_mask": np.ma.getmaskarray(masked)}, g)
+    dev = vc.run_binning(vol, c, _put)
+    dev.update(vc.run_area(vol, c, g, _put))
+    dev.update(vc.run_signal(vol, c, _put))
+    vc.assert_same_bits(dev, g)
+    reg = vc.run_regional(vol, c, g, _put)
+    assert reg["regional_filled"].dtype == vc.ddem_dtype(dtype)
+    _check_regional(reg, g, c, dtype)
+    vc.assert_same_bits(reg, vc.run_regional(vol, c, g))
 
 
 def test_two_runs_return_the_same_bits(vol):

@@ -9,6 +9,9 @@ The reference is imported through oracle/_refimport.py as it stands; this tool a
 ``hypsometric_interpolation`` calls ``xdem.volume.hypsometric_binning``.  rasterio is a stub: ``idw_interpolation`` and
 ``local_hypsometric_interpolation`` cannot run here and nothing of them is recorded.
 
+61 x 83 is also recorded for the two mixed pairs -- the dDEM of the case of one dtype with ``ref`` / ``ref_voids`` of the case of the other,
+labels and mask shared -- as tests/golden/volume_61x83_<ddem dtype>_<ref dtype>.npz.
+
 Recorded per shape and dtype (tests/golden/volume_<H>x<W>_<dtype>.npz):
   * hypsometric_binning for kind "fixed", "count", "quantile", "custom" and a plain edge array (on the reference with voids): the
     value and count columns and the interval ends;
@@ -43,6 +46,8 @@ sys.path.insert(0, os.path.join(ROOT, "oracle"))
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 SHAPES = ((61, 83), (129, 193))
+MIXED_SHAPE = (61, 83)
+MIXED_PAIRS = (("float32", "float64"), ("float64", "float32"))   # (dDEM, reference)
 FUNCTIONS = ("hypsometric_binning", "interpolate_hypsometric_bins", "fit_hypsometric_bins_poly", "calculate_hypsometry_area",
              "hypsometric_interpolation", "get_regional_hypsometric_signal", "norm_regional_hypsometric_interpolation")
 CUSTOM_EDGES = np.arange(900.0, 1800.0, 100.0)
@@ -140,10 +145,20 @@ def glacier_records(volume, ddem, ref, index_map, regional_signal, min_coverage=
     return records
 
 
-def record_case(volume, H: int, W: int, dtype) -> dict:
+def mixed_case(H: int, W: int, ddem_dtype, ref_dtype) -> dict:
+    """The dDEM of the case of one dtype with the reference rasters of the case of the other; labels and mask are the same in both."""
     from xdem_amd import synth
 
-    case = synth.volume_case(H, W, dtype)
+    case = dict(synth.volume_case(H, W, np.dtype(ddem_dtype)))
+    if np.dtype(ref_dtype) != np.dtype(ddem_dtype):
+        other = synth.volume_case(H, W, np.dtype(ref_dtype))
+        assert np.array_equal(other["labels"], case["labels"]) and np.array_equal(other["mask"], case["mask"])
+        case["ref"], case["ref_voids"] = other["ref"], other["ref_voids"]
+    return case
+
+
+def record_case(volume, H: int, W: int, dtype, ref_dtype=None) -> dict:
+    case = mixed_case(H, W, dtype, dtype if ref_dtype is None else ref_dtype)
     ddem, ref, ref_voids, labels, mask = (case[k] for k in ("ddem", "ref", "ref_voids", "labels", "mask"))
     out: dict = {}
     frames = {}
@@ -218,6 +233,11 @@ def main() -> None:
             path = os.path.join(GOLDEN, f"volume_{H}x{W}_{np.dtype(dtype).name}.npz")
             np.savez_compressed(path, **out)
             print(path, os.path.getsize(path), "bytes;", int((~out["glacier_skipped"]).sum()), "of", len(out["glacier_ids"]), "glaciers fitted")
+    for ddem_dtype, ref_dtype in MIXED_PAIRS:
+        out = record_case(volume, *MIXED_SHAPE, ddem_dtype, ref_dtype)
+        path = os.path.join(GOLDEN, f"volume_{MIXED_SHAPE[0]}x{MIXED_SHAPE[1]}_{ddem_dtype}_{ref_dtype}.npz")
+        np.savez_compressed(path, **out)
+        print(path, os.path.getsize(path), "bytes;", int((~out["glacier_skipped"]).sum()), "of", len(out["glacier_ids"]), "glaciers fitted")
     with open(os.path.join(GOLDEN, "signatures_volume.json"), "w") as f:
         json.dump({name: signature_of(getattr(volume, name)) for name in FUNCTIONS}, f, indent=1)
         f.write("\n")
