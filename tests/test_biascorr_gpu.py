@@ -201,7 +201,8 @@ def test_poly2d_apply_device_tensors():
     assert np.array_equal(poly2d_apply(t, params).cpu().numpy(), want, equal_nan=True)
     out = torch.empty_like(t)
     assert poly2d_apply(t, params, out=out) is out and np.array_equal(out.cpu().numpy(), want, equal_nan=True)
-    # odd widths take the scalar kernel: the same bits
+    # 192 columns (W % 4 == 0) take the four-wide kernel on both sides: the device path against the host path, the same bits.  Both
+    # kernels against NumPy: tests/test_deramp_routes_gpu.py
     assert np.array_equal(poly2d_apply(t[:, :-1].contiguous(), params).cpu().numpy(), poly2d_apply(G["tba"][:, :-1], params), equal_nan=True)
     for bad in (t.half(), t.to(torch.bfloat16), t.to(torch.int32), t.t(), t[:, ::2], t.reshape(-1), t.cpu()):
         with pytest.raises(ValueError):

@@ -368,3 +368,85 @@ def test_nuth_kaab_closes_the_plan_when_the_draw_fails(monkeypatch):
     with pytest.raises(RuntimeError, match="draw failed"):
         coreg.nuth_kaab(np.zeros((10, 10)), np.zeros((10, 10)), None, (1.0, 1.0), subsample=0.5, random_state=0)
     assert closed == [True]
+
+
+# ---- the moments oracle of the device tests (tests/deramp_oracle.py) ---------------------------------------------------------------
+def _pairwise_additions(n):
+    """Additions a term passes through in np.sum over n contiguous values: 16 in one of the 8 accumulators of a 128-value block, 3 to
+    combine them, one per level of the pairwise tree above the blocks; + 1 for the product that forms the term."""
+    import math
+
+    return 16 + 3 + max(0, math.ceil(math.log2(max(n / 128.0, 1.0)))) + 1
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("masked", [False, True])
+def test_deramp_oracle_matches_numpy_moments_within_the_bound(dtype, masked):
+    """The longdouble oracle against this module's float64 ``_moments`` (whose error the same bound covers: its coordinate is one
+    division, its powers are correctly rounded ones), and the oracle's row-block and rank forms against its own whole-raster form."""
+    import deramp_oracle as do
+
+    H, W, order = 37, 61, 5
+    ref, tba, inl = do.make_pair(H, W, dtype, seed=7, masked=masked)
+    want = do.moments(ref, tba, inl, order)
+    valid = do.valid_mask(ref, tba, inl)
+    assert want.count == int(valid.sum()) and want.M[0, 0] == want.count and 0 < want.count < H * W
+    y, x = np.nonzero(valid)
+    M, R = _moments(x.astype(float), y.astype(float), (ref[valid] - tba[valid]).astype(np.float64), order, (H, W))
+    bM, bR = do.moments_bound(want, _pairwise_additions(want.count))
+    assert np.all(np.abs(M - want.M) <= bM) and np.all(np.abs(R - want.R) <= bR)
+    # lower orders are the leading blocks
+    low = do.moments(ref, tba, inl, 2)
+    assert np.array_equal(low.M, do.sub(want, 2).M) and np.array_equal(low.R, do.sub(want, 2).R)
+    # rows [r0, r1) with their offset = the whole raster with the other rows masked out
+    r0, r1 = 11, 29
+    rows_only = np.zeros((H, W), dtype=bool)
+    rows_only[r0:r1] = True if inl is None else inl[r0:r1]
+    a = do.moments(ref[r0:r1], tba[r0:r1], None if inl is None else inl[r0:r1], order, row_offset=r0, H_global=H)
+    b = do.moments(ref, tba, rows_only, order)
+    tiny = np.longdouble(2.0 ** -58)
+    assert a.count == b.count and np.all(np.abs(a.M - b.M) <= tiny * b.magM) and np.all(np.abs(a.R - b.R) <= tiny * b.magR)
+    # ranks: flatnonzero(valid)[unique ranks]
+    ranks = np.array([5, 0, want.count - 1, 5, 17, 17, 400])
+    picked = np.zeros(H * W, dtype=bool)
+    picked[np.flatnonzero(valid)[np.unique(ranks)]] = True
+    a = do.moments(ref, tba, inl, order, ranks=ranks)
+    b = do.moments(ref, tba, picked.reshape(H, W), order)
+    assert a.count == b.count == 5 and np.array_equal(a.M, b.M) and np.array_equal(a.R, b.R)
+
+
+@pytest.mark.parametrize("num_cu", [64, 256, 304])
+def test_deramp_count_moment_is_exact_on_every_tested_shape(num_cu):
+    """The bound of M[0, 0] is below 0.5 on every moments shape of tests/test_deramp_routes_gpu.py, on either route a shape can take
+    and for every device size: the device tests may ask for M[0, 0] == count exactly."""
+    import deramp_oracle as do
+
+    for H, W, vec in do.moments_shapes(num_cu):
+        for route in {vec, False}:
+            assert do.count_bound(H * W, do.additions_rows(H, W, route, num_cu)) < 0.5, (H, W, route)
+    side, k_large = do.list_large_case(num_cu)
+    assert k_large + 1000 <= 0.99 * side * side and do.list_grid(k_large, num_cu)[0] > 256
+    for k in do.LIST_SMALL_K + (k_large,):
+        assert do.count_bound(k, do.additions_list(k, num_cu)) < 0.5, k
+    assert do.count_bound(side * side, do.additions_rows(side, side, True, num_cu)) < 0.5
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_deramp_oracle_bound_notices_one_dropped_pixel(dtype):
+    """Dropping one valid pixel -- a corner, the centre, the last pixel of a row -- moves at least one entry of (M, R) by more than
+    its bound: a kernel that loses a pixel cannot pass the device tests."""
+    import deramp_oracle as do
+
+    H, W, order = 40, 64, 5
+    ref, tba, _ = do.make_pair(H, W, dtype, seed=11, nan_frac=0.0)
+    want = do.moments(ref, tba, None, order)
+    assert want.count == H * W
+    bM, bR = do.moments_bound(want, do.additions_rows(H, W, True, 256))
+    for r, c in ((0, 0), (H // 2, W // 2), (17, W - 1)):
+        inl = np.ones((H, W), dtype=bool)
+        inl[r, c] = False
+        less = do.moments(ref, tba, inl, order)
+        moved_m, moved_r = np.abs(less.M - want.M) > bM, np.abs(less.R - want.R) > bR
+        assert less.count == want.count - 1 and (moved_m.any() or moved_r.any())
+        # not the count alone: the right-hand side feels it too
+        assert moved_m[0, 0] and moved_r[0, 0], (r, c)
