@@ -783,6 +783,39 @@ void xdemhip_binstats_destroy(xdemhip_binstats* plan);
 int xdemhip_nmad(xdemhip_ctx* ctx, const void* values, int dtype, int64_t n, double nfact, double abs_limit, int memspace,
                  double* median, double* nmad, int64_t* count);
 
+/* The statistics of one raster (geoutils' Raster.get_stats, which xdem's DEM inherits: xdem/workflows/topo.py:291,
+ * accuracy.py:243-381) from fused passes and a multi-rank exact selection (csrc/rasterstats.hip, csrc/multi_select.h).
+ * A pixel is VALID when its value is finite (+-Inf is not), differs from `nodata` (has_nodata != 0) and total_mask (uint8, or NULL:
+ * all ones) is non-zero there; the value statistics are over the valid pixels whose `inlier` byte (uint8, or NULL) is non-zero too.
+ *   n, n_valid, n_inlier   pixels behind the value statistics; valid pixels whatever `inlier` says; non-zero bytes of `inlier`
+ *                          (n_values without one)
+ *   min, max               exact
+ *   sum, sumsq, sumdev2    float64 sums of v, v^2 and (v - sum / n)^2, the squares formed in float64 from the widened value, added in
+ *                          one fixed order: two calls return the same bits
+ *   med_lo, med_hi         the order statistics of ranks (n - 1) / 2 and n / 2;  median = their mean in the value dtype (np.median)
+ *   q_lo[i], q_hi[i]       the order statistics of ranks lo = floor((n - 1) * quantiles[i]) (one float64 multiply) and
+ *                          min(lo + 1, n - 1): what np.percentile(..., method="linear") interpolates between; nq <= XDEMHIP_STATS_MAXQ
+ *                          quantiles in [0, 1]
+ *   mad_lo, mad_hi         the same two ranks of |v - median|, formed in the value dtype;  nmad = nfact * their mean, rounded as
+ *                          xdemhip_nmad rounds it
+ *   reads                  full reads of the raster the call made;  route[r] of round r (0: v, 1: |v - median|): 1 plain digit
+ *                          passes, 0 bracketed, 2 bracketed first and then plain (a bracket missed or the candidates overflowed)
+ * The route follows the "selection" option -- 0: bracketed from 2^22 pixels on, 1: plain, 2: collapsed brackets (the fall-back), 3:
+ * bracketed at every size -- and never changes a bit of the result.  n == 0 or no valid pixel: counts 0, every value NaN, XDEMHIP_OK.
+ * With a reduction hook installed: XDEMHIP_EUNSUPPORTED (the statistics of a partitioned raster are not provided).
+ * XDEMHIP_DEVICE: values and both masks are device arrays; the call returns synchronised on the context's stream. */
+#define XDEMHIP_STATS_MAXQ 4
+typedef struct xdemhip_raster_stats_out {
+    int64_t n, n_valid, n_inlier;
+    double min, max, sum, sumsq, sumdev2, med_lo, med_hi, median, mad_lo, mad_hi, nmad;
+    double q_lo[XDEMHIP_STATS_MAXQ], q_hi[XDEMHIP_STATS_MAXQ];
+    double reads;
+    int32_t route[2];
+} xdemhip_raster_stats_out;
+int xdemhip_raster_stats(xdemhip_ctx* ctx, const void* values, int dtype, int64_t n_values, const uint8_t* total_mask,
+                         const uint8_t* inlier, int has_nodata, double nodata, const double* quantiles, int nq, double nfact,
+                         int memspace, xdemhip_raster_stats_out* out);
+
 /* out[p] = scale * f(vars[0][p], ..., vars[n_dims-1][p]) for the multilinear interpolant f on a regular grid: the evaluation
  * scipy.interpolate.RegularGridInterpolator(axes, grid_values, method="linear", bounds_error=False, fill_value=None) performs
  * for the error function returned by interp_nd_binning (xdem/spatialstats.py:417-421) and applied to whole rasters by

@@ -73,6 +73,14 @@ class VarSrc(ctypes.Structure):
                 ("sin_t", ctypes.c_double), ("res_x", ctypes.c_double), ("res_y", ctypes.c_double), ("offset", ctypes.c_double)]
 
 
+class RasterStatsOut(ctypes.Structure):
+    """``xdemhip_raster_stats_out``: what ``xdemhip_raster_stats`` returns."""
+
+    _fields_ = [("n", ctypes.c_int64), ("n_valid", ctypes.c_int64), ("n_inlier", ctypes.c_int64)] + \
+               [(k, ctypes.c_double) for k in ("min", "max", "sum", "sumsq", "sumdev2", "med_lo", "med_hi", "median", "mad_lo", "mad_hi", "nmad")] + \
+               [("q_lo", ctypes.c_double * 4), ("q_hi", ctypes.c_double * 4), ("reads", ctypes.c_double), ("route", ctypes.c_int32 * 2)]
+
+
 def lib() -> ctypes.CDLL:
     """Load (once) and return the shared library with argtypes declared."""
     global _lib
@@ -192,6 +200,8 @@ def lib() -> ctypes.CDLL:
                                              c_dp, c_dp, c_dp, c_dp, ctypes.c_int]
         L.xdemhip_nmad.argtypes = [c_ctx, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_double, ctypes.c_double,
                                    ctypes.c_int, c_dp, c_dp, c_i64p]
+        L.xdemhip_raster_stats.argtypes = [c_ctx, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                           ctypes.c_double, c_dp, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.POINTER(RasterStatsOut)]
         L.xdemhip_interp_grid_linear.argtypes = [c_ctx, ctypes.c_int, c_dp, c_ip, c_dp, ctypes.POINTER(ctypes.c_void_p), c_ip,
                                                  ctypes.c_int64, ctypes.c_double, c_dp, ctypes.c_int]
         L.xdemhip_dh_create.argtypes = [c_ctx, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,

@@ -17,6 +17,7 @@ import numpy as np
 from . import coreg as _coreg
 from ._coregbase import _Step
 from . import spatialstats as _ss
+from . import stats as _stats
 from . import terrain
 
 
@@ -121,6 +122,25 @@ class DEM:
 
     def get_terrain_attribute(self, attribute, **kwargs: Any):
         return terrain.get_terrain_attribute(self, attribute=attribute, **kwargs)
+
+    # ---- raster statistics (geoutils' Raster.get_stats, inherited by xdem.DEM: xdem/workflows/topo.py:291) ------------
+    def get_stats(self, stats_name=None, inlier_mask=None, band: int = 1, counts=None):
+        """Statistics of the elevations on the GPU (``xdem_amd.stats.get_stats`` with this DEM's data and nodata): a dict, or the bare
+        value for a single name.  ``band`` other than 1 raises (a DEM has one band); ``counts`` = (valid, total), if given, overrides
+        the "Valid count" and "Total count" keys."""
+        if band != 1:
+            raise ValueError(f"band must be 1: a DEM has a single band (got {band!r})")
+        mask = None if inlier_mask is None else np.asarray(getattr(inlier_mask, "data", inlier_mask), dtype=bool)
+        out = _stats.get_stats(self.data, stats_name, inlier_mask=mask, nodata=None if self.nodata is None else float(self.nodata))
+        if counts is not None:
+            override = {"Valid count": counts[0], "Total count": counts[1]}
+            if isinstance(out, dict):
+                for name in out:
+                    if isinstance(name, str) and _stats._NAMES.get(_stats._norm(name)) in override:
+                        out[name] = override[_stats._NAMES[_stats._norm(name)]]
+            elif isinstance(stats_name, str) and _stats.resolve_name(stats_name) in override:
+                out = override[_stats.resolve_name(stats_name)]
+        return out
 
     # ---- co-registration forwarder (xdem/dem.py:621-665) -----------------------------------------------------------
     def coregister_3d(self, reference_elev: "DEM", coreg_method=None, inlier_mask=None, bias_vars=None, random_state=None,
