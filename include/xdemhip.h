@@ -787,6 +787,8 @@ int xdemhip_nmad(xdemhip_ctx* ctx, const void* values, int dtype, int64_t n, dou
  * accuracy.py:243-381) from fused passes and a multi-rank exact selection (csrc/rasterstats.hip, csrc/multi_select.h).
  * A pixel is VALID when its value is finite (+-Inf is not), differs from `nodata` (has_nodata != 0) and total_mask (uint8, or NULL:
  * all ones) is non-zero there; the value statistics are over the valid pixels whose `inlier` byte (uint8, or NULL) is non-zero too.
+ * `nodata` is rounded to `dtype` before it is compared (NumPy's `v == nodata`): for a float32 raster 0.1 matches the pixels that hold
+ * (float)0.1; a NaN `nodata` matches nothing, and neither does one that rounds to +-Inf (such pixels are not valid anyway).
  *   n, n_valid, n_inlier   pixels behind the value statistics; valid pixels whatever `inlier` says; non-zero bytes of `inlier`
  *                          (n_values without one)
  *   min, max               exact

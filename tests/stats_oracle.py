@@ -10,9 +10,10 @@ import numpy as np
 from xdem_amd import spatialstats, stats
 
 
-def valid_values(values, inlier_mask=None, nodata=None):
-    """(valid-and-inlier values in their dtype, raster order; valid pixels whatever the inlier mask; inlier pixels; all pixels).
-    Valid: finite, not nodata, not masked.  Dtypes other than float32 / float64 are widened to float64."""
+def valid_mask(values, inlier_mask=None, nodata=None):
+    """(values as float32 / float64; valid-and-inlier pixels; valid pixels whatever the inlier mask; inlier pixels or None).
+    Valid: finite, not nodata (`v != nodata` as NumPy decides it: nodata rounded to the dtype of v), not masked.  Dtypes other than
+    float32 / float64 are widened to float64."""
     total_mask = None
     if isinstance(values, np.ma.MaskedArray):
         total_mask = ~np.ma.getmaskarray(values)
@@ -20,18 +21,20 @@ def valid_values(values, inlier_mask=None, nodata=None):
     v = np.asarray(values)
     if v.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
         v = v.astype(np.float64)
-    ok = np.isfinite(v)
+    valid = np.isfinite(v)
     if nodata is not None and not (isinstance(nodata, float) and math.isnan(nodata)):
-        ok &= v != nodata
+        with np.errstate(over="ignore"):
+            valid &= v != v.dtype.type(nodata)
     if total_mask is not None:
-        ok &= total_mask
-    n_valid = int(ok.sum())
-    n_inlier = v.size
-    if inlier_mask is not None:
-        inl = np.asarray(inlier_mask, dtype=bool)
-        n_inlier = int(inl.sum())
-        ok = ok & inl
-    return v[ok], n_valid, n_inlier, int(v.size)
+        valid &= total_mask
+    inl = None if inlier_mask is None else np.asarray(inlier_mask, dtype=bool)
+    return v, (valid if inl is None else valid & inl), valid, inl
+
+
+def valid_values(values, inlier_mask=None, nodata=None):
+    """(valid-and-inlier values in their dtype, raster order; valid pixels whatever the inlier mask; inlier pixels; all pixels)."""
+    v, ok, valid, inl = valid_mask(values, inlier_mask, nodata)
+    return v[ok], int(valid.sum()), int(v.size if inl is None else inl.sum()), int(v.size)
 
 
 def table(values, inlier_mask=None, nodata=None) -> dict:
@@ -91,3 +94,97 @@ def patched():
         yield stats
     finally:
         stats._device_stats = saved
+
+
+# ---- the sample and the brackets of the bracketed route (csrc/select.h, select_run.h, rasterstats.hip), restated ----------------
+# Used to BUILD inputs and to assert that a built input has the property its test is about (the brackets hold, a named one misses,
+# a workgroup's staging buffer fills) -- never to produce an expected value: those stay with `device_block` / `table` above.
+LINE = 8                 # elements of a sampled line (SEL_LINE)
+TILE = 4096              # elements a workgroup takes per step (HIST_THREADS x SEL_TILE)
+FLUSH_EVERY = 4          # steps between two flushes of the staging buffer (SEL_FLUSH_EVERY)
+STAGE_CAP = 8192         # slots of the staging buffer (SEL_STAGE_CAP)
+BRACKET_DIGITS = 3       # leading key bytes the sample's selection fixes
+PASSES = {np.dtype(np.float32): 4, np.dtype(np.float64): 8}
+
+
+def sampled_positions(n: int) -> np.ndarray:
+    """The elements of the 1/64 line sample of an n-element raster, ascending: one LINE-element line per group of 64 lines, picked by
+    the top 6 bits of a multiplicative hash of the group's number (sel_sampled_line / sample_lines_kernel)."""
+    groups = -(-(-(-n // LINE)) // 64)
+    g = np.arange(groups, dtype=np.uint64)
+    line = g * np.uint64(64) + ((g * np.uint64(0x9E3779B97F4A7C15)) >> np.uint64(58))   # (uint64 arrays wrap: mod 2^64)
+    pos = (line[:, None] * np.uint64(LINE) + np.arange(LINE, dtype=np.uint64)[None, :]).reshape(-1).astype(np.int64)
+    return pos[pos < n]
+
+
+def ordered_keys(v: np.ndarray) -> np.ndarray:
+    """key_of: unsigned integers that order as the floats do (negative: every bit flipped; else the sign bit set)."""
+    K = np.uint32 if v.dtype == np.float32 else np.uint64
+    b = np.ascontiguousarray(v).view(K)
+    top = K(1) << K(8 * v.dtype.itemsize - 1)
+    return np.where(b & top, ~b, b | top).astype(K)
+
+
+def rank_pair(c: int, q=None):
+    """ms_rank: the two ranks wanted of c elements -- the medians (q None), or floor((c - 1) q) and the next, clipped."""
+    if q is None:
+        return (c - 1) // 2, c // 2
+    lo = min(int(math.floor(np.float64(c - 1) * np.float64(q))), c - 1)
+    return lo, min(lo + 1, c - 1)
+
+
+def halfwidth(m: int) -> int:
+    """sel_bracket_halfwidth: sample ranks a bracket end is moved by."""
+    return int(3.0 * math.sqrt(8.0 * m)) + 32
+
+
+def predict_round(values_flat, valid_flat, qs, dtype, n_cu: int, flush_every: int = FLUSH_EVERY) -> dict:
+    """One round of the bracketed route on `values_flat` (raster order) of which `valid_flat` are used, for the median and the
+    quantiles `qs`: "holds" -- per bracket, whether both wanted ranks lie in it; "candidates" -- the elements of the union of the
+    brackets; "capacity" of the candidate buffer; "peak" -- the most candidates one workgroup stages between two flushes (the staging
+    buffer holds STAGE_CAP; `flush_every`: steps between two flushes, for asking what another rhythm would stage); "sample" -- the
+    valid sampled elements."""
+    v = np.ascontiguousarray(np.asarray(values_flat).reshape(-1), dtype=dtype)
+    ok = np.asarray(valid_flat).reshape(-1).astype(bool)
+    n = v.size
+    keys = ordered_keys(v)
+    K = keys.dtype.type
+    pos = sampled_positions(n)
+    sk = np.sort(keys[pos][ok[pos]])
+    pk = np.sort(keys[ok])
+    m, c = int(sk.size), int(pk.size)
+    low = K((1 << (8 * (v.dtype.itemsize - BRACKET_DIGITS))) - 1)   # the open bits: zeros at the low end, ones at the high end
+    cand = np.zeros(n, dtype=bool)
+    holds = []
+    for q in [None] + [float(x) for x in qs]:
+        if m:
+            lo, hi = rank_pair(m, q)
+            h = halfwidth(m)
+            klo, khi = K(sk[max(lo - h, 0)] & ~low), K(sk[min(hi + h, m - 1)] | low)
+        else:
+            klo, khi = K(0), ~K(0)   # (an empty sample: everything is a candidate)
+        below, upto = int(np.searchsorted(pk, klo, "left")), int(np.searchsorted(pk, khi, "right"))
+        r0, r1 = rank_pair(c, q) if c else (0, -1)
+        holds.append(bool(below <= r0 and r1 < upto))
+        cand |= ok & (keys >= klo) & (keys <= khi)
+    G = min(-(-n // TILE), 2 * n_cu)
+    tile = np.flatnonzero(cand) // TILE
+    slot = (tile // G // flush_every) * G + tile % G   # (workgroup, group of `flush_every` steps)
+    peak = int(np.bincount(slot).max()) if tile.size else 0
+    return {"holds": holds, "candidates": int(cand.sum()), "capacity": n // 2 + 4096, "peak": peak, "sample": m}
+
+
+def predict_rounds(values, inlier_mask, nodata, qs, n_cu: int, flush_every: int = FLUSH_EVERY):
+    """predict_round for both rounds of one call: the valid values with `qs`, then |v - median| (formed in the value dtype) alone."""
+    v, ok, _, _ = valid_mask(values, inlier_mask, nodata)
+    v, ok = v.reshape(-1), ok.reshape(-1)
+    first = predict_round(v, ok, qs, v.dtype, n_cu, flush_every)
+    if not ok.any():
+        return first, predict_round(v, ok, (), v.dtype, n_cu, flush_every)
+    T = v.dtype.type
+    srt = np.sort(v[ok])
+    n = srt.size
+    med = T((srt[(n - 1) // 2] + srt[n // 2]) / T(2)) if n % 2 == 0 else srt[n // 2]
+    with np.errstate(invalid="ignore", over="ignore"):
+        dev = np.abs(v - med)
+    return first, predict_round(dev, ok, (), v.dtype, n_cu, flush_every)

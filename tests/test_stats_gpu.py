@@ -1,5 +1,6 @@
 """xdem_amd.stats on the GPU: xdemhip_raster_stats (csrc/rasterstats.hip, csrc/multi_select.h) against the NumPy restatement of
-tests/stats_oracle.py, under every value of the "selection" option.
+tests/stats_oracle.py, under every value of the "selection" option (the comparison itself: tests/stats_cases.py, shared with
+test_stats_routes_gpu.py).
 
 Order-statistic keys (Median, Max, Min, 90th percentile, LE90, NMAD) and the counts: bit for bit (by value: +-0.0 compare equal).
 Summed keys: bounds that hold for ANY order of a float64 summation of n terms (u = 2^-53), so derived, not measured:
@@ -9,20 +10,15 @@ Summed keys: bounds that hold for ANY order of a float64 summation of n terms (u
 A dropped or doubled pixel moves a sum by about 1 / n of sum|v|: orders of magnitude outside these bounds at the sizes used here.
 Every route returns the same bits: asserted on the whole output block."""
 import ctypes
-import math
-import struct
 
 import numpy as np
 import pytest
 
 import stats_oracle
+from stats_cases import EXACT, bits, check, check_block, mixed, run, same
 from xdem_amd import DEM, _lib, stats
 
 pytestmark = pytest.mark.gpu
-
-U = 2.0 ** -53
-EXACT = ("Median", "Max", "Min", "90th percentile", "LE90", "NMAD", "Valid count", "Total count", "Percentage valid points") + stats.INLIER_KEYS
-QS = (0.9, 0.95, 0.05)
 
 
 @pytest.fixture(scope="module")
@@ -31,87 +27,6 @@ def ctx():
     c.set_option("selection", 0)
     yield c
     c.set_option("selection", 0)
-
-
-def run(values, mask, nodata, ctx):
-    """get_stats (all keys) and the device block behind it."""
-    blocks = []
-    orig = stats._device_stats
-
-    def recording(inp, q, c=None):
-        blocks.append(orig(inp, q, c))
-        return blocks[-1]
-
-    stats._device_stats = recording
-    try:
-        s = stats.get_stats(values, None, mask, nodata, ctx)
-    finally:
-        stats._device_stats = orig
-    assert len(blocks) == 1
-    return s, blocks[0]
-
-
-def bits(block):
-    flat = [block[k] for k in ("n", "n_valid", "n_inlier")] + [block[k] for k in ("min", "max", "sum", "sumsq", "sumdev2", "med_lo", "med_hi", "median",
-                                                                                  "mad_lo", "mad_hi", "nmad")] + list(block["q_lo"]) + list(block["q_hi"])
-    return [struct.pack("d", float(x)) for x in flat]
-
-
-def same(a, b):
-    return a == b or (isinstance(a, float) and isinstance(b, float) and math.isnan(a) and math.isnan(b))
-
-
-def check(values, ctx, mask=None, nodata=None, routes=None):
-    """Every mode against the oracle and against each other; `routes`: {mode: expected route pair}.  Returns the blocks by mode."""
-    host = values.cpu().numpy() if hasattr(values, "is_cuda") else values
-    want = stats_oracle.table(host, mask, nodata)
-    v, _, _, _ = stats_oracle.valid_values(host, mask, nodata)
-    v64 = v.astype(np.float64)
-    n = int(v.size)
-    blocks = {}
-    try:
-        for mode in (0, 1, 2, 3):
-            ctx.set_option("selection", mode)
-            got, blk = run(values, mask, nodata, ctx)
-            blocks[mode] = blk
-            assert list(got) == list(want)
-            for k in EXACT:
-                if k in want:
-                    assert same(got[k], want[k]), (mode, k, got[k], want[k])
-            if n == 0:
-                assert all(math.isnan(got[k]) for k in stats.STAT_KEYS[:11]), (mode, got)
-                continue
-            sabs, s2 = math.fsum(np.abs(v64)), math.fsum(v64 * v64)
-            mean = math.fsum(v64) / n
-            dev2 = math.fsum((v64 - mean) ** 2)
-            fig = {"Sum": (abs(got["Sum"] - want["Sum"]), n * U * sabs), "Mean": (abs(got["Mean"] - want["Mean"]), U * sabs),
-                   "Sum of squares": (abs(got["Sum of squares"] - s2), 2 * n * U * s2), "sumdev2": (abs(blk["sumdev2"] - dev2), 2 * n * U * dev2),
-                   "RMSE": (abs(got["RMSE"] - want["RMSE"]), want["RMSE"] * (n * U + 4 * U)),
-                   "Standard deviation": (abs(got["Standard deviation"] - want["Standard deviation"]), want["Standard deviation"] * (n * U + 4 * U))}
-            print(f"mode {mode} n {n} route {blk['route']} reads {blk['reads']:.3f}: " + ", ".join(f"{k} {e:.3e} <= {b:.3e}" for k, (e, b) in fig.items()))
-            for k, (e, b) in fig.items():
-                assert e <= b, (mode, k, e, b)
-            assert blk["route"] == (1, 1) if mode == 1 else True, blk["route"]
-            if routes and mode in routes:
-                assert blk["route"] == routes[mode], (mode, blk["route"])
-    finally:
-        ctx.set_option("selection", 0)
-    for mode in (0, 2, 3):
-        assert bits(blocks[mode]) == bits(blocks[1]), (mode, blocks[mode], blocks[1])
-    return blocks
-
-
-def mixed(dtype, shape=(61, 83), seed=1):
-    """~20 % NaN, a nodata value, +-Inf, values quantised to 0.25 (ties), both signs, +-0.0, a subnormal; and an inlier mask."""
-    rng = np.random.default_rng(seed)
-    a = (np.round(rng.normal(scale=300.0, size=shape) * 4) / 4).astype(dtype)
-    a[rng.random(shape) < 0.2] = np.nan
-    flat = a.reshape(-1)
-    flat[5], flat[17], flat[29], flat[31] = np.inf, -np.inf, 0.0, -0.0
-    flat[43] = np.finfo(dtype).smallest_subnormal
-    flat[rng.choice(flat.size, 40, replace=False)] = -9999.0
-    inl = rng.random(shape) < 0.8
-    return a, inl
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
@@ -163,6 +78,9 @@ def test_ranks_that_separate_at_one_digit(ctx, dtype, d):
     b = blocks[1]
     picked = [b["med_lo"], b["med_hi"]] + b["q_lo"] + b["q_hi"]
     assert len(set(picked)) == 8   # ranks 127 128 | 229 230 | 242 243 | 12 13 of 256 distinct values (d = 0: 63 64 | 114 115 | 120 121 | 6 7 of 128)
+    # four quantiles: all ten states, + ranks 76 77 (d = 0: 38 39); below the last digit ten distinct prefixes, so ten tables a pass
+    b = check_block(digit_raster(dtype, d), (0.9, 0.95, 0.05, 0.3), ctx)[1]
+    assert len(set([b["med_lo"], b["med_hi"]] + b["q_lo"] + b["q_hi"])) == 10
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])

@@ -2,7 +2,8 @@
 // computes on the host with several full sorts -- count, min, max, sum, sum of squares, sum of squared deviations, the median, up to
 // four percentiles and the NMAD -- from fused passes and the multi-rank exact selection of multi_select.h.
 //
-// A pixel is VALID when its value is finite, differs from `nodata` (when given) and both byte masks (when given) are non-zero.
+// A pixel is VALID when its value is finite, differs from `nodata` (when given; rounded to the value dtype first) and both byte masks
+// (when given) are non-zero.
 // Round 1 selects the two median ranks and two ranks per quantile of the valid values v; round 2 the two median ranks of
 // |v - median| (formed in the value dtype).  Routes, by the context's "selection" option:
 //   plain (1; and what the others fall back to): the first digit's histogram comes out of the statistics pass itself (round 1: count,
@@ -312,7 +313,7 @@ static int raster_stats_typed(xdemhip_ctx* ctx, const void* values, int64_t n, c
     if (buf.rc) return buf.rc;
     src.par = &ctrl->par;
     src.nodata = (T)nodata;
-    src.has_nodata = has_nodata && nodata == nodata && (double)(T)nodata == nodata;   // (a nodata no value of T can equal never matches)
+    src.has_nodata = has_nodata && nodata == nodata;   // (rounded to T before it is compared, as NumPy's `v == nodata` does)
     src.round = 1;
     src.med = (T)0;
     XD_HIP_CHECK(ctx, hipMemsetAsync(ctrl, 0, offsetof(RsCtrl<T>, hist), ctx->stream));

@@ -11,7 +11,9 @@ installed where this project is developed and nothing offline pins it).  With ``
 ``v64 = v.astype(float64)``: Mean = sum(v64) / n; Median = np.median(v) (the mean of the two middle values taken in T); Max, Min;
 Sum, Sum of squares (float64); 90th percentile = np.percentile(v64, 90); LE90 = np.percentile(v64, 95) - np.percentile(v64, 5);
 NMAD = spatialstats.nmad(v); RMSE = sqrt(sum(v64^2) / n); Standard deviation = sqrt(sum((v64 - mean)^2) / n); Valid count,
-Total count, Percentage valid points.  A pixel is valid when it is finite, is not ``nodata`` and is not masked.
+Total count, Percentage valid points.  A pixel is valid when it is finite, is not ``nodata`` and is not masked.  ``nodata`` is rounded
+to the dtype of the values before it is compared (``v == nodata`` in NumPy, and what ``DEM`` does when it is built): for a float32
+raster ``nodata=0.1`` drops the pixels that hold ``np.float32(0.1)``.
 """
 from __future__ import annotations
 
@@ -112,9 +114,7 @@ class _Input:
         ok = np.isfinite(v)
         if self.nodata is not None:
             with np.errstate(over="ignore"):
-                nd = v.dtype.type(self.nodata)
-            if float(nd) == self.nodata:   # (a nodata no value of the dtype can equal never matches)
-                ok &= v != nd
+                ok &= v != v.dtype.type(self.nodata)   # (rounded to the dtype first: NumPy's `v == nodata`, and DEM's)
         if self.total_mask is not None:
             ok &= self.total_mask.astype(bool)
         if self.inlier is not None:
@@ -180,8 +180,9 @@ def get_stats(values, stats_name=None, inlier_mask=None, nodata=None, ctx: _lib.
 
     `values`: N-D NumPy array, masked array, or a contiguous float32 / float64 CUDA tensor (read in place, on the current torch
     stream); other dtypes are widened to float64.  `inlier_mask` (True = keep) restricts the value statistics; the three count keys
-    keep describing the whole raster and four inlier keys are added.  A callable is applied on the host to the valid values in
-    raster order."""
+    keep describing the whole raster and four inlier keys are added.  `nodata` is rounded to the dtype of the values before it is
+    compared with them, on the device and for a callable alike.  A callable is applied on the host to the valid values in raster
+    order."""
     single = stats_name is not None and (isinstance(stats_name, str) or callable(stats_name))
     names = None if stats_name is None else ([stats_name] if single else list(stats_name))
     keys = None if names is None else [n if callable(n) else resolve_name(n) for n in names]   # (errors before any work)
