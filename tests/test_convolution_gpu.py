@@ -128,6 +128,8 @@ def test_perbin_lookup_callable_statistic_csv_round_trip_and_overlaps(ss):
 
 
 def test_perbin_lookup_raster_sized_vs_oracle(ss):
+    # (raster-sized, yet one trip of the kernel's grid-stride loop: 2.55 M pixels against 16 workgroups of 1024 pixels per compute unit.
+    #  The second trip is test_lookup_routes_gpu.py::test_perbin_second_trip_of_the_grid_stride_loop.)
     rng = np.random.default_rng(21)
     n = 30000
     a, b = rng.gamma(2.0, 8.0, n).astype(np.float32), np.abs(rng.normal(0, 1.5, n))

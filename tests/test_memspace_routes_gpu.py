@@ -10,9 +10,10 @@ import ctypes
 import numpy as np
 import pytest
 
+from gpu_helpers import DP, _back, _dev, _dev_empty, _with_nans
+
 pytestmark = pytest.mark.gpu
 
-DP = ctypes.POINTER(ctypes.c_double)
 EINVAL = -1
 
 
@@ -31,34 +32,8 @@ def _code(dtype):
     return _lib.F32 if np.dtype(dtype) == np.float32 else _lib.F64
 
 
-def _dev(a):
-    """A device copy of a NumPy array, complete before the library's own stream reads it."""
-    import torch
-
-    t = torch.from_numpy(np.ascontiguousarray(a)).cuda()
-    torch.cuda.synchronize()
-    return t
-
-
-def _dev_empty(shape, dtype):
-    import torch
-
-    return torch.empty(shape, dtype=torch.float32 if np.dtype(dtype) == np.float32 else torch.float64, device="cuda")
-
-
-def _back(ctx, t):
-    ctx.synchronize()   # the library launches on its own stream
-    return t.cpu().numpy()
-
-
 def _same(a, b):
     return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
-
-
-def _with_nans(rng, a, k):
-    a = a.copy()
-    a.reshape(-1)[rng.choice(a.size, k, replace=False)] = np.nan
-    return a
 
 
 @pytest.mark.parametrize("size", [3, 5])
