@@ -876,6 +876,44 @@ void xdemhip_hypso_destroy(xdemhip_hypso* plan);
 int xdemhip_hypso_area(xdemhip_ctx* ctx, const void* ref, int dtype, int64_t n, int timeframe, int m, const double* xs,
                        const double* ys, int nb, const double* edges, int64_t* counts, int memspace);
 
+/* ---- a stack of DEMs (xdem/demcollection.py, xdem/ddem.py) ----------------------------------------------------------------
+ * T planes (1 .. 1024) of n pixels on one grid, all float32 or all float64, one of them the reference.  Host planes are uploaded
+ * once and kept, device planes are used in place and must outlive the stack.  subtract and fill write T contiguous planes to `out`
+ * in `memspace`: a device array is written in place and read again by the later passes (it must outlive the stack, or the next call
+ * that replaces it); behind a host array the stack owns the device planes and copies them out.  Every pass is a number of launches
+ * that does not depend on T and ends in one fetch.
+ *  subtract     ddem_t = ref - dem_t, one IEEE subtraction in the planes' dtype.  n_differ[t]: pixels of plane t that differ from the
+ *               reference (other bits, and not both NaN); a plane with none EQUALS the reference and its dDEM is set to 0 -- unless
+ *               can_equal[t] is 0 (T host ints, null: all 1; the caller knows of a difference outside the pixels, a nodata value).
+ *               n_nonfinite[t]: non-finite pixels of the dDEM as left.
+ *  set_masks    n_masks distinct byte masks of n pixels (non-zero = inside) and one mask id per plane (-1: every pixel).  Masks in
+ *               `memspace`; device masks must outlive the stack.  Without a call every plane has every pixel.
+ *  stats        per plane over its INLIERS -- inside its mask, dDEM and reference finite: their number, min and max of the
+ *               reference over them (NaN without an inlier).
+ *  segments     the grouping pass of xdemhip_hypso_segments for all planes at once: plane t has nbs[t] bins (0: the plane is left
+ *               out) whose nbs[t] + 1 edges start row t of `edges`, rows of nb_max + 1.  counts / medians: T rows of nb_max, the
+ *               entries beyond a plane's bins 0 / NaN.  Medians are np.median's, exact.  (Test switch "hypso_seg_lds".)
+ *  fill         filled_t[p] = (p inside mask_t, ddem_t[p] not finite, ms[t] >= 2) ? model_t(ref[p]) rounded to the planes' dtype
+ *               : ddem_t[p]; model_t = interp1d(xs[t * m_max ..], ys[t * m_max ..], fill_value="extrapolate") of ms[t] points
+ *               (ms[t] = 0: plane t is copied).  Fused into the pass, per plane over its own mask: n_mask[t] pixels of the mask,
+ *               n_finite[t] finite filled values among them, sums[t] their float64 sum in the fixed order of the library's
+ *               repeatable sums (one partial per workgroup, a grid that depends on the device and n only): the same bits every run.
+ *  series       the same three figures without filling, over `which` planes: 0 the inputs, 1 the dDEMs, 2 the filled dDEMs;
+ *               mask (n bytes in `memspace`; null: every plane's own mask) is the mask of all planes.
+ * A context serialises these calls like all others. */
+typedef struct xdemhip_stack xdemhip_stack;
+int xdemhip_stack_create(xdemhip_ctx* ctx, const void* const* planes, int n_planes, int dtype, int64_t n, int ref_index, int memspace,
+                         xdemhip_stack** out);
+int xdemhip_stack_set_masks(xdemhip_stack* stack, const unsigned char* const* masks, int n_masks, const int32_t* mask_id, int memspace);
+int xdemhip_stack_subtract(xdemhip_stack* stack, const int32_t* can_equal, void* out, int memspace, int64_t* n_differ, int64_t* n_nonfinite);
+int xdemhip_stack_stats(xdemhip_stack* stack, int64_t* inliers, double* ref_min, double* ref_max);
+int xdemhip_stack_segments(xdemhip_stack* stack, int nb_max, const int32_t* nbs, const double* edges, int64_t* counts, double* medians);
+int xdemhip_stack_fill(xdemhip_stack* stack, int m_max, const int32_t* ms, const double* xs, const double* ys, void* out, int memspace,
+                       int64_t* n_mask, int64_t* n_finite, double* sums);
+int xdemhip_stack_series(xdemhip_stack* stack, int which, const unsigned char* mask, int memspace, int64_t* n_mask, int64_t* n_finite,
+                         double* sums);
+void xdemhip_stack_destroy(xdemhip_stack* stack);
+
 #ifdef __cplusplus
 }
 #endif

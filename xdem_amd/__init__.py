@@ -16,6 +16,8 @@ from . import stats  # noqa: F401  (get_stats, percentile, linear_error: the ras
 from . import freq, surfit, window  # noqa: F401  (the reference's engine-boundary modules: xdem.terrain.surfit / .window / .freq)
 from .dem import DEM  # noqa: F401
 from .epc import EPC  # noqa: F401
+from .ddem import dDEM  # noqa: F401
+from .demcollection import DEMCollection  # noqa: F401
 from .terrain import get_terrain_attribute  # noqa: F401
 
 terrain.surfit, terrain.window, terrain.freq = surfit, window, freq   # reachable as upstream spells them: xdem_amd.terrain.surfit._get_surface_attributes

@@ -276,6 +276,17 @@ def lib() -> ctypes.CDLL:
         L.xdemhip_hypso_destroy.restype = None
         L.xdemhip_hypso_area.argtypes = [c_ctx, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, c_dp, c_dp, ctypes.c_int,
                                          c_dp, c_i64p, ctypes.c_int]
+        c_vpp = ctypes.POINTER(ctypes.c_void_p)
+        L.xdemhip_stack_create.argtypes = [c_ctx, c_vpp, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                           ctypes.POINTER(ctypes.c_void_p)]
+        L.xdemhip_stack_set_masks.argtypes = [ctypes.c_void_p, c_vpp, ctypes.c_int, c_i32p, ctypes.c_int]
+        L.xdemhip_stack_subtract.argtypes = [ctypes.c_void_p, c_i32p, ctypes.c_void_p, ctypes.c_int, c_i64p, c_i64p]
+        L.xdemhip_stack_stats.argtypes = [ctypes.c_void_p, c_i64p, c_dp, c_dp]
+        L.xdemhip_stack_segments.argtypes = [ctypes.c_void_p, ctypes.c_int, c_i32p, c_dp, c_i64p, c_dp]
+        L.xdemhip_stack_fill.argtypes = [ctypes.c_void_p, ctypes.c_int, c_i32p, c_dp, c_dp, ctypes.c_void_p, ctypes.c_int, c_i64p, c_i64p, c_dp]
+        L.xdemhip_stack_series.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, c_i64p, c_i64p, c_dp]
+        L.xdemhip_stack_destroy.argtypes = [ctypes.c_void_p]
+        L.xdemhip_stack_destroy.restype = None
         _lib = L
         return L
 

@@ -7,8 +7,8 @@ DataFrames come out bit for bit -- including upstream's storing of bin ``i``'s s
 first bin's result lands in the last row), which everything downstream inherits.
 
 Inputs are host arrays, masked arrays or device tensors; device inputs give device outputs wherever upstream returns an array.
-``idw_interpolation`` and ``local_hypsometric_interpolation`` (GDAL's fillnodata) and the ``dDEM`` / ``DEMCollection`` classes are
-not part of this module.
+``idw_interpolation`` and ``local_hypsometric_interpolation`` (GDAL's fillnodata) are not part of this module (DESIGN.md section 6);
+the ``dDEM`` / ``DEMCollection`` classes built on it are xdem_amd/ddem.py and xdem_amd/demcollection.py.
 """
 from __future__ import annotations
 
