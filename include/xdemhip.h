@@ -914,6 +914,39 @@ int xdemhip_stack_series(xdemhip_stack* stack, int which, const unsigned char* m
                          double* sums);
 void xdemhip_stack_destroy(xdemhip_stack* stack);
 
+/* ---- polygons burnt into a grid (geoutils' Vector.create_mask / Vector.rasterize with all_touched=False) -------------------
+ * A table of P polygons as R rings over V vertices: xy = the V abscissae, then the V ordinates (float64); ring r is the vertices
+ * ring_off[r] .. ring_off[r + 1] (ring_off[0] = 0, ring_off[R] = V, non-decreasing) and belongs to polygon poly_of_ring[r] in
+ * [0, P) -- the rings of a multipolygon and its holes share one ordinal.  The grid is H x W under the north-up transform6
+ * (a, 0, c0, 0, e, f) with a > 0 > e; anything else is XDEMHIP_EINVAL.
+ * THE RULE: a pixel belongs to a polygon iff its centre is inside, every operation below rounded on its own in float64
+ * (the file is built without contraction):
+ *   centre of pixel (r, c):   cy(r) = f + (r + 0.5) * e,   cx(c) = c0 + (c + 0.5) * a
+ *   an edge (x1, y1) -> (x2, y2) with y1 != y2 crosses row r iff min(y1, y2) <= cy(r) < max(y1, y2) (half open: a vertex on a centre
+ *   line counts once, a horizontal edge never), at x = x1 + (cy(r) - y1) * (x2 - x1) / (y2 - y1), evaluated in that order
+ *   (r, c) is inside iff the number of crossings of row r by the edges of ALL rings of the polygon with x <= cx(c) is odd: even-odd,
+ *   so interior rings are holes.
+ * Rings are closed implicitly (the edge from the last vertex back to the first; a repeated first vertex adds a horizontal edge of
+ * length 0); a ring of fewer than three vertices contributes nothing.  Vertices must be finite (the callers check; an edge with a
+ * NaN ordinate crosses no row).  Row ranges of edges and column ranges of spans start from a division and are corrected with the
+ * very comparisons above, so membership is decided by those comparisons alone.
+ *   out_kind 0   `out` = H * W bytes: 1 inside any polygon, 0 elsewhere (burn and out_value are not read)
+ *   out_kind 1   `out` = H * W int32: burn[p] of the LAST polygon p in table order that holds the pixel (burn null: p + 1), out_value
+ *                where none does
+ * n_burnt (may be null): the pixels inside at least one polygon.  All arrays and `out` in `memspace`; n_burnt is a host word.  The
+ * number of kernel launches does not depend on P, R or V (xdemhip_rasterize_launches: those of the last call).  Overlaps resolve
+ * through an integer maximum, the count through the fixed order of the library's repeatable sums: the same bits every run.
+ * (Test switches "vec_seg_reg", "vec_seg_lds".)
+ * xdemhip_rasterize_union: the byte mask of the pixels inside a polygon of table A OR of table B (either table may have V = 0). */
+int xdemhip_rasterize(xdemhip_ctx* ctx, const double* xy, int64_t V, const int64_t* ring_off, int64_t R, const int32_t* poly_of_ring,
+                      const int32_t* burn_or_null, int32_t P, int64_t H, int64_t W, const double* transform6, void* out, int out_kind,
+                      int32_t out_value, int memspace, int64_t* n_burnt);
+int xdemhip_rasterize_union(xdemhip_ctx* ctx, const double* xy_a, int64_t V_a, const int64_t* ring_off_a, int64_t R_a,
+                            const int32_t* poly_of_ring_a, int32_t P_a, const double* xy_b, int64_t V_b, const int64_t* ring_off_b,
+                            int64_t R_b, const int32_t* poly_of_ring_b, int32_t P_b, int64_t H, int64_t W, const double* transform6,
+                            unsigned char* out, int memspace, int64_t* n_burnt);
+int xdemhip_rasterize_launches(xdemhip_ctx* ctx, int64_t* n_launches);
+
 #ifdef __cplusplus
 }
 #endif

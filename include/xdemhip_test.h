@@ -16,13 +16,22 @@
  *   "bw_seg_lds"         0 (default: 4096) the longest (tile, bin) segment of xdemhip_bw_nk_step that one workgroup sorts in LDS; a longer one
  *                        takes the radix selection over its slice of global memory (1 .. 4096: a test sends 20-value segments down it).
  *   "pts_tile_order"     0 (default) the 4-tap gather of a raster-point plan walks the selected points in cloud order, 1 ordered by raster
- *                        tile (32 x 32 pixels) of their unshifted position; read when a selection is made (create / subsample). */
+ *                        tile (32 x 32 pixels) of their unshifted position; read when a selection is made (create / subsample).
+ *   "vec_seg_reg"        0 (default: 8) the longest crossing segment (one polygon, one pixel row) of xdemhip_rasterize that a single lane sorts
+ *                        in registers; a longer one goes to a workgroup (1 .. 8; 1 sends every segment to the workgroup routes).
+ *   "vec_seg_lds"        0 (default: 4096) the longest crossing segment that one workgroup sorts in LDS; a longer one is sorted in place in
+ *                        global memory (1 .. 4096; with "vec_seg_reg" = 1 the value 1 sends every segment down the global route).
+ *   "vec_stage_times"    0 (default) / 1: xdemhip_rasterize records an event where each of its five stages starts and
+ *                        xdemhip_rasterize_stage_ms returns the device time between them (a measurement form: the same planes). */
 #pragma once
 #include "xdemhip.h"
 #ifdef __cplusplus
 extern "C" {
 #endif
 int xdemhip_set_test_switch(xdemhip_ctx* ctx, const char* name, int value);
+/* ms[5]: edges, crossings into segments (with the call's one fetch of two totals), sorts, spans, finish -- of the last
+ * xdemhip_rasterize / xdemhip_rasterize_union call made with "vec_stage_times" = 1 (two tables: summed per stage); zeros otherwise. */
+int xdemhip_rasterize_stage_ms(xdemhip_ctx* ctx, float* ms);
 #ifdef __cplusplus
 }
 #endif

@@ -18,6 +18,7 @@ from .dem import DEM  # noqa: F401
 from .epc import EPC  # noqa: F401
 from .ddem import dDEM  # noqa: F401
 from .demcollection import DEMCollection  # noqa: F401
+from .vector import Vector  # noqa: F401
 from .terrain import get_terrain_attribute  # noqa: F401
 
 terrain.surfit, terrain.window, terrain.freq = surfit, window, freq   # reachable as upstream spells them: xdem_amd.terrain.surfit._get_surface_attributes

@@ -287,6 +287,13 @@ def lib() -> ctypes.CDLL:
         L.xdemhip_stack_series.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, c_i64p, c_i64p, c_dp]
         L.xdemhip_stack_destroy.argtypes = [ctypes.c_void_p]
         L.xdemhip_stack_destroy.restype = None
+        c_table = [c_dp, ctypes.c_int64, c_i64p, ctypes.c_int64, c_i32p]   # xy, V, ring_off, R, poly_of_ring
+        L.xdemhip_rasterize.argtypes = [c_ctx] + c_table + [c_i32p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, c_dp, ctypes.c_void_p,
+                                                            ctypes.c_int, ctypes.c_int32, ctypes.c_int, c_i64p]
+        L.xdemhip_rasterize_union.argtypes = [c_ctx] + (c_table + [ctypes.c_int32]) * 2 + [ctypes.c_int64, ctypes.c_int64, c_dp, ctypes.c_void_p,
+                                                                                          ctypes.c_int, c_i64p]
+        L.xdemhip_rasterize_launches.argtypes = [c_ctx, c_i64p]
+        L.xdemhip_rasterize_stage_ms.argtypes = [c_ctx, ctypes.POINTER(ctypes.c_float)]
         _lib = L
         return L
 
@@ -555,7 +562,7 @@ class Context:
             self._L.xdemhip_device_free(self.handle, ctypes.c_void_p(p))
 
     TEST_SWITCHES = frozenset(("terrain_stream", "terrain_order", "terrain_ring_wait", "terrain_window_lds", "nk_narrow",
-                               "vario_grid", "vario_runs", "vario_sort", "hypso_seg_lds", "pts_tile_order", "bw_seg_lds"))
+                               "vario_grid", "vario_runs", "vario_sort", "hypso_seg_lds", "pts_tile_order", "bw_seg_lds", "vec_seg_reg", "vec_seg_lds", "vec_stage_times"))
 
     def set_option(self, name: str, value: int) -> None:
         """Option of the library (``xdemhip_set_option``: the fourteen names of include/xdemhip.h), e.g. ``("selection", 1)`` -- or,

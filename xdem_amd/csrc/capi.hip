@@ -322,6 +322,9 @@ const XdOpt kTestSwitches[] = {
     {"pts_tile_order", 0, 1, &xdemhip_ctx::pts_tile_order, "pts_tile_order: 0 or 1"},
     {"bw_seg_lds", 0, 4096, &xdemhip_ctx::bw_seg_lds, "bw_seg_lds: 0 (default: 4096) or 1 to 4096 values"},
     {"hypso_seg_lds", 0, 16384, &xdemhip_ctx::hypso_seg_lds, "hypso_seg_lds: 0 (default: 8192) or 1 to 16384 values"},
+    {"vec_seg_reg", 0, 8, &xdemhip_ctx::vec_seg_reg, "vec_seg_reg: 0 (default: 8) or 1 to 8 crossings"},
+    {"vec_stage_times", 0, 1, &xdemhip_ctx::vec_stage_times, "vec_stage_times: 0 or 1"},
+    {"vec_seg_lds", 0, 4096, &xdemhip_ctx::vec_seg_lds, "vec_seg_lds: 0 (default: 4096) or 1 to 4096 crossings"},
 };
 int xd_set_from(xdemhip_ctx* ctx, const XdOpt* tab, size_t n, const char* name, int value, bool* found) {
     *found = false;

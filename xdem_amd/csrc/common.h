@@ -52,6 +52,11 @@ struct xdemhip_ctx {
     int pts_tile_order = 0;  // test switch "pts_tile_order": 1 the gather of a raster-point plan walks its points by raster tile, 0 in cloud order (ptsplan.hip)
     int hypso_seg_lds = 0;   // test switch "hypso_seg_lds": longest segment of xdemhip_hypso_segments sorted in LDS (values; 0 = 8192), longer ones take the radix selection
     int bw_seg_lds = 0;      // test switch "bw_seg_lds": longest (tile, bin) segment of xdemhip_bw_nk_step sorted in LDS (values; 0 = 4096), longer ones take the radix selection
+    int vec_seg_reg = 0;     // test switch "vec_seg_reg": longest crossing segment of xdemhip_rasterize sorted in one lane's registers (0 = 8), longer ones go to a workgroup
+    int vec_seg_lds = 0;     // test switch "vec_seg_lds": longest crossing segment of xdemhip_rasterize one workgroup sorts in LDS (0 = 4096), longer ones are sorted in place in global memory
+    int vec_stage_times = 0; // test switch "vec_stage_times": 1 xdemhip_rasterize records an event at every stage's start (measurement: xdemhip_rasterize_stage_ms)
+    float vec_stage_ms[5] = {0, 0, 0, 0, 0};   // device time of the five stages of the last xdemhip_rasterize call made under that switch
+    int64_t vec_launches = 0;   // kernels launched by the last xdemhip_rasterize / xdemhip_rasterize_union call (xdemhip_rasterize_launches)
     int selection_mode = 0;  // 0 auto (bracketed for large inputs), 1 plain digit passes only, 2 degenerate brackets (tests the
                              // fallback), 3 bracketed whatever the per-bin sample size (2 and 3: test switches)
     // Deferred device-to-host results (xd_d2h / xd_sync below): small result blocks land in one pinned staging buffer with

@@ -16,6 +16,7 @@ import numpy as np
 
 from . import volume
 from .dem import DEM
+from .vector import Vector
 
 _GDAL_METHODS = ("idw", "local_hypsometric")
 
@@ -48,9 +49,14 @@ def raster_of(data, transform, crs=None, nodata=None) -> DEM:
     return dem
 
 
-def mask_as_array(mask) -> Any:
-    """A mask given as an array, a tensor or a DEM of a mask, as a boolean array / tensor.  For a DEM upstream's rule (ddem.py:70-72):
-    the true value is the raster's maximum, unless that is 0 or False."""
+def mask_as_array(mask, like=None) -> Any:
+    """A mask given as an array, a tensor, a DEM of a mask or a Vector, as a boolean array / tensor.  For a DEM upstream's rule
+    (ddem.py:70-72): the true value is the raster's maximum, unless that is 0 or False.  A Vector is burnt into the grid of the
+    raster `like` on the GPU (``Vector.create_mask``), in the memspace of that raster's data."""
+    if isinstance(mask, Vector):
+        if like is None:
+            raise ValueError("a Vector mask needs the raster it is burnt into")
+        return mask.create_mask(like, device=_is_tensor(like.data))
     if isinstance(mask, DEM):
         data = mask.data
         if _is_tensor(data):
@@ -121,7 +127,7 @@ class dDEM(DEM):
         """Fill the voids with `method` and return ``filled_data``.
 
         "regional_hypsometric": the dDEM's median per 50 m elevation bin of `reference_elevation` (an array, a tensor or a DEM on this
-        grid) over `mask` (a boolean array or a DEM of a mask), evaluated at the voids inside the mask.  "idw" and "local_hypsometric"
+        grid) over `mask` (a boolean array, a DEM of a mask or a Vector), evaluated at the voids inside the mask.  "idw" and "local_hypsometric"
         are GDAL's fillnodata upstream and raise NotImplementedError here."""
         if reference_elevation is not None:
             ref_data = reference_elevation.data if isinstance(reference_elevation, (DEM, np.ma.MaskedArray)) else reference_elevation
@@ -135,7 +141,7 @@ class dDEM(DEM):
             raise NotImplementedError(f"Interpolation method '{method}' not supported")
         assert reference_elevation is not None
         assert mask is not None
-        mask_array = mask_as_array(mask).reshape(tuple(self.data.shape))
+        mask_array = mask_as_array(mask, self).reshape(tuple(self.data.shape))
         ref = reference_elevation.data if isinstance(reference_elevation, DEM) else reference_elevation
         filled = volume.hypsometric_interpolation(self.data, ref, mask=mask_array)
         self.filled_data = filled.data if isinstance(filled, np.ma.MaskedArray) else filled

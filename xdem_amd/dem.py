@@ -19,6 +19,7 @@ from ._coregbase import _Step
 from . import spatialstats as _ss
 from . import stats as _stats
 from . import terrain
+from .vector import Vector
 
 
 class DEM:
@@ -204,6 +205,8 @@ class DEM:
         dh = other_elev.data - self.data
         if precision_of_other == "same":
             dh = dh / np.sqrt(2)
+        if isinstance(stable_terrain, Vector):
+            stable_terrain = stable_terrain.create_mask(self)
         stable = None if stable_terrain is None else np.asarray(getattr(stable_terrain, "data", stable_terrain), dtype=bool)
         if approach_dict[approach]["heterosc"]:
             list_var_rast = [getattr(terrain, v)(self).data if isinstance(v, str) else np.asarray(getattr(v, "data", v)) for v in list_vars]

@@ -8,8 +8,10 @@ csrc/demstack.hip) and every step is a constant number of launches whatever T is
 fused into the fill.  The tables of tens of rows per plane stay in pandas / SciPy, through the functions of ``xdem_amd.volume``, so a
 filled plane has the bits ``volume.hypsometric_interpolation`` gives for it.
 
-Outlines are boolean arrays on the DEMs' grid (or a dict of them by timestamp) where upstream takes vectors and rasterises them; DEMs
-on different grids are refused (reprojection is geoutils' job).  A stack of mixed dtypes is float64 throughout.
+Outlines are ``xdem_amd.Vector`` tables, as upstream takes them, or boolean arrays on the DEMs' grid (or a dict of either by
+timestamp).  A Vector is burnt into the grid on the GPU when a mask is first asked for and the mask is kept per (vector, filter, grid);
+the union of a start and an end outline is one call (``xdemhip_rasterize_union``).  DEMs on different grids are refused (reprojection
+is geoutils' job).  A stack of mixed dtypes is float64 throughout.
 
 One quirk of upstream is reproduced on purpose: the constructor sorts ``dems`` by time but leaves ``timestamps`` in the caller's order
 (demcollection.py:70-78), so ``reference_timestamp`` and the intervals of the dDEMs index the UNSORTED stamps with SORTED positions.
@@ -27,6 +29,7 @@ import scipy.interpolate
 from . import _lib, volume
 from .ddem import dDEM
 from .dem import DEM
+from .vector import Vector, union_mask
 
 _is_tensor = volume._is_tensor
 _I64P = ctypes.POINTER(ctypes.c_int64)
@@ -213,7 +216,7 @@ def _address(x) -> tuple:
 
 
 def _is_outline(x) -> bool:
-    return _is_tensor(x) or isinstance(x, np.ndarray)
+    return _is_tensor(x) or isinstance(x, (np.ndarray, Vector))
 
 
 def plane_model(counts: np.ndarray, medians: np.ndarray, zbins: np.ndarray, dtype: np.dtype):
@@ -231,7 +234,7 @@ class DEMCollection:
 
     def __init__(self, dems, timestamps=None, outlines=None, reference_dem=0):
         """`dems`: ``xdem_amd.DEM`` objects on one grid; `timestamps`: one per DEM (default: every DEM's ``datetime`` attribute);
-        `outlines`: a boolean array on the grid, or a dict of them by timestamp; `reference_dem`: an index into `dems` or one of them."""
+        `outlines`: a Vector or a boolean array on the grid, or a dict of them by timestamp; `reference_dem`: an index into `dems` or one of them."""
         if timestamps is None:
             timestamp_attributes = [getattr(dem, "datetime", None) for dem in dems]
             if any(stamp is None for stamp in timestamp_attributes):
@@ -265,6 +268,7 @@ class DEMCollection:
         self._plan: StackPlan | None = None
         self._views: dict = {}     # DDEMS / FILLED: the (T, n) planes the dDEMs' arrays are views of
         self._fused = None         # (mask keys, figures) of the last batched fill
+        self._burnt: dict = {}     # masks made from Vector outlines, by (vectors, filter, grid, memspace)
 
     @property
     def reference_dem(self) -> DEM:
@@ -309,18 +313,39 @@ class DEMCollection:
         """The outlines whose union is the dDEM's mask, by upstream's four rules; () for the full mask."""
         if not any(ddem is ddem_in_list for ddem_in_list in self.ddems):
             raise ValueError("Given dDEM must be a part of the DEMCollection object.")
-        if outlines_filter is not None:
-            raise NotImplementedError("outlines_filter is a pandas query on a vector's table; the outlines of this class are boolean arrays.")
         outlines = self.outlines
+        all_vectors = bool(outlines) and all(isinstance(value, Vector) for value in outlines.values())
+        if outlines_filter is not None and not all_vectors:
+            raise NotImplementedError("outlines_filter is a pandas query on a vector's table; the outlines of this class are boolean arrays.")
         if ddem.start_time in outlines and ddem.end_time in outlines:
             if outlines[ddem.start_time] is outlines[ddem.end_time]:   # (the union of an outline with itself)
-                return (outlines[ddem.start_time],)
-            return (outlines[ddem.start_time], outlines[ddem.end_time])
-        if ddem.start_time in outlines:
-            return (outlines[ddem.start_time],)
-        if len(outlines) == 1:
-            return (list(outlines.values())[0],)
-        return ()
+                parts = (outlines[ddem.start_time],)
+            else:
+                parts = (outlines[ddem.start_time], outlines[ddem.end_time])
+        elif ddem.start_time in outlines:
+            parts = (outlines[ddem.start_time],)
+        elif len(outlines) == 1:
+            parts = (list(outlines.values())[0],)
+        else:
+            return ()
+        if any(isinstance(part, Vector) for part in parts):
+            return self._burn_parts(parts, outlines_filter, ddem)
+        return parts
+
+    def _burn_parts(self, parts: tuple, outlines_filter, ddem: dDEM) -> tuple:
+        """`parts` with their Vectors burnt into the dDEM's grid, in the memspace of its data: two Vectors in one union call.  The masks
+        are kept, so a part is the same array every time it is asked for (the plans tell masks apart by address)."""
+        grid = (tuple(ddem.data.shape), tuple(self.reference_dem.transform))
+        device = _is_tensor(ddem.data)
+        key = (tuple(id(part) for part in parts), outlines_filter, grid, device)
+        if key not in self._burnt:
+            chosen = tuple(part.query(outlines_filter) if outlines_filter is not None else part for part in parts)
+            if len(chosen) == 2 and all(isinstance(part, Vector) for part in chosen):
+                burnt = (union_mask(chosen[0], chosen[1], grid, device=device),)
+            else:
+                burnt = tuple(part.create_mask(grid, device=device) if isinstance(part, Vector) else part for part in chosen)
+            self._burnt[key] = (burnt, parts)   # (the parts are kept alive: their ids are the key)
+        return self._burnt[key][0]
 
     @staticmethod
     def _mask_of(parts: tuple, shape: tuple):
@@ -338,9 +363,9 @@ class DEMCollection:
         only: that one; a single outline in all: that one; else every pixel."""
         return self._mask_of(self._mask_parts(ddem, outlines_filter), tuple(ddem.data.shape))
 
-    def _set_plan_masks(self, plan: StackPlan, ddems) -> tuple:
+    def _set_plan_masks(self, plan: StackPlan, ddems, outlines_filter=None) -> tuple:
         """The distinct masks of `ddems` handed to `plan`; returns their keys (one per dDEM)."""
-        keys = tuple(tuple(_address(p) for p in self._mask_parts(d)) for d in ddems)
+        keys = tuple(tuple(_address(p) for p in self._mask_parts(d, outlines_filter)) for d in ddems)
         if getattr(plan, "_mask_keys", None) != keys:
             distinct: dict = {}
             ids = []
@@ -349,7 +374,7 @@ class DEMCollection:
                     ids.append(-1)
                     continue
                 if key not in distinct:
-                    distinct[key] = (len(distinct), self._mask_of(self._mask_parts(d), (plan.n,)))
+                    distinct[key] = (len(distinct), self._mask_of(self._mask_parts(d, outlines_filter), (plan.n,)))
                 ids.append(distinct[key][0])
             plan.set_masks([m for _, m in distinct.values()], ids)
             plan._mask_keys = keys
@@ -431,14 +456,14 @@ class DEMCollection:
                 plan = self._plan
                 if mask is not None:
                     return plan.series(which, mask)
-                keys = self._set_plan_masks(plan, self.ddems)
+                keys = self._set_plan_masks(plan, self.ddems, outlines_filter)
                 if which == FILLED and self._fused is not None and self._fused[0] == keys and self._fused[2] == self._version(self._views[FILLED]):
                     return self._fused[1]   # (summed in the fill pass, and nothing has written to the filled planes since)
                 return plan.series(which)
         # arrays the stack does not hold (dDEMs filled one by one, or set by the caller): a stack of their own
         with StackPlan(sources, 0) as plan:
             if mask is None:
-                self._set_plan_masks(plan, self.ddems)
+                self._set_plan_masks(plan, self.ddems, outlines_filter)
             return plan.series(INPUTS, mask)
 
     def get_dh_series(self, outlines_filter: str | None = None, mask=None, nans_ok: bool = False) -> pd.DataFrame:

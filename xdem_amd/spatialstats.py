@@ -1582,6 +1582,21 @@ def _estimate_model_heteroscedasticity(dvalues, list_var, list_var_names, spread
     return df, final_fun
 
 
+def _burn_vector_masks(masks, raster) -> list:
+    """`masks` with every ``xdem_amd.Vector`` among them burnt into the grid of `raster` (``Vector.create_mask`` on the GPU); the rest
+    as it came, for the callers' own checks."""
+    from .vector import Vector
+
+    out = []
+    for m in masks:
+        if isinstance(m, Vector):
+            if not (hasattr(raster, "transform") and hasattr(raster, "data")):
+                raise ValueError("a Vector mask needs the grid it is burnt into: pass the values as a Raster-like object (.data, .transform)")
+            m = m.create_mask((tuple(np.shape(raster.data))[-2:], raster.transform))
+        out.append(m)
+    return out
+
+
 def infer_heteroscedasticity_from_stable(dvalues, list_var, stable_mask=None, unstable_mask=None, list_var_names=None,
                                          spread_statistic=nmad, list_var_bins=None, min_count: int | None = 100,
                                          fac_spread_outliers: float | None = 7, ctx: _lib.Context | None = None):
@@ -1599,6 +1614,7 @@ def infer_heteroscedasticity_from_stable(dvalues, list_var, stable_mask=None, un
     if list_var_names is None:
         list_var_names = ["var" + str(i + 1) for i in range(len(list_var))]
     arrs = [arr_of(dvalues)] + [arr_of(v) for v in list_var]
+    stable_mask, unstable_mask = _burn_vector_masks((stable_mask, unstable_mask), dvalues)
     for m in (stable_mask, unstable_mask):
         if m is not None and not isinstance(m, np.ndarray):
             raise ValueError("xdem_amd takes stable / unstable masks as boolean arrays (vector rasterisation is outside the hot path).")
@@ -1773,6 +1789,7 @@ def infer_spatial_correlation_from_stable(dvalues, list_models, stable_mask=None
         arr = np.ma.filled(data, np.nan)
         if gsd is None:
             gsd = dvalues.res[0]
+    stable_mask, unstable_mask = _burn_vector_masks((stable_mask, unstable_mask), dvalues)
     for m in (stable_mask, unstable_mask):
         if m is not None and not isinstance(m, np.ndarray):
             raise ValueError("xdem_amd takes stable / unstable masks as boolean arrays (vector rasterisation is outside the hot path).")
@@ -1898,11 +1915,33 @@ def number_effective_samples(area, params_variogram_model, rasterize_resolution=
     """Number of effective (uncorrelated) samples in an area for a sum of variogram models; mirror of
     ``xdem.spatialstats.number_effective_samples`` (xdem/spatialstats.py:2311-2404).
 
-    A numeric ``area`` takes the continuous disk approximation (host SciPy integration, as upstream).  Where upstream takes a
-    vector and rasterises it with geoutils (vector I/O: out of scope here), pass the rasterised area itself: a 2-D boolean
-    ``area`` mask on a grid of ``rasterize_resolution`` -- the coordinates of its pixels are built exactly as upstream builds
-    them from its mask and the double sum of covariances runs on the GPU (``neff_hugonnet_approx``; ``kwargs`` go to it)."""
+    A numeric ``area`` takes the continuous disk approximation (host SciPy integration, as upstream).  An ``xdem_amd.Vector`` area is
+    burnt on the GPU into a grid of ``rasterize_resolution`` -- a number (the grid of ``Vector.create_mask(res=)``, coordinates
+    relative) or a Raster-like object (its grid, the coordinates of its pixel centres) -- as upstream's two constructions do.  The
+    rasterised area itself is taken too: a 2-D boolean ``area`` mask on a grid of ``rasterize_resolution``.  The double sum of
+    covariances runs on the GPU (``neff_hugonnet_approx``; ``kwargs`` go to it)."""
+    from .vector import Vector
+
     _check_validity_params_variogram(params_variogram_model)
+    if isinstance(area, Vector):
+        if rasterize_resolution is None:
+            rasterize_resolution = np.min(params_variogram_model["range"].values) / 5.0
+            warnings.warn(
+                "Resolution for vector rasterization is not defined and thus set at 20% of the shortest "
+                "correlation range, which might result in large memory usage."
+            )
+        if isinstance(rasterize_resolution, (float, int, np.floating, np.integer)):
+            area = area.create_mask(res=rasterize_resolution)   # (the bool-mask branch below builds upstream's relative coordinates)
+        elif hasattr(rasterize_resolution, "transform") and hasattr(rasterize_resolution, "shape"):
+            shape, t6 = tuple(rasterize_resolution.shape)[-2:], tuple(rasterize_resolution.transform)
+            mask = area.create_mask((shape, t6))
+            xc = t6[2] + (np.arange(shape[1]) + 0.5) * t6[0]
+            yc = t6[5] + (np.arange(shape[0]) + 0.5) * t6[4]
+            coords_on_mask = np.array(np.meshgrid(xc, yc))[:, mask].T
+            return neff_hugonnet_approx(coords=coords_on_mask, errors=np.ones(len(coords_on_mask)),
+                                        params_variogram_model=params_variogram_model, **kwargs)
+        else:
+            raise ValueError("The rasterize resolution must be a float, integer or Raster subclass.")
     if isinstance(area, (float, int)) and not isinstance(area, bool):
         return neff_circular_approx_numerical(area=area, params_variogram_model=params_variogram_model)
     if isinstance(area, np.ndarray) and area.dtype == bool and area.ndim == 2:
@@ -1929,15 +1968,24 @@ def spatial_error_propagation(areas, errors, params_variogram_model, **kwargs: A
     """Standard error (1-sigma) of the mean elevation error in each area: mean error / sqrt(number of effective samples); mirror
     of ``xdem.spatialstats.spatial_error_propagation`` (xdem/spatialstats.py:2407-2458) for the array-level inputs of
     ``number_effective_samples``: ``errors`` is the error map (array, masked array or Raster-like with ``.data`` / ``.res``),
-    an area is a float (disk of that surface, mean over the whole map) or a boolean mask on the map's grid."""
+    an area is a float (disk of that surface, mean over the whole map), a boolean mask on the map's grid or an ``xdem_amd.Vector``
+    (burnt into the grid of Raster-like ``errors``)."""
     gsd = errors.res[0] if hasattr(errors, "res") and hasattr(errors, "data") else None
     arr = errors.data if gsd is not None else errors
     if isinstance(arr, np.ma.MaskedArray):
         arr = np.where(np.ma.getmaskarray(arr), np.nan, arr.data.astype(np.float64, copy=False))
     arr = np.asarray(arr)
+    from .vector import Vector
+
     standard_errors = []
     for area in areas:
-        if isinstance(area, np.ndarray):
+        if isinstance(area, Vector):   # (upstream: the errors' own grid for the area's coordinates, the mean error inside the outline)
+            if gsd is None:
+                raise ValueError("a Vector area needs the errors' grid: pass a Raster-like `errors` (.data, .transform)")
+            kw = {k: v for k, v in kwargs.items() if k != "rasterize_resolution"}
+            neff = number_effective_samples(area, params_variogram_model, rasterize_resolution=errors, **kw)
+            average_spread = np.nanmean(arr[area.create_mask((tuple(arr.shape)[-2:], errors.transform))])
+        elif isinstance(area, np.ndarray):
             if gsd is None and "rasterize_resolution" not in kwargs:
                 raise ValueError("a mask area needs the grid spacing: pass a Raster-like `errors` or rasterize_resolution=")
             kw = dict(kwargs)
@@ -2152,10 +2200,11 @@ def patches_method(values, areas: list[float], gsd: float = None, stable_mask=No
                    random_state=None):
     """Monte-Carlo patches method: empirical standard error of the mean over patches of given areas; drop-in for
     ``xdem.spatialstats.patches_method`` (2928-3048) for arrays (or Raster-like objects with ``.data`` / ``.res``) and boolean
-    array masks (vector masks need the I/O stack, which is out of scope).  ``vectorized=True`` runs the mean filter on the GPU
+    array masks (an ``xdem_amd.Vector`` mask is burnt into the grid of Raster-like `values`).  ``vectorized=True`` runs the mean filter on the GPU
     for every pixel at once; ``False`` samples quadrants on the host."""
     import pandas as pd
 
+    stable_mask, unstable_mask = _burn_vector_masks((stable_mask, unstable_mask), values)
     if hasattr(values, "res") and hasattr(values, "data"):
         gsd = values.res[0] if gsd is None else gsd
         values = values.data
