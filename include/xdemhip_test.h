@@ -32,6 +32,9 @@ int xdemhip_set_test_switch(xdemhip_ctx* ctx, const char* name, int value);
 /* ms[5]: edges, crossings into segments (with the call's one fetch of two totals), sorts, spans, finish -- of the last
  * xdemhip_rasterize / xdemhip_rasterize_union call made with "vec_stage_times" = 1 (two tables: summed per stage); zeros otherwise. */
 int xdemhip_rasterize_stage_ms(xdemhip_ctx* ctx, float* ms);
+/* Device bytes that the plans of this context hold between calls: what their creates and steps asked for and have not yet freed
+ * (0 once every plan is destroyed; the memory tests read it). */
+int xdemhip_plan_bytes(xdemhip_ctx* ctx, int64_t* bytes);
 #ifdef __cplusplus
 }
 #endif

@@ -294,6 +294,7 @@ def lib() -> ctypes.CDLL:
                                                                                           ctypes.c_int, c_i64p]
         L.xdemhip_rasterize_launches.argtypes = [c_ctx, c_i64p]
         L.xdemhip_rasterize_stage_ms.argtypes = [c_ctx, ctypes.POINTER(ctypes.c_float)]
+        L.xdemhip_plan_bytes.argtypes = [c_ctx, ctypes.POINTER(ctypes.c_int64)]
         _lib = L
         return L
 

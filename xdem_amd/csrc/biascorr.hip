@@ -498,11 +498,8 @@ int ensure_mask(xdemhip_dh_plan* P) {
     if (P->valid) return XDEMHIP_OK;
     xdemhip_ctx* ctx = P->ctx;
     const int64_t n = P->H * P->W;
-    if (hipMalloc(reinterpret_cast<void**>(&P->valid), (size_t)n) != hipSuccess) {
-        (void)hipGetLastError();
-        P->valid = nullptr;
-        return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed (valid mask)");
-    }
+    P->valid = P->mem.take<uint8_t>((size_t)n, "valid mask");
+    { const int rc = P->mem.status(); if (rc) return rc; }
     const int rc = launch_valid(P, true);
     if (rc) return rc;
     hipLaunchKernelGGL(rank_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, P->tile_off, P->n_tiles, P->tile_off + P->n_tiles);
@@ -514,11 +511,8 @@ int ensure_valid_idx(xdemhip_dh_plan* P) {
     if (P->drawn || P->idx) return XDEMHIP_OK;
     xdemhip_ctx* ctx = P->ctx;
     { const int rc = ensure_mask(P); if (rc) return rc; }
-    if (hipMalloc(reinterpret_cast<void**>(&P->idx), (size_t)(P->n_valid > 0 ? P->n_valid : 1) * 8) != hipSuccess) {
-        (void)hipGetLastError();
-        P->idx = nullptr;
-        return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed (valid pixel list)");
-    }
+    P->idx = P->mem.take<int64_t>((size_t)P->n_valid, "valid pixel list");
+    { const int rc = P->mem.status(); if (rc) return rc; }
     hipLaunchKernelGGL((rank_select_kernel<RankOut::List>), dim3((unsigned)P->n_tiles), dim3(256), 0, ctx->stream, P->valid, P->H * P->W,
                        (const unsigned long long*)nullptr, (const uint8_t*)nullptr, P->tile_off, P->idx, (uint8_t*)nullptr);
     if (launched(ctx, "dh_sel_kernel")) return XDEMHIP_EHIP;
@@ -545,7 +539,7 @@ int median_typed(xdemhip_dh_plan* P, double* median, int64_t* count) {
     std::vector<SelResult<K>> r;
     XdLocalSelection local(ctx);   // (one process's pixels)
     SelWorkspaceLocal lws(ctx);
-    if (n >= SEL_BRACKET_MIN_N) (void)sel_ws_create(ctx, n, sizeof(T), 1, lws.ws);  // (on failure: plain selection)
+    if (n >= SEL_BRACKET_MIN_N) (void)sel_ws_create(lws.mem, n, sizeof(T), 1, lws.ws);  // (on failure: plain selection)
     const int rc = run_select<T>(ctx, d, nullptr, n, 1, scratch, r, &lws.ws);
     if (rc == XDEMHIP_OK) {
         *count = (int64_t)r[0].st.count;
@@ -557,28 +551,15 @@ int median_typed(xdemhip_dh_plan* P, double* median, int64_t* count) {
 // ---- shifted-dh evaluations: buffers the plan keeps, and the sequence of one evaluation ---------------------------------------------
 int ensure_stage(xdemhip_dh_plan* P, int64_t n) {
     if (P->stage && P->stage_n == n) return XDEMHIP_OK;
-    xdemhip_ctx* ctx = P->ctx;
-    if (P->stage) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(P->stage); P->stage = nullptr; P->stage_n = 0; }
-    const size_t es = P->dtype == XDEMHIP_F32 ? 4 : 8;
-    if (hipMalloc(&P->stage, (size_t)(n > 0 ? n : 1) * es) != hipSuccess) {
-        (void)hipGetLastError();
-        P->stage = nullptr;
-        return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed (dh staging buffer)");
-    }
-    P->stage_n = n;
-    return XDEMHIP_OK;
+    P->stage_n = P->mem.regrow(P->stage, (size_t)n * (P->dtype == XDEMHIP_F32 ? 4 : 8), "dh staging buffer") ? n : 0;
+    return P->mem.status();
 }
 int ensure_selection(xdemhip_dh_plan* P, int64_t n) {
-    xdemhip_ctx* ctx = P->ctx;
-    if (!P->sel_scratch && hipMalloc(reinterpret_cast<void**>(&P->sel_scratch), scratch_size(1) + sizeof(DhEvalOut)) != hipSuccess) {
-        (void)hipGetLastError();
-        P->sel_scratch = nullptr;
-        return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed (dh selection scratch)");
-    }
+    if (!P->sel_scratch) P->sel_scratch = P->mem.take<unsigned char>(scratch_size(1) + sizeof(DhEvalOut), "dh selection scratch");
+    { const int rc = P->mem.status(); if (rc) return rc; }
     if (P->sel_ws_n != n) {
-        (void)hipStreamSynchronize(ctx->stream);
-        sel_ws_free(P->sel_ws);
-        if (n >= SEL_BRACKET_MIN_N) (void)sel_ws_create(ctx, n, P->dtype == XDEMHIP_F32 ? 4 : 8, 1, P->sel_ws);  // (on failure: plain selection)
+        sel_ws_free(P->mem, P->sel_ws);
+        if (n >= SEL_BRACKET_MIN_N) (void)sel_ws_create(P->mem, n, P->dtype == XDEMHIP_F32 ? 4 : 8, 1, P->sel_ws);  // (on failure: plain selection)
         P->sel_ws_n = n;
     }
     return XDEMHIP_OK;
@@ -656,17 +637,11 @@ static __global__ __launch_bounds__(256) void fixed_sums_reduce_kernel(const dou
     }
     if (threadIdx.x == 0) out[t] = s[0];
 }
-int FixedSums::reserve(xdemhip_ctx* ctx, int nt, const char* who) {
-    const int64_t need = ((int64_t)ctx->num_cu * 8 + 1) * nt;
+int FixedSums::reserve(XdOwned& mem, int nt, const char* who) {
+    const int64_t need = ((int64_t)mem.ctx->num_cu * 8 + 1) * nt;
     if (cap >= need) return XDEMHIP_OK;
-    if (part) { (void)hipStreamSynchronize(ctx->stream); release(); }
-    if (hipMalloc(reinterpret_cast<void**>(&part), (size_t)need * 8) != hipSuccess) {
-        (void)hipGetLastError();
-        part = nullptr;
-        return xd_fail(ctx, XDEMHIP_ENOMEM, std::string("hipMalloc failed (") + who + ")");
-    }
-    cap = need;
-    return XDEMHIP_OK;
+    cap = mem.regrow(part, (size_t)need * 8, who) ? need : 0;
+    return mem.status();
 }
 int fixed_sums_reduce(xdemhip_ctx* ctx, double* part, int nblocks, int nt, const char* what) {
     hipLaunchKernelGGL(fixed_sums_reduce_kernel, dim3((unsigned)nt), dim3(256), 0, ctx->stream, part, nblocks, nt, part + (int64_t)nblocks * nt);
@@ -686,27 +661,7 @@ using namespace xd;
 
 extern "C" {
 
-void xdemhip_dh_destroy(xdemhip_dh_plan* P) {
-    if (!P) return;
-    (void)hipSetDevice(P->ctx->device);
-    if (P->own_inputs) {
-        if (P->ref) (void)hipFree(P->ref);
-        if (P->tba) (void)hipFree(P->tba);
-        if (P->inlier) (void)hipFree(P->inlier);
-    }
-    if (P->valid) (void)hipFree(P->valid);
-    if (P->tile_off) (void)hipFree(P->tile_off);
-    if (P->idx) (void)hipFree(P->idx);
-    if (P->stage) (void)hipFree(P->stage);
-    if (P->sel_scratch) (void)hipFree(P->sel_scratch);
-    if (P->gradx) (void)hipFree(P->gradx);
-    if (P->grady) (void)hipFree(P->grady);
-    P->sums.release();
-    for (int a = 0; a < 3; ++a)
-        if (P->icp_n[a]) (void)hipFree(P->icp_n[a]);
-    sel_ws_free(P->sel_ws);
-    delete P;
-}
+void xdemhip_dh_destroy(xdemhip_dh_plan* P) { delete P; }   // (its owner frees the device buffers)
 
 int xdemhip_dh_create(xdemhip_ctx* ctx, const void* ref, const void* tba, const uint8_t* inlier, int dtype, int64_t H, int64_t W, int memspace,
                       xdemhip_dh_plan** out_plan, int64_t* n_valid) {
@@ -720,30 +675,15 @@ int xdemhip_dh_create(xdemhip_ctx* ctx, const void* ref, const void* tba, const 
     const size_t es = dtype == XDEMHIP_F32 ? 4 : 8;
     const int64_t n = H * W;
     xdemhip_dh_plan* P = new xdemhip_dh_plan();
-    P->ctx = ctx; P->dtype = dtype; P->H = H; P->W = W;
+    P->ctx = P->mem.ctx = ctx; P->dtype = dtype; P->H = H; P->W = W;
     P->n_tiles = (n + RANK_TILE - 1) / RANK_TILE;
-    auto fail = [&](int code) { xdemhip_dh_destroy(P); return code; };
+    auto fail = [&](int code) { delete P; return code; };
     if (P->n_tiles > 0x7FFFFFFF) return fail(xd_fail(ctx, XDEMHIP_EINVAL, "xdemhip_dh_create: raster too large"));
-    if (memspace == XDEMHIP_HOST) {
-        P->own_inputs = true;
-        bool own = false;
-        int rc = xd_upload_keep(ctx, ref, (size_t)n * es, memspace, &P->ref, &own);
-        if (rc == XDEMHIP_OK) rc = xd_upload_keep(ctx, tba, (size_t)n * es, memspace, &P->tba, &own);
-        if (rc == XDEMHIP_OK && inlier) {
-            void* d = nullptr;
-            rc = xd_upload_keep(ctx, inlier, (size_t)n, memspace, &d, &own);
-            P->inlier = static_cast<uint8_t*>(d);
-        }
-        if (rc) return fail(rc);
-    } else {
-        P->ref = const_cast<void*>(ref);
-        P->tba = const_cast<void*>(tba);
-        P->inlier = const_cast<uint8_t*>(inlier);
-    }
-    if (hipMalloc(reinterpret_cast<void**>(&P->tile_off), (size_t)(P->n_tiles + 1) * 8) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed (xdemhip_dh_create)"));
-    }
+    P->ref = P->mem.keep(ref, (size_t)n * es, memspace, "xdemhip_dh_create");
+    P->tba = P->mem.keep(tba, (size_t)n * es, memspace, "xdemhip_dh_create");
+    P->inlier = P->mem.keep(inlier, (size_t)n, memspace, "xdemhip_dh_create");
+    P->tile_off = P->mem.take<unsigned long long>((size_t)P->n_tiles + 1, "xdemhip_dh_create");
+    if (P->mem.rc) return fail(P->mem.rc);
     // (counts only: the mask itself is built by the routes that read it)
     { const int rc_ = launch_valid(P, false); if (rc_) return fail(rc_); }
     hipLaunchKernelGGL(rank_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, P->tile_off, P->n_tiles, P->tile_off + P->n_tiles);
@@ -765,23 +705,20 @@ int xdemhip_dh_subsample(xdemhip_dh_plan* P, const int64_t* ranks, int64_t k, in
     if (memspace != XDEMHIP_HOST && memspace != XDEMHIP_DEVICE) return xd_fail(ctx, XDEMHIP_EINVAL, "bad memspace");
     XD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     { const int rc_ = ensure_mask(P); if (rc_) return rc_; }
-    RankSelect rs;
+    RankSelect rs(ctx, "xdemhip_dh_subsample");
     unsigned long long total = 0, bad = 0;
-    { const int rc_ = rs.run(ctx, "xdemhip_dh_subsample", ranks, k, memspace, P->n_valid, P->valid, P->H * P->W, P->tile_off, &total, &bad); if (rc_) return rc_; }
+    { const int rc_ = rs.run(ranks, k, memspace, P->n_valid, P->valid, P->H * P->W, P->tile_off, &total, &bad); if (rc_) return rc_; }
     if (bad != 0) return xd_fail(ctx, XDEMHIP_EINVAL, "xdemhip_dh_subsample: a rank is outside [0, n_valid)");
     if ((int64_t)total > k) return xd_fail(ctx, XDEMHIP_EINVAL, "xdemhip_dh_subsample: more pixels than ranks");
     // (repeated ranks select one pixel: the list is as long as the distinct ranks)
-    int64_t* idx = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&idx), (size_t)k * 8) != hipSuccess) {
-        (void)hipGetLastError();
-        return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed (xdemhip_dh_subsample)");
-    }
+    int64_t* idx = P->mem.take<int64_t>((size_t)k, "xdemhip_dh_subsample");
+    { const int rc_ = P->mem.status(); if (rc_) return rc_; }
     hipLaunchKernelGGL((rank_select_kernel<RankOut::List>), dim3((unsigned)P->n_tiles), dim3(256), 0, ctx->stream, P->valid, P->H * P->W, P->tile_off,
                        rs.mark, rs.off, idx, (uint8_t*)nullptr);
     int rc = launched(ctx, "xdemhip_dh_subsample: kernel");
     if (rc == XDEMHIP_OK) rc = xd_sync(ctx);
-    if (rc) { (void)hipFree(idx); return rc; }
-    if (P->idx) (void)hipFree(P->idx);
+    if (rc) { P->mem.drop(idx); return rc; }
+    P->mem.drop(P->idx);
     P->idx = idx;
     P->n_idx = (int64_t)total;
     P->drawn = true;
@@ -806,7 +743,7 @@ int xdemhip_dh_poly_moments(xdemhip_dh_plan* P, int order, int64_t row_offset, i
     double ax, bx, ay, by;
     norm_axis(W_global, &ax, &bx);
     norm_axis(H_global, &ay, &by);
-    { const int rc_ = P->sums.reserve(ctx, NT, "xdemhip_dh_poly_moments"); if (rc_) return rc_; }
+    { const int rc_ = P->sums.reserve(P->mem, NT, "xdemhip_dh_poly_moments"); if (rc_) return rc_; }
     int nblocks = 0;
     (void)hipEventRecord(ctx->ev_start, ctx->stream);
     int rc = P->dtype == XDEMHIP_F32 ? launch_moments<float>(P, order, row_offset, ax, bx, ay, by, P->sums.part, &nblocks)

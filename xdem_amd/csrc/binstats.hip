@@ -184,12 +184,11 @@ struct xdemhip_binstats {
     xdemhip_ctx* ctx = nullptr;
     int dtype = XDEMHIP_F32;
     int64_t n = 0;
-    void* values = nullptr;
-    bool own_values = false;
+    XdOwned mem;               // every device buffer of the plan but the caller's own device arrays
+    void* values = nullptr;    // the caller's device array, or an owned copy of its host array (the variables likewise)
     uint8_t* valid = nullptr;
     std::vector<void*> var;
     std::vector<int> var_dtype;
-    std::vector<bool> var_own;
     uint16_t* bins = nullptr;
     void* absdev = nullptr;
     bool finalized = false;
@@ -207,7 +206,7 @@ int run_typed(xdemhip_binstats* P, int nb, int want_nmad, double nfact, int64_t*
     std::vector<SelResult<K>> hs;
     SelWorkspaceLocal local(ctx);
     SelWorkspace& ws = local.ws;
-    if (P->n >= SEL_BRACKET_MIN_N && nb <= MAX_BINS_PER_SWEEP && sel_ws_create(ctx, P->n, sizeof(T), nb, ws) != XDEMHIP_OK) return XDEMHIP_ENOMEM;
+    if (P->n >= SEL_BRACKET_MIN_N && nb <= MAX_BINS_PER_SWEEP && sel_ws_create(local.mem, P->n, sizeof(T), nb, ws) != XDEMHIP_OK) return XDEMHIP_ENOMEM;
     int rc = run_select<T>(ctx, static_cast<const T*>(P->values), P->bins, P->n, nb, base, hs, &ws);
     std::vector<T> med(nb);
     if (rc == XDEMHIP_OK)
@@ -243,18 +242,7 @@ int run_typed(xdemhip_binstats* P, int nb, int want_nmad, double nfact, int64_t*
 
 extern "C" {
 
-void xdemhip_binstats_destroy(xdemhip_binstats* P) {
-    if (!P) return;
-    (void)hipSetDevice(P->ctx->device);
-    (void)hipStreamSynchronize(P->ctx->stream);
-    if (P->own_values && P->values) (void)hipFree(P->values);
-    for (size_t i = 0; i < P->var.size(); ++i)
-        if (P->var_own[i] && P->var[i]) (void)hipFree(P->var[i]);
-    if (P->valid) (void)hipFree(P->valid);
-    if (P->bins) (void)hipFree(P->bins);
-    if (P->absdev) (void)hipFree(P->absdev);
-    delete P;
-}
+void xdemhip_binstats_destroy(xdemhip_binstats* P) { delete P; }   // (its owner frees the device buffers)
 
 int xdemhip_binstats_create(xdemhip_ctx* ctx, const void* values, int dtype, int64_t n, int memspace, xdemhip_binstats** out) {
     if (!ctx) return XDEMHIP_EINVAL;
@@ -263,14 +251,13 @@ int xdemhip_binstats_create(xdemhip_ctx* ctx, const void* values, int dtype, int
     if (memspace != XDEMHIP_HOST && memspace != XDEMHIP_DEVICE) return xd_fail(ctx, XDEMHIP_EINVAL, "bad memspace");
     XD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     xdemhip_binstats* P = new xdemhip_binstats;
-    P->ctx = ctx; P->dtype = dtype; P->n = n;
+    P->ctx = P->mem.ctx = ctx; P->dtype = dtype; P->n = n;
     const size_t es = dtype == XDEMHIP_F32 ? 4 : 8;
-    int rc = xd_upload_keep(ctx, values, (size_t)n * es, memspace, &P->values, &P->own_values);
-    if (rc == XDEMHIP_OK && (hipMalloc(reinterpret_cast<void**>(&P->valid), (size_t)n) != hipSuccess ||
-                             hipMalloc(reinterpret_cast<void**>(&P->bins), (size_t)n * 2) != hipSuccess ||
-                             hipMalloc(&P->absdev, (size_t)n * es) != hipSuccess))
-        rc = xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed");
-    if (rc != XDEMHIP_OK) { xdemhip_binstats_destroy(P); return rc; }
+    P->values = P->mem.keep(values, (size_t)n * es, memspace, "xdemhip_binstats_create");
+    P->valid = P->mem.take<uint8_t>((size_t)n, "xdemhip_binstats_create");
+    P->bins = P->mem.take<uint16_t>((size_t)n, "xdemhip_binstats_create");
+    P->absdev = P->mem.take((size_t)n * es, "xdemhip_binstats_create");
+    if (P->mem.rc) { const int rc = P->mem.rc; delete P; return rc; }
     const dim3 g(grid_for(ctx, n, 256, 16));
     if (dtype == XDEMHIP_F32) hipLaunchKernelGGL((finite_and_kernel<float>), g, dim3(256), 0, ctx->stream, static_cast<const float*>(P->values), n, P->valid, 1);
     else hipLaunchKernelGGL((finite_and_kernel<double>), g, dim3(256), 0, ctx->stream, static_cast<const double*>(P->values), n, P->valid, 1);
@@ -285,12 +272,9 @@ int xdemhip_binstats_add_var(xdemhip_binstats* P, const void* var, int dtype, in
         return xd_fail(ctx, XDEMHIP_EINVAL, "bad argument");
     if ((int)P->var.size() >= BS_MAXDIM) return xd_fail(ctx, XDEMHIP_EUNSUPPORTED, "at most 8 explanatory variables");
     XD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    void* d = nullptr;
-    bool own = false;
-    const size_t es = dtype == XDEMHIP_F32 ? 4 : 8;
-    int rc = xd_upload_keep(ctx, var, (size_t)P->n * es, memspace, &d, &own);
-    if (rc != XDEMHIP_OK) return rc;
-    P->var.push_back(d); P->var_dtype.push_back(dtype); P->var_own.push_back(own);
+    void* d = P->mem.keep(var, (size_t)P->n * (dtype == XDEMHIP_F32 ? 4 : 8), memspace, "xdemhip_binstats_add_var");
+    { const int rc = P->mem.status(); if (rc) return rc; }
+    P->var.push_back(d); P->var_dtype.push_back(dtype);
     const dim3 g(grid_for(ctx, P->n, 256, 16));
     if (dtype == XDEMHIP_F32) hipLaunchKernelGGL((finite_and_kernel<float>), g, dim3(256), 0, ctx->stream, static_cast<const float*>(d), P->n, P->valid, 0);
     else hipLaunchKernelGGL((finite_and_kernel<double>), g, dim3(256), 0, ctx->stream, static_cast<const double*>(d), P->n, P->valid, 0);
@@ -414,7 +398,7 @@ static int nmad_typed(xdemhip_ctx* ctx, const void* values, int64_t n, double nf
     std::vector<SelResult<K>> r;
     XdLocalSelection local(ctx);
     SelWorkspaceLocal lws(ctx);
-    if (n >= SEL_BRACKET_MIN_N) (void)sel_ws_create(ctx, n, sizeof(T), 1, lws.ws);  // (on failure: plain selection)
+    if (n >= SEL_BRACKET_MIN_N) (void)sel_ws_create(lws.mem, n, sizeof(T), 1, lws.ws);  // (on failure: plain selection)
     int rc = run_select<T>(ctx, src, nullptr, n, 1, base, r, &lws.ws);
     if (rc == XDEMHIP_OK) {
         *count = (int64_t)r[0].st.count;

@@ -344,7 +344,7 @@ struct xdemhip_bw_plan {
     int n_tiles = 0;
     int nan_rule = 0;
     int64_t total = 0, max_px = 0;   // samples of all tiles; of the largest tile
-    std::vector<void*> owned;
+    XdOwned mem;
     BwTile* tiles = nullptr;
     void *ref = nullptr, *tba = nullptr, *slope_tan = nullptr, *aspect = nullptr, *dh = nullptr, *y = nullptr, *seg = nullptr;
     uint8_t *valid = nullptr, *bin = nullptr;
@@ -453,13 +453,7 @@ int bw_step_typed(xdemhip_bw_plan* P, const uint8_t* active, const double* shift
 extern "C" {
 
 void xdemhip_bw_destroy(xdemhip_bw_plan* P) {
-    if (!P) return;
-    if (P->ctx) {
-        (void)hipSetDevice(P->ctx->device);
-        (void)hipStreamSynchronize(P->ctx->stream);
-    }
-    for (void* p : P->owned) (void)hipFree(p);
-    delete P;
+    delete P;   // (its owner frees the device buffers)
 }
 
 int xdemhip_bw_create(xdemhip_ctx* ctx, const void* ref, const void* tba, const unsigned char* inlier, int dtype, int64_t H, int64_t W, int n_tiles,
@@ -487,16 +481,9 @@ int xdemhip_bw_create(xdemhip_ctx* ctx, const void* ref, const void* tba, const 
     }
     XD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     xdemhip_bw_plan* P = new xdemhip_bw_plan;
-    P->ctx = ctx; P->dtype = dtype; P->n_tiles = n_tiles; P->nan_rule = ctx->nk_nan_rule; P->total = total; P->max_px = max_px;
+    P->ctx = P->mem.ctx = ctx; P->dtype = dtype; P->n_tiles = n_tiles; P->nan_rule = ctx->nk_nan_rule; P->total = total; P->max_px = max_px;
     const size_t es = dtype == XDEMHIP_F32 ? 4 : 8, N = (size_t)n_tiles;
-    bool ok = true;
-    auto take = [&](size_t bytes) -> void* {
-        void* p = nullptr;
-        if (!ok) return nullptr;
-        if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess) { (void)hipGetLastError(); ok = false; return nullptr; }
-        P->owned.push_back(p);
-        return p;
-    };
+    auto take = [&](size_t bytes) { return P->mem.take(bytes, "xdemhip_bw_create"); };
     P->tiles = static_cast<BwTile*>(take(N * sizeof(BwTile)));
     P->ref = take(total * es); P->tba = take(total * es); P->slope_tan = take(total * es); P->aspect = take(total * es);
     P->dh = take(total * es); P->y = take(total * es); P->seg = take(total * es);
@@ -510,7 +497,7 @@ int xdemhip_bw_create(xdemhip_ctx* ctx, const void* ref, const void* tba, const 
     P->vshift_t = take(N * es);
     P->edges_t = take(N * (BW_MAX_BINS + 1) * es);
     P->res = static_cast<unsigned char*>(take(bw_res_bytes(n_tiles, BW_MAX_BINS)));
-    int rc = ok ? XDEMHIP_OK : xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed (xdemhip_bw_create)");
+    int rc = P->mem.rc;
     if (rc == XDEMHIP_OK && hipMemcpyAsync(P->tiles, tiles.data(), N * sizeof(BwTile), hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
         rc = xd_fail(ctx, XDEMHIP_EHIP, "H2D copy failed (xdemhip_bw_create)");
     if (rc == XDEMHIP_OK)   // (`tiles` outlives the copy: both typed functions synchronise the stream before they return)

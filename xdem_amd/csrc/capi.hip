@@ -363,6 +363,12 @@ int xdemhip_set_option(xdemhip_ctx* ctx, const char* name, int value) {
     return xd_fail(ctx, XDEMHIP_EINVAL, std::string("unknown option: ") + name);
 }
 
+int xdemhip_plan_bytes(xdemhip_ctx* ctx, int64_t* bytes) {
+    if (!ctx || !bytes) return XDEMHIP_EINVAL;
+    *bytes = ctx->plan_bytes;
+    return XDEMHIP_OK;
+}
+
 int xdemhip_set_test_switch(xdemhip_ctx* ctx, const char* name, int value) {
     if (!ctx || !name) return XDEMHIP_EINVAL;
     if (strcmp(name, "terrain_stream") == 0 && !(value == 0 || value == 1 || value == 2 || value == 3 || value == 128 || value == 256 || value == 512))

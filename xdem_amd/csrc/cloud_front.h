@@ -55,16 +55,17 @@ struct CloudFront {
     double *nx = nullptr, *ny = nullptr, *nz = nullptr;
 };
 
-// Gather the n = P->n_idx selected pixels (dh_ensure_valid_idx was called, n > 0) and standardise them.  `alloc(&ptr, bytes, what)`
-// gives device memory that the caller's object owns (and frees, also after a failure here).  `who`: "ICP" or "CPD", for messages.
-template <typename Alloc>
-int cloud_front_build(xdemhip_dh_plan* P, const double* transform6, bool with_normals, bool standardize, const char* who, Alloc alloc, CloudFront& C,
-                      double* centroid3, double* std_fac) {
+// Gather the n = P->n_idx selected pixels (dh_ensure_valid_idx was called, n > 0) and standardise them.  `mem` is the owner of the
+// caller's object: the clouds live as long as it does (it frees them, also after a failure here).  `who`: "ICP" or "CPD", for messages.
+inline int cloud_front_build(xdemhip_dh_plan* P, const double* transform6, bool with_normals, bool standardize, const char* who, XdOwned& mem, CloudFront& C,
+                             double* centroid3, double* std_fac) {
     xdemhip_ctx* ctx = P->ctx;
     const int64_t n = P->n_idx;
     const std::string w(who);
-    double* base = nullptr;
-    { const int rc_ = alloc(&base, (size_t)n * 8 * (with_normals ? 7 : 4), (w + " clouds").c_str()); if (rc_) return rc_; }
+    double* base = mem.take<double>((size_t)n * (with_normals ? 7 : 4), (w + " clouds").c_str());
+    unsigned char* scratch = mem.take<unsigned char>(scratch_size(1), (w + " selection").c_str());
+    double* tmp = mem.take<double>((size_t)n, (w + " selection").c_str());
+    if (mem.rc) return mem.rc;
     C.x = base; C.y = base + n; C.zr = base + 2 * n; C.zt = base + 3 * n;
     if (with_normals) { C.nx = base + 4 * n; C.ny = base + 5 * n; C.nz = base + 6 * n; }
     const dim3 grid(grid_for(ctx, n, 256, 16));
@@ -81,17 +82,13 @@ int cloud_front_build(xdemhip_dh_plan* P, const double* transform6, bool with_no
     { const int rc_ = launched(ctx, "icp_gather_kernel"); if (rc_) return rc_; }
     // standardisation: three medians for the centroid, three more (of the centred values, as np.median sees them) and three of the
     // absolute deviations for the NMADs
-    unsigned char* scratch = nullptr;
-    double* tmp = nullptr;
-    { const int rc_ = alloc(&scratch, scratch_size(1), (w + " selection").c_str()); if (rc_) return rc_; }
-    { const int rc_ = alloc(&tmp, (size_t)n * 8, (w + " selection").c_str()); if (rc_) return rc_; }
     double* axis[3] = {C.x, C.y, C.zr};
     double nmads[3] = {0.0, 0.0, 0.0};
     int rc = XDEMHIP_OK;
     {   // (the workspace goes when the medians are done)
         SelWorkspaceLocal lws(ctx);
         SelWorkspace& ws = lws.ws;
-        if (n >= SEL_BRACKET_MIN_N) (void)sel_ws_create(ctx, n, 8, 1, ws);
+        if (n >= SEL_BRACKET_MIN_N) (void)sel_ws_create(lws.mem, n, 8, 1, ws);
         for (int a = 0; a < 3 && rc == XDEMHIP_OK; ++a) {
             double med = 0.0, med2 = 0.0, mad = 0.0;
             rc = icp_median(ctx, axis[a], n, scratch, &ws, &med);

@@ -66,6 +66,7 @@ struct xdemhip_ctx {
     size_t pin_cap = 0, pin_used = 0;
     struct Pending { void* dst; size_t off, bytes; };
     std::vector<Pending> pending;
+    int64_t plan_bytes = 0;  // device bytes the plans of this context hold (XdOwned below; read by xdemhip_plan_bytes only)
     std::string err;
 };
 
@@ -169,20 +170,89 @@ struct XdBuffers {
     XdBuffers& operator=(const XdBuffers&) = delete;
 };
 
-// For plan constructors, which keep what they upload: the caller's device array itself (*own false), or a device copy of its host
-// array with the upload queued on the stream (*own true).  On failure nothing is left allocated and HIP's last error is cleared.
-inline int xd_upload_keep(xdemhip_ctx* ctx, const void* src, size_t bytes, int memspace, void** dptr, bool* own) {
-    *own = false;
-    if (memspace == XDEMHIP_DEVICE) { *dptr = const_cast<void*>(src); return XDEMHIP_OK; }
-    if (hipMalloc(dptr, bytes) != hipSuccess) { (void)hipGetLastError(); *dptr = nullptr; return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed"); }
-    if (hipMemcpyAsync(*dptr, src, bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
-        (void)hipFree(*dptr);
-        *dptr = nullptr;
-        return xd_fail(ctx, XDEMHIP_EHIP, "H2D copy failed");
+// The device buffers a plan keeps from create to destroy; the plan struct holds one by value.  take() gives a buffer for the life of
+// the owner (a zero-byte request still a valid pointer).  keep() gives the device side of an array the plan goes on reading: the
+// caller's array itself where it is on the device (XDEMHIP_DEVICE; not owned), else an owned copy with the upload queued on the
+// context's stream.  A failure returns nullptr, clears HIP's last error and sets `rc` (XDEMHIP_ENOMEM "hipMalloc failed (`who`)",
+// XDEMHIP_EHIP "H2D copy failed (`who`)"); after it every further request returns nullptr, so a call site asks for all it needs
+// and looks once: at `rc` in a constructor, whose plan dies with the failure, at status() in a step, which hands the owner back
+// ready for the next call.  Buffers a plan can do without are taken between optional() and all_or_none(): if one of them fails,
+// all of them are freed, the pointers named are nulled and `rc` stays clear.  drop() frees one buffer now and regrow() replaces
+// it, both after waiting for the stream; a pointer the owner does not own is left alone.  release(), and the end of the owner,
+// free everything after that wait.  ctx->plan_bytes counts the bytes asked for that are still held.
+struct XdOwned {
+    struct Buf { void* p; size_t bytes; };
+    xdemhip_ctx* ctx = nullptr;
+    int rc = XDEMHIP_OK;
+    std::vector<Buf> owned;
+    size_t opt_from = 0;
+    bool in_opt = false, opt_failed = false;
+    void* take(size_t bytes, const char* who) {
+        void* p = nullptr;
+        if (rc != XDEMHIP_OK || (in_opt && opt_failed)) return nullptr;
+        if (hipMalloc(&p, bytes ? bytes : 8) != hipSuccess) {
+            (void)hipGetLastError();
+            if (in_opt) opt_failed = true;
+            else rc = xd_fail(ctx, XDEMHIP_ENOMEM, std::string("hipMalloc failed (") + who + ")");
+            return nullptr;
+        }
+        owned.push_back({p, bytes});
+        ctx->plan_bytes += (int64_t)bytes;
+        return p;
     }
-    *own = true;
-    return XDEMHIP_OK;
-}
+    template <typename T> T* take(size_t count, const char* who) { return static_cast<T*>(take(count * sizeof(T), who)); }
+    template <typename T> T* keep(const T* src, size_t bytes, int memspace, const char* who) {
+        if (memspace == XDEMHIP_DEVICE || !src) return const_cast<T*>(src);
+        T* d = static_cast<T*>(take(bytes, who));
+        if (d && hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
+            (void)hipGetLastError();
+            drop(d);
+            rc = xd_fail(ctx, XDEMHIP_EHIP, std::string("H2D copy failed (") + who + ")");
+            return nullptr;
+        }
+        return d;
+    }
+    void optional() { opt_from = owned.size(); in_opt = true; opt_failed = rc != XDEMHIP_OK; }
+    template <typename... T> bool all_or_none(T*&... ptrs) {
+        in_opt = false;
+        if (!opt_failed) return true;
+        if (owned.size() > opt_from) (void)hipStreamSynchronize(ctx->stream);
+        while (owned.size() > opt_from) free_last();
+        ((ptrs = nullptr), ...);
+        return false;
+    }
+    void drop(const void* p) {
+        for (size_t i = 0; p && i < owned.size(); ++i)
+            if (owned[i].p == p) {
+                (void)hipStreamSynchronize(ctx->stream);
+                std::swap(owned[i], owned.back());
+                free_last();
+                return;
+            }
+    }
+    template <typename T> bool regrow(T*& p, size_t bytes, const char* who) {
+        drop(p);
+        p = static_cast<T*>(take(bytes, who));
+        return p != nullptr;
+    }
+    int status() { const int r = rc; rc = XDEMHIP_OK; return r; }
+    void release() {
+        if (owned.empty()) return;
+        (void)hipSetDevice(ctx->device);
+        (void)hipStreamSynchronize(ctx->stream);
+        while (!owned.empty()) free_last();
+    }
+    void free_last() {
+        (void)hipFree(owned.back().p);
+        ctx->plan_bytes -= (int64_t)owned.back().bytes;
+        owned.pop_back();
+    }
+    XdOwned() = default;
+    explicit XdOwned(xdemhip_ctx* c) : ctx(c) {}
+    ~XdOwned() { release(); }
+    XdOwned(const XdOwned&) = delete;
+    XdOwned& operator=(const XdOwned&) = delete;
+};
 
 // "This selection is local": the reduction hook is off for the length of the scope (one process's values, a single-device helper).
 struct XdLocalSelection {

@@ -34,7 +34,7 @@
 struct xdemhip_cpd {
     xdemhip_ctx* ctx = nullptr;
     int64_t n = 0, m = 0;            // reference points, to-be-aligned points
-    std::vector<void*> owned;        // every device allocation of the object
+    XdOwned mem;                     // every device allocation of the object
     double *rx = nullptr, *ry = nullptr, *rz = nullptr;   // reference cloud
     double *qx = nullptr, *qy = nullptr, *qz = nullptr;   // to-be-aligned cloud (qx, qy = rx, ry for a cloud made from a plan)
     double4* x4 = nullptr;           // n x (x, y, z, inv): what pass B stages
@@ -247,26 +247,6 @@ __global__ void cpd_results_kernel(const double* __restrict__ tot1, const double
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------------
-template <typename P> int cpd_alloc(xdemhip_cpd* C, P** p, size_t bytes, const char* what) {
-    void* d = nullptr;
-    if (hipMalloc(&d, bytes > 0 ? bytes : 8) != hipSuccess) {
-        (void)hipGetLastError();
-        return xd_fail(C->ctx, XDEMHIP_ENOMEM, std::string("hipMalloc failed (") + what + ")");
-    }
-    C->owned.push_back(d);
-    *p = static_cast<P*>(d);
-    return XDEMHIP_OK;
-}
-
-void cpd_free(xdemhip_cpd* C) {
-    if (!C) return;
-    (void)hipSetDevice(C->ctx->device);
-    (void)hipStreamSynchronize(C->ctx->stream);
-    for (void* p : C->owned) (void)hipFree(p);
-    C->sums.release();
-    delete C;
-}
-
 // Points per slice of a cloud of `other` points walked by the blocks of a cloud of `own` points: enough slices that blocks x slices
 // reaches num_cu * 8 workgroups and no more, at least CPD_MIN_SLICE points each.  A function of N, M and the device only.
 void cpd_slicing(const xdemhip_ctx* ctx, int64_t own, int64_t other, int64_t* len, int64_t* slices) {
@@ -286,16 +266,17 @@ int cpd_alloc_work(xdemhip_cpd* C) {
     cpd_slicing(ctx, n, m, &C->len_a, &C->slices_a);
     cpd_slicing(ctx, m, n, &C->len_b, &C->slices_b);
     const int64_t pa = C->slices_a * n, pb = 4 * C->slices_b * m;
-    int rc = cpd_alloc(C, &C->x4, (size_t)n * 32, "CPD clouds");
-    if (rc == XDEMHIP_OK) rc = cpd_alloc(C, &C->t4, (size_t)m * 32, "CPD clouds");
-    if (rc == XDEMHIP_OK) rc = cpd_alloc(C, &C->den, (size_t)n * 8, "CPD E-step");
-    if (rc == XDEMHIP_OK) rc = cpd_alloc(C, &C->pt1, (size_t)n * 8, "CPD E-step");
-    if (rc == XDEMHIP_OK) rc = cpd_alloc(C, &C->p1, (size_t)m * 8, "CPD E-step");
-    if (rc == XDEMHIP_OK) rc = cpd_alloc(C, &C->px, (size_t)m * 24, "CPD E-step");
-    if (rc == XDEMHIP_OK) rc = cpd_alloc(C, &C->part, (size_t)(pa > pb ? pa : pb) * 8, "CPD slice partials");
-    if (rc == XDEMHIP_OK) rc = cpd_alloc(C, &C->dpar, 32 * 8, "CPD E-step");
-    if (rc == XDEMHIP_OK) rc = C->sums.reserve(ctx, CPD_NT1 + CPD_NT2, "CPD partial sums");
-    if (rc) return rc;
+    XdOwned& mem = C->mem;
+    C->x4 = mem.take<double4>((size_t)n, "CPD clouds");
+    C->t4 = mem.take<double4>((size_t)m, "CPD clouds");
+    C->den = mem.take<double>((size_t)n, "CPD E-step");
+    C->pt1 = mem.take<double>((size_t)n, "CPD E-step");
+    C->p1 = mem.take<double>((size_t)m, "CPD E-step");
+    C->px = mem.take<double>((size_t)m * 3, "CPD E-step");
+    C->part = mem.take<double>((size_t)(pa > pb ? pa : pb), "CPD slice partials");
+    C->dpar = mem.take<double>(32, "CPD E-step");
+    if (mem.rc) return mem.rc;
+    { const int rc = C->sums.reserve(mem, CPD_NT1 + CPD_NT2, "CPD partial sums"); if (rc) return rc; }
     hipLaunchKernelGGL(cpd_pack_kernel, dim3(grid_for(ctx, n, 256, 16)), dim3(256), 0, ctx->stream, C->rx, C->ry, C->rz, n, C->x4);
     return launched(ctx, "cpd_pack_kernel");
 }
@@ -318,7 +299,7 @@ using namespace xd;
 
 extern "C" {
 
-void xdemhip_cpd_destroy(xdemhip_cpd* C) { cpd_free(C); }
+void xdemhip_cpd_destroy(xdemhip_cpd* C) { delete C; }
 
 int xdemhip_cpd_create_plan(xdemhip_dh_plan* P, const double* transform6, int standardize, xdemhip_cpd** out, double* centroid3, double* std_fac,
                             int64_t* count) {
@@ -333,11 +314,10 @@ int xdemhip_cpd_create_plan(xdemhip_dh_plan* P, const double* transform6, int st
     if (count) *count = n;
     if (n == 0) return xd_fail(ctx, XDEMHIP_EINVAL, "no valid points");
     xdemhip_cpd* C = new xdemhip_cpd();
-    C->ctx = ctx; C->n = n; C->m = n;
-    auto fail = [&](int code) { cpd_free(C); return code; };
+    C->ctx = C->mem.ctx = ctx; C->n = n; C->m = n;
+    auto fail = [&](int code) { delete C; return code; };
     CloudFront F;
-    int rc = cloud_front_build(P, transform6, false, standardize != 0, "CPD",
-                               [&](auto** p, size_t bytes, const char* what) { return cpd_alloc(C, p, bytes, what); }, F, centroid3, std_fac);
+    int rc = cloud_front_build(P, transform6, false, standardize != 0, "CPD", C->mem, F, centroid3, std_fac);
     if (rc) return fail(rc);
     C->rx = C->qx = F.x; C->ry = C->qy = F.y; C->rz = F.zr; C->qz = F.zt;
     rc = cpd_alloc_work(C);
@@ -354,15 +334,12 @@ int xdemhip_cpd_create_points(xdemhip_ctx* ctx, const double* ref3n, int64_t n, 
     if (n < 1 || m < 1) return xd_fail(ctx, XDEMHIP_EINVAL, "xdemhip_cpd_create_points: both clouds need at least one point");
     XD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     xdemhip_cpd* C = new xdemhip_cpd();
-    C->ctx = ctx; C->n = n; C->m = m;
-    auto fail = [&](int code) { cpd_free(C); return code; };
-    double *r = nullptr, *q = nullptr;
-    int rc = cpd_alloc(C, &r, (size_t)n * 24, "CPD clouds");
-    if (rc == XDEMHIP_OK) rc = cpd_alloc(C, &q, (size_t)m * 24, "CPD clouds");
+    C->ctx = C->mem.ctx = ctx; C->n = n; C->m = m;
+    auto fail = [&](int code) { delete C; return code; };
+    double* r = C->mem.keep(ref3n, (size_t)n * 24, XDEMHIP_HOST, "CPD clouds");
+    double* q = C->mem.keep(tba3m, (size_t)m * 24, XDEMHIP_HOST, "CPD clouds");
+    int rc = C->mem.rc;
     if (rc) return fail(rc);
-    if (hipMemcpyAsync(r, ref3n, (size_t)n * 24, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
-        hipMemcpyAsync(q, tba3m, (size_t)m * 24, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
-        return fail(xd_fail(ctx, XDEMHIP_EHIP, "H2D copy failed"));
     C->rx = r; C->ry = r + n; C->rz = r + 2 * n;
     C->qx = q; C->qy = q + m; C->qz = q + 2 * m;
     rc = cpd_alloc_work(C);

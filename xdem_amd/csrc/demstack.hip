@@ -32,10 +32,11 @@ struct xdemhip_stack {
     xdemhip_ctx* ctx = nullptr;
     int f32 = 1, T = 0, K = 0, ref_index = 0;
     int64_t n = 0;
+    XdOwned mem;                        // every device buffer of the stack but the caller's own device arrays
     void* upload = nullptr;             // [T * n] the planes of host inputs (device inputs are used in place)
     const void* ref = nullptr;          // the reference's input plane
     void *ddem = nullptr, *filled = nullptr;   // [T * n] each: the caller's device array, or the stack's own buffer behind a host array
-    bool own_ddem = false, own_filled = false;
+    void* out_buf[2] = {nullptr, nullptr};     // those own buffers of the two slots (null: none)
     const void** tabs = nullptr;        // [3 * T] device pointers: the input planes | the dDEM planes | the filled planes
     unsigned char* mask_upload = nullptr;      // [K * n] the masks of host inputs
     const unsigned char** mask_tab = nullptr;  // [T] device pointers: the mask of every plane (null: every pixel)
@@ -265,22 +266,17 @@ __global__ __launch_bounds__(256) void stk_fill_kernel(const V* const* __restric
 int stk_place(xdemhip_stack* S, int slot, void* out, int memspace) {
     xdemhip_ctx* ctx = S->ctx;
     void*& buf = slot == 1 ? S->ddem : S->filled;
-    bool& own = slot == 1 ? S->own_ddem : S->own_filled;
+    void*& mine = S->out_buf[slot - 1];
     const size_t plane = (size_t)S->n * (S->f32 ? 4 : 8);
     XD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     if (memspace == XDEMHIP_DEVICE) {
-        if (own && buf) (void)hipFree(buf);
+        S->mem.drop(mine);
+        mine = nullptr;
         buf = out;
-        own = false;
-    } else if (!own || !buf) {
-        buf = nullptr;
-        own = false;
-        if (hipMalloc(&buf, plane * S->T) != hipSuccess) {
-            (void)hipGetLastError();
-            buf = nullptr;
-            return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed (xdemhip_stack)");
-        }
-        own = true;
+    } else {
+        if (!mine) mine = S->mem.take(plane * S->T, "xdemhip_stack");
+        buf = mine;
+        { const int rc = S->mem.status(); if (rc) return rc; }
     }
     std::vector<const void*> tab((size_t)S->T);
     for (int t = 0; t < S->T; ++t) tab[t] = static_cast<const char*>(buf) + plane * t;
@@ -301,7 +297,7 @@ int stk_series(xdemhip_stack* S, const void** src_tab, void* out, int m_max, con
     xdemhip_ctx* ctx = S->ctx;
     const int T = S->T;
     const int64_t n = S->n;
-    int rc = S->sums.reserve(ctx, T, "xdemhip_stack");
+    int rc = S->sums.reserve(S->mem, T, "xdemhip_stack");
     if (rc) return rc;
     unsigned long long* d_cnt = buf.alloc<unsigned long long>((size_t)2 * T);
     if (buf.rc) return buf.rc;
@@ -348,17 +344,13 @@ int xdemhip_stack_create(xdemhip_ctx* ctx, const void* const* planes, int n_plan
     const int T = n_planes;
     const size_t es = dtype == XDEMHIP_F32 ? 4 : 8, plane = (size_t)n * es;
     xdemhip_stack* S = new xdemhip_stack;
-    S->ctx = ctx; S->f32 = dtype == XDEMHIP_F32; S->T = T; S->n = n; S->ref_index = ref_index;
+    S->ctx = S->mem.ctx = ctx; S->f32 = dtype == XDEMHIP_F32; S->T = T; S->n = n; S->ref_index = ref_index;
     std::vector<const void*> tabs((size_t)3 * T, nullptr);
     std::vector<const unsigned char*> no_masks((size_t)T, nullptr);
-    bool ok = hipMalloc(reinterpret_cast<void**>(&S->tabs), (size_t)3 * T * sizeof(void*)) == hipSuccess &&
-              hipMalloc(reinterpret_cast<void**>(&S->mask_tab), (size_t)T * sizeof(void*)) == hipSuccess &&
-              (memspace == XDEMHIP_DEVICE || hipMalloc(&S->upload, plane * T) == hipSuccess);
-    int rc = XDEMHIP_OK;
-    if (!ok) {
-        (void)hipGetLastError();
-        rc = xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed (xdemhip_stack_create)");
-    }
+    S->tabs = S->mem.take<const void*>((size_t)3 * T, "xdemhip_stack_create");
+    S->mask_tab = S->mem.take<const unsigned char*>((size_t)T, "xdemhip_stack_create");
+    if (memspace == XDEMHIP_HOST) S->upload = S->mem.take(plane * T, "xdemhip_stack_create");
+    int rc = S->mem.rc;
     for (int t = 0; t < T && rc == XDEMHIP_OK; ++t) {
         if (memspace == XDEMHIP_DEVICE) tabs[t] = planes[t];
         else {
@@ -376,20 +368,7 @@ int xdemhip_stack_create(xdemhip_ctx* ctx, const void* const* planes, int n_plan
     return XDEMHIP_OK;
 }
 
-void xdemhip_stack_destroy(xdemhip_stack* S) {
-    if (!S) return;
-    (void)hipSetDevice(S->ctx->device);
-    (void)hipStreamSynchronize(S->ctx->stream);
-    if (S->upload) (void)hipFree(S->upload);
-    if (S->own_ddem && S->ddem) (void)hipFree(S->ddem);
-    if (S->own_filled && S->filled) (void)hipFree(S->filled);
-    if (S->tabs) (void)hipFree(S->tabs);
-    if (S->mask_upload) (void)hipFree(S->mask_upload);
-    if (S->mask_tab) (void)hipFree(S->mask_tab);
-    if (S->grp) (void)hipFree(S->grp);
-    S->sums.release();
-    delete S;
-}
+void xdemhip_stack_destroy(xdemhip_stack* S) { delete S; }   // (its owner frees the device buffers)
 
 int xdemhip_stack_set_masks(xdemhip_stack* S, const unsigned char* const* masks, int n_masks, const int32_t* mask_id, int memspace) {
     if (!S) return XDEMHIP_EINVAL;
@@ -403,13 +382,11 @@ int xdemhip_stack_set_masks(xdemhip_stack* S, const unsigned char* const* masks,
         if (!masks[k]) return xd_fail(ctx, XDEMHIP_EINVAL, "null argument");
     XD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     XD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    if (S->mask_upload) { (void)hipFree(S->mask_upload); S->mask_upload = nullptr; }
+    S->mem.drop(S->mask_upload);
+    S->mask_upload = nullptr;
     if (memspace == XDEMHIP_HOST && n_masks > 0) {
-        if (hipMalloc(reinterpret_cast<void**>(&S->mask_upload), (size_t)n_masks * S->n) != hipSuccess) {
-            (void)hipGetLastError();
-            S->mask_upload = nullptr;
-            return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed (xdemhip_stack_set_masks)");
-        }
+        S->mask_upload = S->mem.take<unsigned char>((size_t)n_masks * S->n, "xdemhip_stack_set_masks");
+        { const int rc = S->mem.status(); if (rc) return rc; }
         for (int k = 0; k < n_masks; ++k)
             XD_HIP_CHECK(ctx, hipMemcpyAsync(S->mask_upload + (size_t)k * S->n, masks[k], (size_t)S->n, hipMemcpyHostToDevice, ctx->stream));
     }
@@ -510,11 +487,8 @@ int xdemhip_stack_segments(xdemhip_stack* S, int nb_max, const int32_t* nbs, con
     XD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     const int n_groups = T * nb_max;
     const size_t es = S->f32 ? 4 : 8;
-    if (!S->grp && hipMalloc(reinterpret_cast<void**>(&S->grp), (size_t)T * n * 4) != hipSuccess) {
-        (void)hipGetLastError();
-        S->grp = nullptr;
-        return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed (xdemhip_stack_segments)");
-    }
+    if (!S->grp) S->grp = S->mem.take<int32_t>((size_t)T * n, "xdemhip_stack_segments");
+    { const int rc_ = S->mem.status(); if (rc_) return rc_; }
     unsigned long long total = 0;   // (a copy's destination: declared before the buffers)
     XdBuffers buf(ctx, "xdemhip_stack_segments");
     const int32_t* d_nbs = buf.input(nbs, (size_t)T * 4, XDEMHIP_HOST);

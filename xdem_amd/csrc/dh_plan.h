@@ -11,8 +11,8 @@ struct xdemhip_dh_plan {
     xdemhip_ctx* ctx = nullptr;
     int dtype = XDEMHIP_F32;
     int64_t H = 0, W = 0;
-    bool own_inputs = false;
-    void* ref = nullptr;
+    XdOwned mem;                              // every device buffer of the plan but the caller's own device arrays
+    void* ref = nullptr;                      // the caller's device arrays, or owned copies of its host arrays
     void* tba = nullptr;
     uint8_t* inlier = nullptr;
     uint8_t* valid = nullptr;                 // n bytes: inlier & finite(ref) & finite(tba)

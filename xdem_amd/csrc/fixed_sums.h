@@ -49,12 +49,7 @@ template <int N> __device__ __forceinline__ void block_sums_store(const double* 
 struct FixedSums {
     double* part = nullptr;
     int64_t cap = 0;   // doubles
-    int reserve(xdemhip_ctx* ctx, int nt, const char* who);   // growing synchronises the stream before it frees; XDEMHIP_ENOMEM: "hipMalloc failed (who)"
-    void release() {
-        if (part) (void)hipFree(part);
-        part = nullptr;
-        cap = 0;
-    }
+    int reserve(XdOwned& mem, int nt, const char* who);   // from the owner of whoever holds the sums; XDEMHIP_ENOMEM: "hipMalloc failed (who)"
 };
 // the workgroups of a sums kernel over `units` units of work (tiles, rows, runs of 256 elements)
 inline int fixed_sums_grid(const xdemhip_ctx* ctx, int64_t units) {

@@ -28,7 +28,7 @@
 struct xdemhip_icp {
     xdemhip_ctx* ctx = nullptr;
     int64_t n = 0, m = 0;            // reference points, query points
-    std::vector<void*> owned;        // every device allocation of the object
+    XdOwned mem;                     // every device allocation of the object
     double *rx = nullptr, *ry = nullptr, *rz = nullptr;   // reference cloud
     double *qx = nullptr, *qy = nullptr, *qz = nullptr;   // query cloud (qx, qy = rx, ry for a cloud made from a plan)
     double *nx = nullptr, *ny = nullptr, *nz = nullptr;   // normals at the reference points (null: none)
@@ -306,25 +306,14 @@ __global__ __launch_bounds__(256) void icp_values_kernel(PairSrc src, int64_t k,
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------------
-template <typename P> int icp_alloc(xdemhip_icp* I, P** p, size_t bytes, const char* what) {
-    void* d = nullptr;
-    if (hipMalloc(&d, bytes > 0 ? bytes : 8) != hipSuccess) {
-        (void)hipGetLastError();
-        return xd_fail(I->ctx, XDEMHIP_ENOMEM, std::string("hipMalloc failed (") + what + ")");
-    }
-    I->owned.push_back(d);
-    *p = static_cast<P*>(d);
-    return XDEMHIP_OK;
-}
-
 // The grid over the reference cloud: cells of side h with about ICP_OCCUPANCY points each, from the bounding box and n; an axis of
 // zero extent gets one row of cells, and h is never below what a one-dimensional cloud needs (so the cells number at most ~ n).
 int icp_build_grid(xdemhip_icp* I) {
     xdemhip_ctx* ctx = I->ctx;
     const int64_t n = I->n;
     const int nb = grid_for(ctx, n, 256, 4);
-    double* d_box = nullptr;
-    { const int rc_ = icp_alloc(I, &d_box, (size_t)nb * 32, "ICP bounding box"); if (rc_) return rc_; }
+    double* d_box = I->mem.take<double>((size_t)nb * 4, "ICP bounding box");
+    if (I->mem.rc) return I->mem.rc;
     hipLaunchKernelGGL(icp_bbox_kernel, dim3((unsigned)nb), dim3(256), 0, ctx->stream, I->rx, I->ry, n, d_box);
     { const int rc_ = launched(ctx, "icp_bbox_kernel"); if (rc_) return rc_; }
     std::vector<double> hb((size_t)nb * 4);
@@ -349,14 +338,14 @@ int icp_build_grid(xdemhip_icp* I) {
     while (fx * fy > 4.0 * limit) { if (fx > fy) fx = ceil(fx / 2); else fy = ceil(fy / 2); }   // (cannot happen for h >= h1; a guard)
     I->x0 = x0; I->y0 = y0; I->h = h; I->gx = (int)fx; I->gy = (int)fy;
     const int64_t ncell = (int64_t)I->gx * I->gy;
-    unsigned long long* cursor = nullptr;
-    int rc = icp_alloc(I, &I->cell_start, (size_t)(ncell + 1) * 8, "ICP cells");
-    if (rc == XDEMHIP_OK) rc = icp_alloc(I, &cursor, (size_t)ncell * 8, "ICP cells");
-    if (rc == XDEMHIP_OK) rc = icp_alloc(I, &I->sx, (size_t)n * 8, "ICP sorted cloud");
-    if (rc == XDEMHIP_OK) rc = icp_alloc(I, &I->sy, (size_t)n * 8, "ICP sorted cloud");
-    if (rc == XDEMHIP_OK) rc = icp_alloc(I, &I->sz, (size_t)n * 8, "ICP sorted cloud");
-    if (rc == XDEMHIP_OK) rc = icp_alloc(I, &I->sidx, (size_t)n * 8, "ICP sorted cloud");
-    if (rc) return rc;
+    XdOwned& mem = I->mem;
+    I->cell_start = mem.take<unsigned long long>((size_t)ncell + 1, "ICP cells");
+    unsigned long long* cursor = mem.take<unsigned long long>((size_t)ncell, "ICP cells");
+    I->sx = mem.take<double>((size_t)n, "ICP sorted cloud");
+    I->sy = mem.take<double>((size_t)n, "ICP sorted cloud");
+    I->sz = mem.take<double>((size_t)n, "ICP sorted cloud");
+    I->sidx = mem.take<int64_t>((size_t)n, "ICP sorted cloud");
+    if (mem.rc) return mem.rc;
     XD_HIP_CHECK(ctx, hipMemsetAsync(I->cell_start, 0, (size_t)(ncell + 1) * 8, ctx->stream));
     XD_HIP_CHECK(ctx, hipMemsetAsync(cursor, 0, (size_t)ncell * 8, ctx->stream));
     const Grid g = {I->x0, I->y0, I->h, I->gx, I->gy};
@@ -370,27 +359,19 @@ int icp_build_grid(xdemhip_icp* I) {
 
 // the arrays of the query and of the pairs, sized once the clouds are known
 int icp_alloc_work(xdemhip_icp* I) {
-    const int64_t n = I->n, m = I->m;
-    int rc = icp_alloc(I, &I->tx, (size_t)m * 8, "ICP query");
-    if (rc == XDEMHIP_OK) rc = icp_alloc(I, &I->ty, (size_t)m * 8, "ICP query");
-    if (rc == XDEMHIP_OK) rc = icp_alloc(I, &I->tz, (size_t)m * 8, "ICP query");
-    if (rc == XDEMHIP_OK) rc = icp_alloc(I, &I->ind, (size_t)m * 8, "ICP query");
-    if (rc == XDEMHIP_OK) rc = icp_alloc(I, &I->dist, (size_t)m * 8, "ICP query");
-    if (rc == XDEMHIP_OK) rc = icp_alloc(I, &I->best, (size_t)n * 8, "ICP pairs");
-    if (rc == XDEMHIP_OK) rc = icp_alloc(I, &I->bestq, (size_t)n * 8, "ICP pairs");
-    if (rc == XDEMHIP_OK) rc = icp_alloc(I, &I->has, (size_t)n + 16, "ICP pairs");
-    if (rc == XDEMHIP_OK) rc = icp_alloc(I, &I->tile_off, (size_t)((n + RANK_TILE - 1) / RANK_TILE + 2) * 8, "ICP pairs");
-    if (rc == XDEMHIP_OK) rc = icp_alloc(I, &I->pair_r, (size_t)n * 8, "ICP pairs");
-    return rc;
-}
-
-void icp_free(xdemhip_icp* I) {
-    if (!I) return;
-    (void)hipSetDevice(I->ctx->device);
-    (void)hipStreamSynchronize(I->ctx->stream);
-    for (void* p : I->owned) (void)hipFree(p);
-    I->sums.release();
-    delete I;
+    const size_t n = (size_t)I->n, m = (size_t)I->m;
+    XdOwned& mem = I->mem;
+    I->tx = mem.take<double>(m, "ICP query");
+    I->ty = mem.take<double>(m, "ICP query");
+    I->tz = mem.take<double>(m, "ICP query");
+    I->ind = mem.take<int64_t>(m, "ICP query");
+    I->dist = mem.take<double>(m, "ICP query");
+    I->best = mem.take<unsigned long long>(n, "ICP pairs");
+    I->bestq = mem.take<unsigned long long>(n, "ICP pairs");
+    I->has = mem.take<uint8_t>(n + 16, "ICP pairs");
+    I->tile_off = mem.take<unsigned long long>((n + RANK_TILE - 1) / RANK_TILE + 2, "ICP pairs");
+    I->pair_r = mem.take<int64_t>(n, "ICP pairs");
+    return mem.rc;
 }
 
 PairSrc pair_src(const xdemhip_icp* I) {
@@ -405,12 +386,9 @@ template <typename T>
 int normals_typed(xdemhip_dh_plan* P, double res_x, double res_y) {
     xdemhip_ctx* ctx = P->ctx;
     const int64_t n = P->H * P->W;
-    for (int a = 0; a < 3; ++a)
-        if (hipMalloc(&P->icp_n[a], (size_t)n * sizeof(T)) != hipSuccess) {
-            (void)hipGetLastError();
-            for (int b = 0; b < 3; ++b) { if (P->icp_n[b]) (void)hipFree(P->icp_n[b]); P->icp_n[b] = nullptr; }
-            return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed (ICP normal planes)");
-        }
+    P->mem.optional();   // (three planes or none: a plan without them can be asked again)
+    for (int a = 0; a < 3; ++a) P->icp_n[a] = P->mem.take((size_t)n * sizeof(T), "ICP normal planes");
+    if (!P->mem.all_or_none(P->icp_n[0], P->icp_n[1], P->icp_n[2])) return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed (ICP normal planes)");
     hipLaunchKernelGGL((icp_normals_kernel<T>), dim3(grid_for(ctx, n, 256, 16)), dim3(256), 0, ctx->stream, static_cast<const T*>(P->ref), P->H, P->W, (T)res_x,
                        (T)res_y, static_cast<T*>(P->icp_n[0]), static_cast<T*>(P->icp_n[1]), static_cast<T*>(P->icp_n[2]), P->valid);
     // the tiles' counts of the narrowed mask, scanned: the subsample ranks and the pixel list follow the new mask
@@ -458,7 +436,7 @@ int xdemhip_dh_icp_normals(xdemhip_dh_plan* P, const double* transform6, void* n
     return xd_sync(ctx);
 }
 
-void xdemhip_icp_destroy(xdemhip_icp* I) { icp_free(I); }
+void xdemhip_icp_destroy(xdemhip_icp* I) { delete I; }
 
 int xdemhip_icp_create_plan(xdemhip_dh_plan* P, const double* transform6, int with_normals, int standardize, xdemhip_icp** out, double* centroid3,
                             double* std_fac, int64_t* count) {
@@ -474,11 +452,10 @@ int xdemhip_icp_create_plan(xdemhip_dh_plan* P, const double* transform6, int wi
     if (count) *count = n;
     if (n == 0) return xd_fail(ctx, XDEMHIP_EINVAL, "no valid points");
     xdemhip_icp* I = new xdemhip_icp();
-    I->ctx = ctx; I->n = n; I->m = n;
-    auto fail = [&](int code) { icp_free(I); return code; };
+    I->ctx = I->mem.ctx = ctx; I->n = n; I->m = n;
+    auto fail = [&](int code) { delete I; return code; };
     CloudFront C;   // the gather and the standardisation: cloud_front.h, shared with cpd.hip
-    int rc = cloud_front_build(P, transform6, with_normals != 0, standardize != 0, "ICP",
-                               [&](auto** p, size_t bytes, const char* what) { return icp_alloc(I, p, bytes, what); }, C, centroid3, std_fac);
+    int rc = cloud_front_build(P, transform6, with_normals != 0, standardize != 0, "ICP", I->mem, C, centroid3, std_fac);
     if (rc) return fail(rc);
     I->rx = I->qx = C.x; I->ry = I->qy = C.y; I->rz = C.zr; I->qz = C.zt;
     I->nx = C.nx; I->ny = C.ny; I->nz = C.nz;
@@ -498,17 +475,13 @@ int xdemhip_icp_create_points(xdemhip_ctx* ctx, const double* ref3n, int64_t n, 
     if (n < 1 || m < 1) return xd_fail(ctx, XDEMHIP_EINVAL, "xdemhip_icp_create_points: both clouds need at least one point");
     XD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     xdemhip_icp* I = new xdemhip_icp();
-    I->ctx = ctx; I->n = n; I->m = m;
-    auto fail = [&](int code) { icp_free(I); return code; };
-    double *r = nullptr, *q = nullptr, *nn = nullptr;
-    int rc = icp_alloc(I, &r, (size_t)n * 24, "ICP clouds");
-    if (rc == XDEMHIP_OK) rc = icp_alloc(I, &q, (size_t)m * 24, "ICP clouds");
-    if (rc == XDEMHIP_OK && norms3n_or_null) rc = icp_alloc(I, &nn, (size_t)n * 24, "ICP clouds");
+    I->ctx = I->mem.ctx = ctx; I->n = n; I->m = m;
+    auto fail = [&](int code) { delete I; return code; };
+    double* r = I->mem.keep(ref3n, (size_t)n * 24, XDEMHIP_HOST, "ICP clouds");
+    double* q = I->mem.keep(query3m, (size_t)m * 24, XDEMHIP_HOST, "ICP clouds");
+    double* nn = I->mem.keep(norms3n_or_null, (size_t)n * 24, XDEMHIP_HOST, "ICP clouds");
+    int rc = I->mem.rc;
     if (rc) return fail(rc);
-    if (hipMemcpyAsync(r, ref3n, (size_t)n * 24, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
-        hipMemcpyAsync(q, query3m, (size_t)m * 24, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
-        (nn && hipMemcpyAsync(nn, norms3n_or_null, (size_t)n * 24, hipMemcpyHostToDevice, ctx->stream) != hipSuccess))
-        return fail(xd_fail(ctx, XDEMHIP_EHIP, "H2D copy failed"));
     I->rx = r; I->ry = r + n; I->rz = r + 2 * n;
     I->qx = q; I->qy = q + m; I->qz = q + 2 * m;
     if (nn) { I->nx = nn; I->ny = nn + n; I->nz = nn + 2 * n; }
@@ -644,7 +617,7 @@ int xdemhip_icp_sums(xdemhip_icp* I, const double* step16, int method, double* s
     XD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     const int NT = ICP_NS + 1;
     const int nb = fixed_sums_grid(ctx, (I->k + 255) / 256);
-    { const int rc_ = I->sums.reserve(ctx, NT, "ICP partial sums"); if (rc_) return rc_; }
+    { const int rc_ = I->sums.reserve(I->mem, NT, "ICP partial sums"); if (rc_) return rc_; }
     Mat12 S;
     memcpy(S.m, step16, sizeof S.m);
     (void)hipEventRecord(ctx->ev_start, ctx->stream);

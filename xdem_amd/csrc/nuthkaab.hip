@@ -464,12 +464,10 @@ struct xdemhip_nk_plan {
     int64_t H = 0, W = 0;                 // raster shape (global)
     int64_t roff = 0, nbuf = 0;           // the buffers hold raster rows [roff, roff + nbuf)
     int64_t row0 = 0, row1 = 0;           // this rank's own rows [row0, row1) (whole raster unless sharded)
-    void *ref = nullptr, *tba = nullptr;  // device (owned when own_inputs)
-    uint8_t* inlier = nullptr;            // device copy kept for re-partitioning (owned when own_inputs)
-    uint8_t* sub_inlier = nullptr;        // xdemhip_nk_subsample: the inlier mask in force after it (owned; `inlier` then points here and
-    uint8_t* inlier_user = nullptr;       //  the mask the plan was created with is remembered for its release)
-    bool subsampled = false;
-    bool own_inputs = false;
+    XdOwned mem;                          // every device buffer of the plan but the caller's own device arrays
+    void *ref = nullptr, *tba = nullptr;  // device: the caller's arrays, or owned copies of its host arrays
+    uint8_t* inlier = nullptr;            // ... likewise, kept for re-partitioning
+    uint8_t* sub_inlier = nullptr;        // xdemhip_nk_subsample: the inlier mask in force after it (owned; `inlier` then points here)
     void *slope_tan = nullptr, *aspect = nullptr, *dh = nullptr, *y = nullptr;
     uint8_t* valid = nullptr;
     uint16_t* bins = nullptr;
@@ -706,24 +704,11 @@ int nk_mr_alloc(xdemhip_nk_plan* P, int nb, int world, size_t es) {
     auto mx = [](size_t a, size_t b) { return a > b ? a : b; };
     const size_t wa = mx(mx(4, 3 + 3 * (size_t)nb + 5 * (size_t)world + (size_t)world * (DSEL_BUCKETS / 2)), 2 + 2 * (size_t)nb + (size_t)world * nb * (SEL_RADIX / 2));
     const size_t wb = mx((size_t)world * DSEL_HDR_WORDS + (size_t)DSEL_CAP * es / 8, (size_t)nb * MR_GSEG * es / 8);
-    if (!P->mr_small && hipMalloc(reinterpret_cast<void**>(&P->mr_small), (size_t)(11 + BINSEG_CTR_STRIDE) * P->ws.nb_max * 8) != hipSuccess) {
-        (void)hipGetLastError();
-        P->mr_small = nullptr;
-        return XDEMHIP_ENOMEM;
-    }
-    if (P->mr_a_words < wa) {
-        if (P->mr_a) (void)hipFree(P->mr_a);
-        P->mr_a = nullptr; P->mr_a_words = 0;
-        if (hipMalloc(reinterpret_cast<void**>(&P->mr_a), wa * 8) != hipSuccess) { (void)hipGetLastError(); P->mr_a = nullptr; return XDEMHIP_ENOMEM; }
-        P->mr_a_words = wa;
-    }
-    if (P->mr_b_words < wb) {
-        if (P->mr_b) (void)hipFree(P->mr_b);
-        P->mr_b = nullptr; P->mr_b_words = 0;
-        if (hipMalloc(reinterpret_cast<void**>(&P->mr_b), wb * 8) != hipSuccess) { (void)hipGetLastError(); P->mr_b = nullptr; return XDEMHIP_ENOMEM; }
-        P->mr_b_words = wb;
-    }
-    return XDEMHIP_OK;
+    const char* who = "exchange buffers of the one-pass step";
+    if (!P->mr_small) P->mr_small = P->mem.take<uint64_t>((size_t)(11 + BINSEG_CTR_STRIDE) * P->ws.nb_max, who);
+    if (P->mr_a_words < wa) P->mr_a_words = P->mem.regrow(P->mr_a, wa * 8, who) ? wa : 0;
+    if (P->mr_b_words < wb) P->mr_b_words = P->mem.regrow(P->mr_b, wb * 8, who) ? wb : 0;
+    return P->mem.status();
 }
 
 // ---- host side of the one-pass step (device code: "Round 4: the ONE-PASS step" above) ------------------------------------------
@@ -936,13 +921,8 @@ int nk_step_onepass(xdemhip_nk_plan* P, const NkGeom& g, int64_t q0, int64_t n, 
         if ((rows + grid.y - 1) / grid.y > NKZ_CHUNK_MAX) grid.y = (unsigned)((rows + NKZ_CHUNK_MAX - 1) / NKZ_CHUNK_MAX);
         n_wg = (int)(grid.x * grid.y);
         if ((size_t)n_wg > P->wg_sums_cap) {   // (per-workgroup slots of the pass's five float64 sums: nk_sums_reduce)
-            if (P->wg_sums) (void)hipFree(P->wg_sums);
-            P->wg_sums = nullptr; P->wg_sums_cap = 0;
-            if (hipMalloc(reinterpret_cast<void**>(&P->wg_sums), (size_t)n_wg * 5 * sizeof(double)) != hipSuccess) {
-                (void)hipGetLastError();
-                return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc(per-workgroup sums of the one-pass step) failed");
-            }
-            P->wg_sums_cap = (size_t)n_wg;
+            P->wg_sums_cap = P->mem.regrow(P->wg_sums, (size_t)n_wg * 5 * sizeof(double), "per-workgroup sums of the one-pass step") ? (size_t)n_wg : 0;
+            { const int rc_ = P->mem.status(); if (rc_) return rc_; }
         }
         int copies = (4608) / (nb * 12);   // (static 26 KB + this: five workgroups of 256 threads per CU)
         copies = copies < 1 ? 1 : (copies > 16 ? 16 : copies);
@@ -1482,6 +1462,36 @@ int nk_step_values(xdemhip_nk_plan* P, double shift_x, double shift_y, double re
     return XDEMHIP_OK;
 }
 
+// The device side of xdemhip_binned_median: the m finite (x, y) pairs binned on SciPy's edges over [smin, smax], one median per bin.
+template <typename T>
+int binned_median_typed(xdemhip_ctx* ctx, const void* xs, const void* ys, int64_t m, double smin, double smax, int n_bins, double* edges,
+                        int64_t* counts, double* medians) {
+    std::vector<T> e;   // (sources of copies queued on the stream: declared before the buffers)
+    make_edges<T>(smin, smax, n_bins, e);
+    const std::vector<T> ones((size_t)m, (T)1);
+    XdBuffers buf(ctx, "xdemhip_binned_median");
+    const T* d_x = static_cast<const T*>(buf.input(xs, (size_t)m * sizeof(T), XDEMHIP_HOST));
+    const T* d_y = static_cast<const T*>(buf.input(ys, (size_t)m * sizeof(T), XDEMHIP_HOST));
+    const T* d_one = buf.input(ones.data(), (size_t)m * sizeof(T), XDEMHIP_HOST);
+    T* d_yb = buf.alloc<T>((size_t)m);
+    uint16_t* d_bins = buf.alloc<uint16_t>((size_t)m);
+    unsigned char* base = buf.alloc<unsigned char>(scratch_size(n_bins));
+    if (buf.rc) return buf.rc;
+    double* d_sums = reinterpret_cast<double*>(base + OFF_SUMS);
+    XD_HIP_CHECK(ctx, hipMemsetAsync(d_sums, 0, 16, ctx->stream));
+    XD_HIP_CHECK(ctx, hipMemcpyAsync(base, e.data(), sizeof(T) * (n_bins + 1), hipMemcpyHostToDevice, ctx->stream));
+    // reuse nk_y_kernel with vshift = 0 and slope_tan = 1: y passes through unchanged ((y - 0) / 1 is exact)
+    hipLaunchKernelGGL((nk_y_kernel<T>), dim3(grid_for(ctx, m, 256, 16)), dim3(256), sizeof(T) * (n_bins + 1), ctx->stream, d_y, d_one, d_x, m, (T)0,
+                       reinterpret_cast<const T*>(base), n_bins, d_yb, d_bins, d_sums);
+    std::vector<SelResult<typename KeyT<T>::type>> hs;
+    XdLocalSelection local(ctx);   // (a purely local helper)
+    const int rc = run_select<T>(ctx, d_yb, d_bins, m, n_bins, base, hs);
+    if (rc) return rc;
+    for (int k = 0; k < n_bins; ++k) { counts[k] = (int64_t)hs[k].st.count; medians[k] = median_from<T>(hs[k]); }
+    for (int k = 0; k <= n_bins; ++k) edges[k] = (double)e[k];
+    return buf.finish();
+}
+
 // Shared by the two creation entry points.  Buffers hold raster rows [roff, roff + nbuf); own rows [row0, row1).
 int nk_create_impl(xdemhip_ctx* ctx, const void* ref, const void* tba, const uint8_t* inlier, int dtype, int64_t H, int64_t W,
                    int64_t roff, int64_t nbuf, int64_t row0, int64_t row1, int memspace, bool global_count,
@@ -1494,43 +1504,34 @@ int nk_create_impl(xdemhip_ctx* ctx, const void* ref, const void* tba, const uin
     const size_t es = dtype == XDEMHIP_F32 ? 4 : 8;
     const size_t n = (size_t)nbuf * (size_t)W;
     xdemhip_nk_plan* P = new xdemhip_nk_plan();
-    P->ctx = ctx; P->dtype = dtype; P->H = H; P->W = W; P->roff = roff; P->nbuf = nbuf; P->row0 = row0; P->row1 = row1;
+    P->ctx = P->mem.ctx = ctx; P->dtype = dtype; P->H = H; P->W = W; P->roff = roff; P->nbuf = nbuf; P->row0 = row0; P->row1 = row1;
     P->nan_rule = ctx->nk_nan_rule;
-    auto fail = [&](int code, const char* msg) { xdemhip_nk_destroy(P); return xd_fail(ctx, code, msg); };
-    if (memspace == XDEMHIP_HOST) {
-        P->own_inputs = true;
-        if (hipMalloc(&P->ref, n * es) != hipSuccess || hipMalloc(&P->tba, n * es) != hipSuccess) return fail(XDEMHIP_ENOMEM, "hipMalloc failed");
-        if (hipMemcpyAsync(P->ref, ref, n * es, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
-            hipMemcpyAsync(P->tba, tba, n * es, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return fail(XDEMHIP_EHIP, "H2D copy failed");
-        if (inlier) {
-            if (hipMalloc(reinterpret_cast<void**>(&P->inlier), n) != hipSuccess) return fail(XDEMHIP_ENOMEM, "hipMalloc failed");
-            if (hipMemcpyAsync(P->inlier, inlier, n, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return fail(XDEMHIP_EHIP, "H2D copy failed");
-        }
-    } else {
-        P->ref = const_cast<void*>(ref);
-        P->tba = const_cast<void*>(tba);
-        P->inlier = const_cast<uint8_t*>(inlier);
-    }
+    auto fail = [&](int code) { delete P; return code; };
+    const char* who = "xdemhip_nk_create";
+    XdOwned& mem = P->mem;
+    P->ref = mem.keep(ref, n * es, memspace, who);
+    P->tba = mem.keep(tba, n * es, memspace, who);
+    P->inlier = mem.keep(inlier, n, memspace, who);
     P->max_bins = 1024;
     P->scratch_bytes = scratch_size(P->max_bins);
-    if (hipMalloc(&P->slope_tan, n * es) != hipSuccess || hipMalloc(&P->aspect, n * es) != hipSuccess ||
-        hipMalloc(&P->dh, n * es) != hipSuccess || hipMalloc(&P->y, n * es) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&P->valid), n) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&P->bins), n * 2) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&P->bcache), n * sizeof(nk_bin_t)) != hipSuccess || hipMalloc(&P->scratch, P->scratch_bytes) != hipSuccess)
-        return fail(XDEMHIP_ENOMEM, "hipMalloc failed");
-    if ((int64_t)n >= SEL_BRACKET_MIN_N && sel_ws_create(ctx, (int64_t)n, es, MAX_BINS_PER_SWEEP, P->ws) != XDEMHIP_OK)
-        return fail(XDEMHIP_ENOMEM, "hipMalloc failed");
+    P->slope_tan = mem.take(n * es, who);
+    P->aspect = mem.take(n * es, who);
+    P->dh = mem.take(n * es, who);
+    P->y = mem.take(n * es, who);
+    P->valid = mem.take<uint8_t>(n, who);
+    P->bins = mem.take<uint16_t>(n, who);
+    P->bcache = mem.take<nk_bin_t>(n, who);
+    P->scratch = mem.take(P->scratch_bytes, who);
+    if (mem.rc) return fail(mem.rc);
+    if ((int64_t)n >= SEL_BRACKET_MIN_N && sel_ws_create(mem, (int64_t)n, es, MAX_BINS_PER_SWEEP, P->ws) != XDEMHIP_OK) return fail(XDEMHIP_ENOMEM);
     // EXT buffers of the one-pass step (large plans): masked copy of the reference DEM + the lists of extreme-aspect pixels;
     // without the memory for them the plan simply keeps the plain route, which reads mask and aspect
     if ((int64_t)n >= SEL_BRACKET_MIN_N && ctx->nk_fused != 0) {
-        if (hipMalloc(&P->ref_m, n * es) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&P->ext_idx), (size_t)2 * EXT_CAP * 8) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void**>(&P->ext_cnt), 32) != hipSuccess) {
-            (void)hipGetLastError();
-            if (P->ref_m) (void)hipFree(P->ref_m);
-            if (P->ext_idx) (void)hipFree(P->ext_idx);
-            if (P->ext_cnt) (void)hipFree(P->ext_cnt);
-            P->ref_m = nullptr; P->ext_idx = nullptr; P->ext_cnt = nullptr;
-        }
+        mem.optional();
+        P->ref_m = mem.take(n * es, who);
+        P->ext_idx = mem.take<int64_t>((size_t)2 * EXT_CAP, who);
+        P->ext_cnt = mem.take<unsigned long long>(4, who);
+        (void)mem.all_or_none(P->ref_m, P->ext_idx, P->ext_cnt);
     }
     // one-pass step (large single-GPU plans with the EXT buffers): its device block and candidate buffers; without the memory the
     // plan keeps the plain route
@@ -1540,37 +1541,33 @@ int nk_create_impl(xdemhip_ctx* ctx, const void* ref, const void* tba, const uin
         P->fz_bytes = (size_t)(24 + (11 + BINSEG_CTR_STRIDE) * P->ws.nb_max + DSEL_HDR_WORDS + DSEL_BUCKETS / 2) * 8;
         P->cd_cap = (int64_t)n / 8 + 4096;
         P->fz_pack_bytes = (size_t)P->ws.nb_max * (8 * 3 + 8 + 16 + 64 + 8 + 8 * 3 + 16) + 1024;
-        if (hipMalloc(reinterpret_cast<void**>(&P->fz), P->fz_bytes + (size_t)DSEL_CAP * 8) != hipSuccess || hipMalloc(&P->cd_vals, (size_t)P->cd_cap * es) != hipSuccess ||
-            hipMalloc(&P->c_st, (size_t)P->ws.c_cap * es) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&P->fz_pack), P->fz_pack_bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            if (P->fz) (void)hipFree(P->fz);
-            if (P->cd_vals) (void)hipFree(P->cd_vals);
-            if (P->c_st) (void)hipFree(P->c_st);
-            if (P->fz_pack) (void)hipFree(P->fz_pack);
-            P->fz = nullptr; P->cd_vals = nullptr; P->c_st = nullptr; P->fz_pack = nullptr;
-        }
+        mem.optional();
+        P->fz = static_cast<uint64_t*>(mem.take(P->fz_bytes + (size_t)DSEL_CAP * 8, who));
+        P->cd_vals = mem.take((size_t)P->cd_cap * es, who);
+        P->c_st = mem.take((size_t)P->ws.c_cap * es, who);
+        P->fz_pack = mem.take<unsigned char>(P->fz_pack_bytes, who);
+        (void)mem.all_or_none(P->fz, P->cd_vals, P->c_st, P->fz_pack);
     }
     // rules 2 / 3 on plans large enough for the streaming kernels (whole rasters and row blocks alike): the per-pixel neighbourhood
     // flags of the tba buffer, once
     if (P->nan_rule >= 2 && (int64_t)n >= SEL_BRACKET_MIN_N) {
         P->bad_wpr = (W + 63) / 64 + 2;
-        if (hipMalloc(reinterpret_cast<void**>(&P->badbits), (size_t)P->bad_wpr * (size_t)nbuf * 8) != hipSuccess) {
-            (void)hipGetLastError();
-            P->badbits = nullptr;   // (the plan keeps the generic kernels)
-        } else {
+        mem.optional();
+        P->badbits = mem.take<uint64_t>((size_t)P->bad_wpr * (size_t)nbuf, who);
+        if (mem.all_or_none(P->badbits)) {   // (without them the plan keeps the generic kernels)
             const dim3 bgrid((unsigned)((P->bad_wpr - 2 + 3) / 4), (unsigned)(nbuf < 4096 ? nbuf : 4096));
             if (dtype == XDEMHIP_F32)
                 hipLaunchKernelGGL((nk_badbits_kernel<float>), bgrid, dim3(256), 0, ctx->stream, static_cast<const float*>(P->tba), H, W, roff, nbuf, P->nan_rule, P->bad_wpr, P->badbits);
             else
                 hipLaunchKernelGGL((nk_badbits_kernel<double>), bgrid, dim3(256), 0, ctx->stream, static_cast<const double*>(P->tba), H, W, roff, nbuf, P->nan_rule, P->bad_wpr, P->badbits);
-            if (hipGetLastError() != hipSuccess) return fail(XDEMHIP_EHIP, "nk_badbits_kernel launch failed");
+            if (launched(ctx, "nk_badbits_kernel")) return fail(XDEMHIP_EHIP);
         }
     }
     const xdemhip_allreduce_fn hook = ctx->allreduce;
     if (!global_count) ctx->allreduce = nullptr;  // whole-raster plan: local pass; xdemhip_nk_set_rows re-partitions with the hook
     int rc = dtype == XDEMHIP_F32 ? nk_aux_typed<float>(P) : nk_aux_typed<double>(P);
     ctx->allreduce = hook;
-    if (rc != XDEMHIP_OK) { xdemhip_nk_destroy(P); return rc; }
+    if (rc != XDEMHIP_OK) return fail(rc);
     if (n_valid) *n_valid = P->n_valid0;
     *out_plan = P;
     return XDEMHIP_OK;
@@ -1580,19 +1577,7 @@ int nk_create_impl(xdemhip_ctx* ctx, const void* ref, const void* tba, const uin
 
 extern "C" {
 
-void xdemhip_nk_destroy(xdemhip_nk_plan* P) {
-    if (!P) return;
-    (void)hipSetDevice(P->ctx->device);
-    uint8_t* inl_created = P->subsampled ? P->inlier_user : P->inlier;
-    if (P->own_inputs) { (void)hipFree(P->ref); (void)hipFree(P->tba); if (inl_created) (void)hipFree(inl_created); }
-    if (P->sub_inlier) (void)hipFree(P->sub_inlier);
-    void* bufs[] = {P->slope_tan, P->aspect, P->dh, P->y, P->valid, P->bins, P->bcache, P->scratch, P->ref_m, P->ext_idx, P->ext_cnt,
-                    P->fz, P->cd_vals, P->c_st, P->fz_pack, P->badbits, P->mr_a, P->mr_b, P->mr_small, P->wg_sums};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
-    xd::sel_ws_free(P->ws);
-    delete P;
-}
+void xdemhip_nk_destroy(xdemhip_nk_plan* P) { delete P; }   // (its owner frees the device buffers)
 
 int xdemhip_nk_create(xdemhip_ctx* ctx, const void* ref, const void* tba, const uint8_t* inlier, int dtype, int64_t H, int64_t W,
                       int memspace, xdemhip_nk_plan** out_plan, int64_t* n_valid) {
@@ -1643,21 +1628,17 @@ int xdemhip_nk_subsample(xdemhip_nk_plan* P, const int64_t* ranks, int64_t k, in
     XD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     const int64_t n = P->H * P->W, n_tiles = (n + RANK_TILE - 1) / RANK_TILE;
     if (n_tiles > 0x7FFFFFFF) return xd_fail(ctx, XDEMHIP_EINVAL, "xdemhip_nk_subsample: raster too large");
-    if (!P->sub_inlier && hipMalloc(reinterpret_cast<void**>(&P->sub_inlier), (size_t)n) != hipSuccess) {
-        (void)hipGetLastError();
-        P->sub_inlier = nullptr;
-        return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed (xdemhip_nk_subsample)");
-    }
-    RankSelect rs;
+    if (!P->sub_inlier) P->sub_inlier = P->mem.take<uint8_t>((size_t)n, "xdemhip_nk_subsample");
+    { const int rc_ = P->mem.status(); if (rc_) return rc_; }
+    RankSelect rs(ctx, "xdemhip_nk_subsample");
     unsigned long long total = 0, bad = 0;
-    { const int rc_ = rs.run(ctx, "xdemhip_nk_subsample", ranks, k, memspace, P->n_valid0, P->valid, n, nullptr, &total, &bad); if (rc_) return rc_; }
+    { const int rc_ = rs.run(ranks, k, memspace, P->n_valid0, P->valid, n, nullptr, &total, &bad); if (rc_) return rc_; }
     if ((long long)total != P->n_valid0) return xd_fail(ctx, XDEMHIP_EINVAL, "xdemhip_nk_subsample: the valid mask changed under the call");
     if (bad != 0) return xd_fail(ctx, XDEMHIP_EINVAL, "xdemhip_nk_subsample: a rank is outside [0, n_valid)");
     hipLaunchKernelGGL((rank_select_kernel<RankOut::Mask>), dim3((unsigned)n_tiles), dim3(256), 0, ctx->stream, P->valid, n, rs.off, rs.mark,
                        (unsigned long long*)nullptr, (int64_t*)nullptr, P->sub_inlier);
     if (hipGetLastError() != hipSuccess) return xd_fail(ctx, XDEMHIP_EHIP, "xdemhip_nk_subsample: kernel launch failed");
-    if (!P->subsampled) { P->inlier_user = P->inlier; P->subsampled = true; }
-    P->inlier = P->sub_inlier;
+    P->inlier = P->sub_inlier;   // (an owned copy of the mask the plan was created with stays with the owner)
     // (as after xdemhip_nk_set_rows: other valid pixels -- no cached bins, no previous medians, no measured sample offsets)
     P->bcache_force = true;
     P->pr_have = false;
@@ -1783,17 +1764,12 @@ int xdemhip_shift_bilinear(xdemhip_ctx* ctx, const void* src, int dtype, int64_t
     if (dtype != XDEMHIP_F32 && dtype != XDEMHIP_F64) return xd_fail(ctx, XDEMHIP_EINVAL, "dtype must be float32 or float64");
     XD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     const size_t es = dtype == XDEMHIP_F32 ? 4 : 8, bytes = (size_t)H * (size_t)W * es;
-    void *d_src = const_cast<void*>(src), *d_out = out;
     XdPrefault prefault;
-    if (memspace == XDEMHIP_HOST) {
-        d_src = d_out = nullptr;
-        if (hipMalloc(&d_src, bytes) != hipSuccess || hipMalloc(&d_out, bytes) != hipSuccess) {
-            if (d_src) (void)hipFree(d_src);
-            return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed");
-        }
-        (void)hipMemcpyAsync(d_src, src, bytes, hipMemcpyHostToDevice, ctx->stream);
-        xd_prefault_start(prefault, out, bytes, ctx->host_copy_threads);   // (the caller's output pages, while the raster travels and the kernel runs)
-    }
+    XdBuffers buf(ctx, "xdemhip_shift_bilinear");
+    const void* d_src = buf.input(src, bytes, memspace);
+    void* d_out = buf.output(out, bytes, memspace);
+    if (buf.rc) return buf.rc;
+    if (memspace == XDEMHIP_HOST) xd_prefault_start(prefault, out, bytes, ctx->host_copy_threads);   // (the caller's output pages, while the raster travels and the kernel runs)
     const int64_t n = H * W;
     XD_HIP_CHECK(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
     NkGeom g;
@@ -1806,17 +1782,9 @@ int xdemhip_shift_bilinear(xdemhip_ctx* ctx, const void* src, int dtype, int64_t
                            static_cast<const double*>(d_src), g, dz, static_cast<double*>(d_out));
     (void)hipEventRecord(ctx->ev_stop, ctx->stream);
     ctx->timed = true;
-    int rc = XDEMHIP_OK;
-    if (hipGetLastError() != hipSuccess) rc = xd_fail(ctx, XDEMHIP_EHIP, "shift kernel launch failed");
-    if (memspace == XDEMHIP_HOST) {
-        prefault.join();
-        if (rc == XDEMHIP_OK && (hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-                                 hipStreamSynchronize(ctx->stream) != hipSuccess))
-            rc = xd_fail(ctx, XDEMHIP_EHIP, "shift kernel / D2H failed");
-        (void)hipFree(d_src);
-        (void)hipFree(d_out);
-    }
-    return rc;
+    const int rc = launched(ctx, "shift kernel");
+    prefault.join();
+    return rc ? rc : buf.finish();
 }
 
 // Stand-alone binned nanmedian: binned_statistic(x, y, np.nanmedian, n_bins) + counts on SciPy's edges.
@@ -1846,52 +1814,8 @@ int xdemhip_binned_median(xdemhip_ctx* ctx, const void* x, const void* y, int dt
         ++m;
     }
     if (m == 0) { for (int k = 0; k < n_bins; ++k) { counts[k] = 0; medians[k] = NAN; } return XDEMHIP_OK; }
-    void *d_x = nullptr, *d_y = nullptr, *d_one = nullptr, *d_yb = nullptr, *scratch = nullptr;
-    uint16_t* d_bins = nullptr;
-    auto cleanup = [&]() { void* b[] = {d_x, d_y, d_one, d_yb, scratch, d_bins}; for (void* p : b) if (p) (void)hipFree(p); };
-    if (hipMalloc(&d_x, m * es) != hipSuccess || hipMalloc(&d_y, m * es) != hipSuccess || hipMalloc(&d_one, m * es) != hipSuccess ||
-        hipMalloc(&d_yb, m * es) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&d_bins), m * 2) != hipSuccess ||
-        hipMalloc(&scratch, scratch_size(n_bins)) != hipSuccess) { cleanup(); return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed"); }
-    (void)hipMemcpyAsync(d_x, xs.data(), m * es, hipMemcpyHostToDevice, ctx->stream);
-    (void)hipMemcpyAsync(d_y, ys.data(), m * es, hipMemcpyHostToDevice, ctx->stream);
-    unsigned char* base = static_cast<unsigned char*>(scratch);
-    double* d_sums = reinterpret_cast<double*>(base + OFF_SUMS);
-    (void)hipMemsetAsync(d_sums, 0, 16, ctx->stream);
-    int rc;
-    const xdemhip_allreduce_fn hook = ctx->allreduce;
-    ctx->allreduce = nullptr;  // a purely local helper
-    if (dtype == XDEMHIP_F32) {
-        std::vector<float> e; make_edges<float>(smin, smax, n_bins, e);
-        std::vector<float> ones((size_t)m, 1.0f);
-        (void)hipMemcpyAsync(d_one, ones.data(), m * es, hipMemcpyHostToDevice, ctx->stream);
-        (void)hipMemcpyAsync(base, e.data(), sizeof(float) * (n_bins + 1), hipMemcpyHostToDevice, ctx->stream);
-        // reuse nk_y_kernel with vshift = 0 and slope_tan = 1: y passes through unchanged ((y - 0) / 1 is exact)
-        hipLaunchKernelGGL((nk_y_kernel<float>), dim3(grid_for(ctx, m, 256, 16)), dim3(256), sizeof(float) * (n_bins + 1), ctx->stream,
-                           static_cast<const float*>(d_y), static_cast<const float*>(d_one), static_cast<const float*>(d_x), m, 0.0f,
-                           reinterpret_cast<const float*>(base), n_bins, static_cast<float*>(d_yb), d_bins, d_sums);
-        std::vector<SelResult<uint32_t>> hs;
-        rc = run_select<float>(ctx, static_cast<const float*>(d_yb), d_bins, m, n_bins, base, hs);
-        if (rc == XDEMHIP_OK)
-            for (int k = 0; k < n_bins; ++k) { counts[k] = (int64_t)hs[k].st.count; medians[k] = median_from<float>(hs[k]); }
-        for (int k = 0; k <= n_bins; ++k) edges[k] = (double)e[k];
-    } else {
-        std::vector<double> e; make_edges<double>(smin, smax, n_bins, e);
-        std::vector<double> ones((size_t)m, 1.0);
-        (void)hipMemcpyAsync(d_one, ones.data(), m * es, hipMemcpyHostToDevice, ctx->stream);
-        (void)hipMemcpyAsync(base, e.data(), sizeof(double) * (n_bins + 1), hipMemcpyHostToDevice, ctx->stream);
-        hipLaunchKernelGGL((nk_y_kernel<double>), dim3(grid_for(ctx, m, 256, 16)), dim3(256), sizeof(double) * (n_bins + 1), ctx->stream,
-                           static_cast<const double*>(d_y), static_cast<const double*>(d_one), static_cast<const double*>(d_x), m, 0.0,
-                           reinterpret_cast<const double*>(base), n_bins, static_cast<double*>(d_yb), d_bins, d_sums);
-        std::vector<SelResult<uint64_t>> hs;
-        rc = run_select<double>(ctx, static_cast<const double*>(d_yb), d_bins, m, n_bins, base, hs);
-        if (rc == XDEMHIP_OK)
-            for (int k = 0; k < n_bins; ++k) { counts[k] = (int64_t)hs[k].st.count; medians[k] = median_from<double>(hs[k]); }
-        for (int k = 0; k <= n_bins; ++k) edges[k] = (double)e[k];
-    }
-    ctx->allreduce = hook;
-    (void)hipStreamSynchronize(ctx->stream);
-    cleanup();
-    return rc;
+    return dtype == XDEMHIP_F32 ? binned_median_typed<float>(ctx, xs.data(), ys.data(), m, smin, smax, n_bins, edges, counts, medians)
+                                : binned_median_typed<double>(ctx, xs.data(), ys.data(), m, smin, smax, n_bins, edges, counts, medians);
 }
 
 }  // extern "C"

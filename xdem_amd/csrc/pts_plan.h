@@ -16,8 +16,8 @@ struct xdemhip_pts_plan {
     bool pts_is_ref = false;                  // dh = z - raster(x + sx, y + sy); otherwise raster(x - sx, y - sy) - z
     bool with_aux = false;
     int nan_rule = 0;                         // the tap rule the plan was created under (option "nk_nan_rule")
-    bool own_raster = false, own_cloud = false;
-    void* raster = nullptr;
+    XdOwned mem;                              // every device buffer of the plan but the caller's own device arrays
+    void* raster = nullptr;                   // the raster and the cloud: the caller's device arrays, or owned copies of its host arrays
     double* x = nullptr;                      // the cloud's columns, n_pts values each, cloud order
     double* y = nullptr;
     void* z = nullptr;                        // raster dtype

@@ -253,9 +253,8 @@ PtsGeo pts_geo(const xdemhip_pts_plan* P, double shift_x, double shift_y) {
 }
 
 void free_selection(xdemhip_pts_plan* P) {
-    void* b[] = {P->idx, P->sx, P->sy, P->sz, P->sst, P->sasp, P->order};
-    for (void* p : b)
-        if (p) (void)hipFree(p);
+    const void* b[] = {P->idx, P->sx, P->sy, P->sz, P->sst, P->sasp, P->order};
+    for (const void* p : b) P->mem.drop(p);
     P->idx = nullptr; P->sx = P->sy = nullptr; P->sz = P->sst = P->sasp = nullptr; P->order = nullptr;
     P->m = 0;
     P->y_n = -1;
@@ -265,11 +264,14 @@ void free_selection(xdemhip_pts_plan* P) {
 template <typename T> int build_selection(xdemhip_pts_plan* P) {
     xdemhip_ctx* ctx = P->ctx;
     const int64_t m = P->m;
-    const size_t mm = (size_t)(m > 0 ? m : 1);
-    bool bad = hipMalloc(reinterpret_cast<void**>(&P->sx), mm * 8) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&P->sy), mm * 8) != hipSuccess ||
-               hipMalloc(&P->sz, mm * sizeof(T)) != hipSuccess;
-    if (!bad && P->with_aux) bad = hipMalloc(&P->sst, mm * sizeof(T)) != hipSuccess || hipMalloc(&P->sasp, mm * sizeof(T)) != hipSuccess;
-    if (bad) { (void)hipGetLastError(); return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed (selected points)"); }
+    P->sx = P->mem.take<double>((size_t)m, "selected points");
+    P->sy = P->mem.take<double>((size_t)m, "selected points");
+    P->sz = P->mem.take<T>((size_t)m, "selected points");
+    if (P->with_aux) {
+        P->sst = P->mem.take<T>((size_t)m, "selected points");
+        P->sasp = P->mem.take<T>((size_t)m, "selected points");
+    }
+    { const int rc = P->mem.status(); if (rc) return rc; }
     if (m == 0) return XDEMHIP_OK;
     hipLaunchKernelGGL((pts_gather_kernel<T>), dim3(grid_for(ctx, m, 256, 16)), dim3(256), 0, ctx->stream, P->idx, m, P->x, P->y,
                        static_cast<const T*>(P->z), static_cast<const T*>(P->a_st), static_cast<const T*>(P->a_asp), P->sx, P->sy,
@@ -283,11 +285,8 @@ template <typename T> int build_selection(xdemhip_pts_plan* P) {
     uint32_t* tile = buf.alloc<uint32_t>((size_t)m);
     unsigned long long* cnt = buf.alloc<unsigned long long>((size_t)nt + 2);
     if (buf.rc) return buf.rc;
-    if (hipMalloc(reinterpret_cast<void**>(&P->order), (size_t)m * 8) != hipSuccess) {
-        (void)hipGetLastError();
-        P->order = nullptr;
-        return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed (tile order)");
-    }
+    P->order = P->mem.take<int64_t>((size_t)m, "tile order");
+    { const int rc = P->mem.status(); if (rc) return rc; }
     XD_HIP_CHECK(ctx, hipMemsetAsync(cnt, 0, (size_t)(nt + 2) * 8, ctx->stream));
     const PtsGeo q = pts_geo(P, 0.0, 0.0);
     const dim3 grid(grid_for(ctx, m, 256, 16));
@@ -301,39 +300,26 @@ template <typename T> int build_selection(xdemhip_pts_plan* P) {
 int ensure_step(xdemhip_pts_plan* P, bool with_y) {
     xdemhip_ctx* ctx = P->ctx;
     const size_t es = es_of(P);
-    const size_t mm = (size_t)(P->m > 0 ? P->m : 1);
-    if (!P->scratch && hipMalloc(reinterpret_cast<void**>(&P->scratch), pts_scratch_bytes()) != hipSuccess) {
-        (void)hipGetLastError();
-        P->scratch = nullptr;
-        return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed (raster-point plan: selection scratch)");
-    }
+    const size_t mm = (size_t)P->m;
+    XdOwned& mem = P->mem;
+    if (!P->scratch) P->scratch = mem.take<unsigned char>(pts_scratch_bytes(), "raster-point plan: selection scratch");
     if (P->step_n != P->m) {
-        (void)hipStreamSynchronize(ctx->stream);
-        if (P->dh) (void)hipFree(P->dh);
-        if (P->yv) (void)hipFree(P->yv);
-        if (P->bins) (void)hipFree(P->bins);
-        P->dh = P->yv = nullptr; P->bins = nullptr;
-        P->step_n = -1;
+        mem.drop(P->yv);
+        mem.drop(P->bins);
+        P->yv = nullptr; P->bins = nullptr;
         P->y_n = -1;
-        if (hipMalloc(&P->dh, mm * es) != hipSuccess) {
-            (void)hipGetLastError();
-            P->dh = nullptr;
-            return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed (raster-point plan: dh column)");
-        }
-        P->step_n = P->m;
+        P->step_n = mem.regrow(P->dh, mm * es, "raster-point plan: dh column") ? P->m : -1;
     }
-    if (with_y && !P->yv) {
-        if (hipMalloc(&P->yv, mm * es) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&P->bins), mm * 2) != hipSuccess) {
-            (void)hipGetLastError();
-            if (P->yv) (void)hipFree(P->yv);
-            P->yv = nullptr; P->bins = nullptr;
-            return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed (raster-point plan: y column)");
-        }
+    { const int rc = mem.status(); if (rc) return rc; }
+    if (with_y && !P->yv) {   // (both or neither: a later step asks again)
+        mem.optional();
+        P->yv = mem.take(mm * es, "raster-point plan: y column");
+        P->bins = mem.take<uint16_t>(mm, "raster-point plan: y column");
+        if (!mem.all_or_none(P->yv, P->bins)) return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed (raster-point plan: y column)");
     }
     if (P->ws_n != P->m) {
-        (void)hipStreamSynchronize(ctx->stream);
-        sel_ws_free(P->ws);
-        if (P->m >= SEL_BRACKET_MIN_N) (void)sel_ws_create(ctx, P->m, es, MAX_BINS_PER_SWEEP, P->ws);   // (on failure: plain selection)
+        sel_ws_free(mem, P->ws);
+        if (P->m >= SEL_BRACKET_MIN_N) (void)sel_ws_create(mem, P->m, es, MAX_BINS_PER_SWEEP, P->ws);   // (on failure: plain selection)
         P->ws_n = P->m;
     }
     return XDEMHIP_OK;
@@ -363,7 +349,7 @@ int nk_step_typed(xdemhip_pts_plan* P, double shift_x, double shift_y, int nb, d
     xdemhip_ctx* ctx = P->ctx;
     int rc = ensure_step(P, true);
     if (rc) return rc;
-    rc = P->sums.reserve(ctx, 3, "xdemhip_pts_nk_step");
+    rc = P->sums.reserve(P->mem, 3, "xdemhip_pts_nk_step");
     if (rc) return rc;
     const int64_t m = P->m;
     unsigned char* base = P->scratch;
@@ -458,11 +444,8 @@ int create_typed(xdemhip_pts_plan* P, const uint8_t* inlier_host_or_dev, int mem
     P->n_valid = (int64_t)total;
     // the selection: every valid point
     P->m = P->n_valid;
-    if (hipMalloc(reinterpret_cast<void**>(&P->idx), (size_t)(P->m > 0 ? P->m : 1) * 8) != hipSuccess) {
-        (void)hipGetLastError();
-        P->idx = nullptr;
-        return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed (valid point list)");
-    }
+    P->idx = P->mem.take<int64_t>((size_t)P->m, "valid point list");
+    if (P->mem.rc) return P->mem.rc;
     hipLaunchKernelGGL((rank_select_kernel<RankOut::List>), dim3((unsigned)P->n_tiles), dim3(256), 0, ctx->stream, P->pvalid, P->n_pts,
                        (const unsigned long long*)nullptr, (const uint8_t*)nullptr, P->tile_off, P->idx, (uint8_t*)nullptr);
     if (launched(ctx, "xdemhip_pts_create: list kernel")) return XDEMHIP_EHIP;
@@ -476,24 +459,7 @@ using namespace xd;
 
 extern "C" {
 
-void xdemhip_pts_destroy(xdemhip_pts_plan* P) {
-    if (!P) return;
-    (void)hipSetDevice(P->ctx->device);
-    (void)hipStreamSynchronize(P->ctx->stream);
-    if (P->own_raster && P->raster) (void)hipFree(P->raster);
-    if (P->own_cloud) {
-        if (P->x) (void)hipFree(P->x);
-        if (P->y) (void)hipFree(P->y);
-        if (P->z) (void)hipFree(P->z);
-    }
-    void* b[] = {P->pvalid, P->tile_off, P->a_st, P->a_asp, P->dh, P->yv, P->bins, P->scratch, P->d_custom};
-    for (void* p : b)
-        if (p) (void)hipFree(p);
-    free_selection(P);
-    P->sums.release();
-    sel_ws_free(P->ws);
-    delete P;
-}
+void xdemhip_pts_destroy(xdemhip_pts_plan* P) { delete P; }   // (its owner frees the device buffers)
 
 int xdemhip_pts_create(xdemhip_ctx* ctx, const void* raster, const uint8_t* inlier, int dtype, int64_t H, int64_t W, const double* transform6,
                        const double* x, const double* y, const void* z, int64_t n_pts, int pts_is_ref, int with_nk_aux, int memspace,
@@ -509,40 +475,27 @@ int xdemhip_pts_create(xdemhip_ctx* ctx, const void* raster, const uint8_t* inli
     XD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     const size_t es = dtype == XDEMHIP_F32 ? 4 : 8;
     xdemhip_pts_plan* P = new xdemhip_pts_plan();
-    P->ctx = ctx; P->dtype = dtype; P->H = H; P->W = W; P->n_pts = n_pts;
+    P->ctx = P->mem.ctx = ctx; P->dtype = dtype; P->H = H; P->W = W; P->n_pts = n_pts;
     memcpy(P->t6, transform6, sizeof P->t6);
     P->pts_is_ref = pts_is_ref != 0;
     P->with_aux = with_nk_aux != 0;
     P->nan_rule = ctx->nk_nan_rule;
     P->n_tiles = (n_pts + RANK_TILE - 1) / RANK_TILE;
-    auto fail = [&](int code) { xdemhip_pts_destroy(P); return code; };
+    auto fail = [&](int code) { delete P; return code; };
     if (P->n_tiles > 0x7FFFFFFF) return fail(xd_fail(ctx, XDEMHIP_EINVAL, "xdemhip_pts_create: cloud too large"));
-    int rc = xd_upload_keep(ctx, raster, (size_t)(H * W) * es, memspace, &P->raster, &P->own_raster);
-    if (rc) return fail(rc);
-    {
-        // (the three columns are owned together or not at all: a column that fails to upload frees the ones before it)
-        void* d[3] = {nullptr, nullptr, nullptr};
-        const void* src[3] = {x, y, z};
-        const size_t bytes[3] = {(size_t)n_pts * 8, (size_t)n_pts * 8, (size_t)n_pts * es};
-        bool own = false;
-        for (int k = 0; k < 3 && rc == XDEMHIP_OK; ++k) rc = xd_upload_keep(ctx, src[k], bytes[k], memspace, &d[k], &own);
-        if (rc) {
-            if (memspace == XDEMHIP_HOST)
-                for (void* p : d)
-                    if (p) (void)hipFree(p);
-            return fail(rc);
-        }
-        P->x = static_cast<double*>(d[0]); P->y = static_cast<double*>(d[1]); P->z = d[2];
-        P->own_cloud = memspace == XDEMHIP_HOST;
+    XdOwned& mem = P->mem;
+    P->raster = mem.keep(raster, (size_t)(H * W) * es, memspace, "xdemhip_pts_create");
+    P->x = mem.keep(x, (size_t)n_pts * 8, memspace, "xdemhip_pts_create");
+    P->y = mem.keep(y, (size_t)n_pts * 8, memspace, "xdemhip_pts_create");
+    P->z = mem.keep(z, (size_t)n_pts * es, memspace, "xdemhip_pts_create");
+    P->pvalid = mem.take<uint8_t>((size_t)P->n_tiles * RANK_TILE, "xdemhip_pts_create");
+    P->tile_off = mem.take<unsigned long long>((size_t)P->n_tiles + 1, "xdemhip_pts_create");
+    if (P->with_aux) {
+        P->a_st = mem.take((size_t)n_pts * es, "xdemhip_pts_create");
+        P->a_asp = mem.take((size_t)n_pts * es, "xdemhip_pts_create");
     }
-    bool bad = hipMalloc(reinterpret_cast<void**>(&P->pvalid), (size_t)P->n_tiles * RANK_TILE) != hipSuccess ||
-               hipMalloc(reinterpret_cast<void**>(&P->tile_off), (size_t)(P->n_tiles + 1) * 8) != hipSuccess;
-    if (!bad && P->with_aux) bad = hipMalloc(&P->a_st, (size_t)n_pts * es) != hipSuccess || hipMalloc(&P->a_asp, (size_t)n_pts * es) != hipSuccess;
-    if (bad) {
-        (void)hipGetLastError();
-        return fail(xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed (xdemhip_pts_create)"));
-    }
-    rc = dtype == XDEMHIP_F32 ? create_typed<float>(P, inlier, memspace) : create_typed<double>(P, inlier, memspace);
+    if (mem.rc) return fail(mem.rc);
+    int rc = dtype == XDEMHIP_F32 ? create_typed<float>(P, inlier, memspace) : create_typed<double>(P, inlier, memspace);
     if (rc == XDEMHIP_OK) rc = xd_sync(ctx);
     if (rc) return fail(rc);
     if (n_valid) *n_valid = P->n_valid;
@@ -557,21 +510,18 @@ int xdemhip_pts_subsample(xdemhip_pts_plan* P, const int64_t* ranks, int64_t k, 
     if (!ranks || k < 1 || k > P->n_valid) return xd_fail(ctx, XDEMHIP_EINVAL, "xdemhip_pts_subsample: 1 <= k <= the plan's valid points");
     if (memspace != XDEMHIP_HOST && memspace != XDEMHIP_DEVICE) return xd_fail(ctx, XDEMHIP_EINVAL, "bad memspace");
     XD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    RankSelect rs;
+    RankSelect rs(ctx, "xdemhip_pts_subsample");
     unsigned long long total = 0, bad = 0;
-    { const int rc_ = rs.run(ctx, "xdemhip_pts_subsample", ranks, k, memspace, P->n_valid, P->pvalid, P->n_pts, P->tile_off, &total, &bad); if (rc_) return rc_; }
+    { const int rc_ = rs.run(ranks, k, memspace, P->n_valid, P->pvalid, P->n_pts, P->tile_off, &total, &bad); if (rc_) return rc_; }
     if (bad != 0) return xd_fail(ctx, XDEMHIP_EINVAL, "xdemhip_pts_subsample: a rank is outside [0, n_valid)");
     if ((int64_t)total > k) return xd_fail(ctx, XDEMHIP_EINVAL, "xdemhip_pts_subsample: more points than ranks");
-    int64_t* idx = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&idx), (size_t)k * 8) != hipSuccess) {
-        (void)hipGetLastError();
-        return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed (xdemhip_pts_subsample)");
-    }
+    int64_t* idx = P->mem.take<int64_t>((size_t)k, "xdemhip_pts_subsample");
+    { const int rc_ = P->mem.status(); if (rc_) return rc_; }
     hipLaunchKernelGGL((rank_select_kernel<RankOut::List>), dim3((unsigned)P->n_tiles), dim3(256), 0, ctx->stream, P->pvalid, P->n_pts, P->tile_off,
                        rs.mark, rs.off, idx, (uint8_t*)nullptr);
     int rc = launched(ctx, "xdemhip_pts_subsample: kernel");
     if (rc == XDEMHIP_OK) rc = xd_sync(ctx);
-    if (rc) { (void)hipFree(idx); return rc; }
+    if (rc) { P->mem.drop(idx); return rc; }
     free_selection(P);
     P->idx = idx;
     P->m = (int64_t)total;
@@ -598,8 +548,8 @@ int xdemhip_pts_set_bin_edges(xdemhip_pts_plan* P, const double* edges, int n_ed
     if (!P) return XDEMHIP_EINVAL;
     xdemhip_ctx* ctx = P->ctx;
     XD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    (void)hipStreamSynchronize(ctx->stream);
-    if (P->d_custom) { (void)hipFree(P->d_custom); P->d_custom = nullptr; P->n_custom = 0; }
+    P->mem.drop(P->d_custom);
+    P->d_custom = nullptr; P->n_custom = 0;
     if (!edges) return XDEMHIP_OK;
     if (n_edges < 2 || n_edges > PTS_MAX_BINS + 1) return xd_fail(ctx, XDEMHIP_EINVAL, "xdemhip_pts_set_bin_edges: 2 to 1025 edges");
     for (int k = 1; k < n_edges; ++k)
@@ -610,11 +560,8 @@ int xdemhip_pts_set_bin_edges(xdemhip_pts_plan* P, const double* edges, int n_ed
         if (P->dtype == XDEMHIP_F32) reinterpret_cast<float*>(h.data())[k] = (float)edges[k];
         else reinterpret_cast<double*>(h.data())[k] = edges[k];
     }
-    if (hipMalloc(&P->d_custom, h.size()) != hipSuccess) {
-        (void)hipGetLastError();
-        P->d_custom = nullptr;
-        return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed (xdemhip_pts_set_bin_edges)");
-    }
+    P->d_custom = P->mem.take(h.size(), "xdemhip_pts_set_bin_edges");
+    { const int rc = P->mem.status(); if (rc) return rc; }
     XD_HIP_CHECK(ctx, hipMemcpyAsync(P->d_custom, h.data(), h.size(), hipMemcpyHostToDevice, ctx->stream));
     XD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     P->n_custom = n_edges - 1;

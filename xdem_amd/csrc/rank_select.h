@@ -127,37 +127,23 @@ __global__ __launch_bounds__(256) void rank_select_kernel(const uint8_t* __restr
 // The steps both subsample entry points share: the ranks to the device (if they are on the host), the marks cleared, the ranks
 // marked, the pixels of every tile counted and the counts scanned; then *total (pixels counted) and *bad (ranks outside
 // [0, n_ranks)) read back.  Counted are the valid pixels (valid_off == nullptr) or the valid pixels whose rank is marked.  The
-// temporaries live as long as the object: `mark` and `off` are what the caller's selection launch reads after run().
+// temporaries live as long as the object (the queued work that reads them is waited for when it goes): `mark` and `off` are what
+// the caller's selection launch reads after run().
 struct RankSelect {
+    XdBuffers buf;                        // `who`: the entry point, named in the error texts
     uint8_t* mark = nullptr;              // [n_ranks] 1 where a rank is listed
     unsigned long long* off = nullptr;    // [n_tiles] exclusive offsets of the counted pixels, [n_tiles] total, [n_tiles + 1] ranks out of range
-    int64_t* d_ranks = nullptr;
+    RankSelect(xdemhip_ctx* ctx, const char* who) : buf(ctx, who) {}
 
-    RankSelect() = default;
-    RankSelect(const RankSelect&) = delete;
-    RankSelect& operator=(const RankSelect&) = delete;
-    ~RankSelect() {
-        if (mark) (void)hipFree(mark);
-        if (off) (void)hipFree(off);
-        if (d_ranks) (void)hipFree(d_ranks);
-    }
-
-    // `who`: the entry point, named in the error texts
-    int run(xdemhip_ctx* ctx, const char* who, const int64_t* ranks, int64_t k, int memspace, int64_t n_ranks, const uint8_t* valid, int64_t n,
-            const unsigned long long* valid_off, unsigned long long* total, unsigned long long* bad) {
+    int run(const int64_t* ranks, int64_t k, int memspace, int64_t n_ranks, const uint8_t* valid, int64_t n, const unsigned long long* valid_off,
+            unsigned long long* total, unsigned long long* bad) {
+        xdemhip_ctx* ctx = buf.ctx;
+        const char* who = buf.who;
         const int64_t n_tiles = (n + RANK_TILE - 1) / RANK_TILE;
-        if (hipMalloc(reinterpret_cast<void**>(&mark), (size_t)n_ranks) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void**>(&off), (size_t)(n_tiles + 2) * 8) != hipSuccess ||
-            (memspace == XDEMHIP_HOST && hipMalloc(reinterpret_cast<void**>(&d_ranks), (size_t)k * 8) != hipSuccess)) {
-            (void)hipGetLastError();
-            return xd_fail(ctx, XDEMHIP_ENOMEM, std::string("hipMalloc failed (") + who + ")");
-        }
-        const int64_t* rk = ranks;
-        if (memspace == XDEMHIP_HOST) {
-            if (hipMemcpyAsync(d_ranks, ranks, (size_t)k * 8, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
-                return xd_fail(ctx, XDEMHIP_EHIP, "copy of the ranks failed");
-            rk = d_ranks;
-        }
+        mark = buf.alloc<uint8_t>((size_t)n_ranks);
+        off = buf.alloc<unsigned long long>((size_t)n_tiles + 2);
+        const int64_t* rk = buf.input(ranks, (size_t)k * 8, memspace);
+        if (buf.rc) return buf.rc;
         if (hipMemsetAsync(mark, 0, (size_t)n_ranks, ctx->stream) != hipSuccess || hipMemsetAsync(off + n_tiles, 0, 16, ctx->stream) != hipSuccess)
             return xd_fail(ctx, XDEMHIP_EHIP, "hipMemsetAsync failed");
         hipLaunchKernelGGL(rank_mark_kernel, dim3(grid_for(ctx, k, 256, 8)), dim3(256), 0, ctx->stream, rk, k, n_ranks, mark, off + n_tiles + 1);

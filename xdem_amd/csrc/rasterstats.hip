@@ -336,7 +336,7 @@ static int raster_stats_typed(xdemhip_ctx* ctx, const void* values, int64_t n, c
     const int mode = ctx->selection_mode;
     const bool try_brackets = mode != 1 && (mode == 2 || mode == 3 || n >= SEL_BRACKET_MIN_N);
     SelWorkspaceLocal lws(ctx);
-    if (try_brackets) (void)sel_ws_create(ctx, n, sizeof(T), 1, lws.ws);   // (on failure: the plain route)
+    if (try_brackets) (void)sel_ws_create(lws.mem, n, sizeof(T), 1, lws.ws);   // (on failure: the plain route)
     const size_t lds_hist = (size_t)(SEL_RADIX + 1) * 32 * 4;
     const size_t lds_stage = (size_t)SEL_STAGE_CAP * (sizeof(T) + 2) + 16;
     double reads = 0.0;

@@ -230,12 +230,10 @@ int ensure_gradients_t(xdemhip_dh_plan* P, double res_x, double res_y) {
     if (P->gradx && P->grad_res_x == res_x && P->grad_res_y == res_y) return XDEMHIP_OK;
     const int64_t n = P->H * P->W;
     if (!P->gradx) {
-        if (hipMalloc(&P->gradx, (size_t)n * sizeof(T)) != hipSuccess || hipMalloc(&P->grady, (size_t)n * sizeof(T)) != hipSuccess) {
-            (void)hipGetLastError();
-            if (P->gradx) (void)hipFree(P->gradx);
-            P->gradx = P->grady = nullptr;
-            return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed (LZD gradient planes)");
-        }
+        P->mem.optional();   // (both planes or neither: a plan without them can be asked again)
+        P->gradx = P->mem.take((size_t)n * sizeof(T), "LZD gradient planes");
+        P->grady = P->mem.take((size_t)n * sizeof(T), "LZD gradient planes");
+        if (!P->mem.all_or_none(P->gradx, P->grady)) return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed (LZD gradient planes)");
     }
     hipLaunchKernelGGL((lzd_gradient_kernel<T>), dim3(grid_for(ctx, n, 256, 16)), dim3(256), 0, ctx->stream, static_cast<const T*>(P->ref), P->H, P->W,
                        (T)res_x, (T)res_y, static_cast<T*>(P->gradx), static_cast<T*>(P->grady));
@@ -339,7 +337,7 @@ int xdemhip_dh_lzd_normal(xdemhip_dh_plan* P, const double* transform6, const do
     { const int rc_ = ensure_gradients(P, transform6); if (rc_) return rc_; }
     const int nb = fixed_sums_grid(ctx, P->drawn ? (P->n_idx + 255) / 256 : P->n_tiles);
     const int NT = LZD_NS + 1;
-    { const int rc_ = P->sums.reserve(ctx, NT, "xdemhip_dh_lzd_normal"); if (rc_) return rc_; }
+    { const int rc_ = P->sums.reserve(P->mem, NT, "xdemhip_dh_lzd_normal"); if (rc_) return rc_; }
     const NkGeom g = lzd_geom(P);
     const Rigid R = make_rigid(transform6, matrix16, centroid3);
     (void)hipEventRecord(ctx->ev_start, ctx->stream);

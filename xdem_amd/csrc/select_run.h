@@ -488,39 +488,34 @@ constexpr int64_t SEL_BRACKET_MIN_N = (int64_t)1 << 22;
 // ~7000 sampled elements per bin more than 40 % of the data would be candidates and the plain passes are the better route.
 constexpr int64_t SEL_BRACKET_MIN_PER_BIN = 460000;
 
-inline void sel_ws_free(SelWorkspace& w) {
-    void* b[] = {w.s_vals, w.s_bins, w.c_vals, w.c_bins, w.d_small};
-    for (void* p : b)
-        if (p) (void)hipFree(p);
+// The workspace's memory comes from the owner of whoever holds it (`mem`), all five buffers or none: a caller may go on with the
+// plain selection after XDEMHIP_ENOMEM (nothing is left allocated, no stale error for its launch checks, mem.rc clear).
+inline void sel_ws_free(XdOwned& mem, SelWorkspace& w) {
+    const void* b[] = {w.s_vals, w.s_bins, w.c_vals, w.c_bins, w.d_small};
+    for (const void* p : b) mem.drop(p);
     w = SelWorkspace();
 }
-inline int sel_ws_create(xdemhip_ctx* ctx, int64_t n, size_t es, int nb_max, SelWorkspace& w) {
+inline int sel_ws_create(XdOwned& mem, int64_t n, size_t es, int nb_max, SelWorkspace& w) {
     w = SelWorkspace();
     w.es = es; w.nb_max = nb_max;
     w.s_cap = n / 24 + 4096;   // expected n / 64
     w.c_cap = n / 2 + 4096;
-    if (hipMalloc(&w.s_vals, (size_t)w.s_cap * es) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&w.s_bins), (size_t)w.s_cap * 2) != hipSuccess ||
-        hipMalloc(&w.c_vals, (size_t)w.c_cap * es) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&w.c_bins), (size_t)w.c_cap * 2) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&w.d_small), (size_t)(8 + 6 * nb_max) * 8) != hipSuccess) {
-        (void)hipGetLastError();   // (callers may go on with the plain selection: no stale error for their launch checks)
-        sel_ws_free(w);
-        return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc(selection workspace) failed");
-    }
-    return XDEMHIP_OK;
+    mem.optional();
+    w.s_vals = mem.take((size_t)w.s_cap * es, "selection workspace");
+    w.s_bins = mem.take<uint16_t>((size_t)w.s_cap, "selection workspace");
+    w.c_vals = mem.take((size_t)w.c_cap * es, "selection workspace");
+    w.c_bins = mem.take<uint16_t>((size_t)w.c_cap, "selection workspace");
+    w.d_small = mem.take<uint64_t>((size_t)(8 + 6 * nb_max), "selection workspace");
+    if (mem.all_or_none(w.s_vals, w.s_bins, w.c_vals, w.c_bins, w.d_small)) return XDEMHIP_OK;
+    w = SelWorkspace();
+    return xd_fail(mem.ctx, XDEMHIP_ENOMEM, "hipMalloc failed (selection workspace)");
 }
 // A workspace for the length of one call: on every return path the queued work that uses it is waited for and it is freed.  (Plans
-// keep a plain SelWorkspace and free it in their destroy.)
+// keep a plain SelWorkspace that their own owner frees.)
 struct SelWorkspaceLocal {
-    xdemhip_ctx* ctx;
+    XdOwned mem;
     SelWorkspace ws;
-    explicit SelWorkspaceLocal(xdemhip_ctx* c) : ctx(c) {}
-    ~SelWorkspaceLocal() {
-        if (!ws.d_small) return;
-        (void)hipStreamSynchronize(ctx->stream);
-        sel_ws_free(ws);
-    }
-    SelWorkspaceLocal(const SelWorkspaceLocal&) = delete;
-    SelWorkspaceLocal& operator=(const SelWorkspaceLocal&) = delete;
+    explicit SelWorkspaceLocal(xdemhip_ctx* c) : mem(c) {}
 };
 
 // Stratified 1/64 sample of SEL_LINE-element lines: group g covers lines [64 g, 64 g + 64) and contributes the one line picked

@@ -901,8 +901,8 @@ using namespace xd;
 struct xdemhip_pairs {
     xdemhip_ctx* ctx = nullptr;
     int val_dtype = XDEMHIP_F32, nblk = 0, nb = 0, pdist = 0;
-    bool own = false;
-    double *ax = nullptr, *ay = nullptr, *bx = nullptr, *by = nullptr;
+    XdOwned mem;   // every device buffer of the set but the caller's own device arrays
+    double *ax = nullptr, *ay = nullptr, *bx = nullptr, *by = nullptr;   // the caller's device arrays, or owned copies of its host arrays
     void *av = nullptr, *bv = nullptr;
     int64_t *a_off = nullptr, *b_off = nullptr, *wg_off = nullptr, *wg_off_big = nullptr;
     double *thr = nullptr, *sums = nullptr;
@@ -1190,22 +1190,7 @@ bool make_grid(const double* ax, const double* ay, int64_t na, const double* bx,
 
 extern "C" {
 
-void xdemhip_pairs_destroy(xdemhip_pairs* P) {
-    if (!P) return;
-    (void)hipSetDevice(P->ctx->device);
-    if (P->own) {
-        void* b[] = {P->ax, P->ay, P->bx, P->by, P->av, P->bv};
-        for (void* p : b) if (p) (void)hipFree(p);
-    }
-    void* b2[] = {P->a_off, P->b_off, P->wg_off, P->wg_off_big, P->thr, P->sums, P->counts, P->hist, P->hist2, P->prefix, P->succ, P->lut,
-                  P->a_xy, P->b_xy, P->thr_i, P->lut_i};
-    for (void* p : b2) if (p) (void)hipFree(p);
-    if (P->cand_v) (void)hipFree(P->cand_v);   // candidate buffers of the bracketed selection (kept between calls)
-    if (P->cand_b) (void)hipFree(P->cand_b);
-    if (P->sel_small) (void)hipFree(P->sel_small);
-    if (P->sel_scratch) (void)hipFree(P->sel_scratch);
-    delete P;
-}
+void xdemhip_pairs_destroy(xdemhip_pairs* P) { delete P; }   // (its owner frees the device buffers)
 
 int xdemhip_pairs_create(xdemhip_ctx* ctx, int n_blocks, const int64_t* a_off, const double* ax, const double* ay, const void* av,
                          const int64_t* b_off, const double* bx, const double* by, const void* bv, int val_dtype,
@@ -1235,7 +1220,7 @@ int xdemhip_pairs_create(xdemhip_ctx* ctx, int n_blocks, const int64_t* a_off, c
         val_dtype = XDEMHIP_F64;
     }
     xdemhip_pairs* P = new xdemhip_pairs();
-    P->ctx = ctx; P->val_dtype = val_dtype; P->nblk = n_blocks; P->nb = n_bins; P->pdist = pd;
+    P->ctx = P->mem.ctx = ctx; P->val_dtype = val_dtype; P->nblk = n_blocks; P->nb = n_bins; P->pdist = pd;
     const size_t es = val_dtype == XDEMHIP_F32 ? 4 : 8;
     const int64_t na = a_off[n_blocks], nbt = pd ? 0 : b_off[n_blocks];
     std::vector<int64_t> wg(n_blocks + 1, 0), wgb(n_blocks + 1, 0);
@@ -1278,28 +1263,31 @@ int xdemhip_pairs_create(xdemhip_ctx* ctx, int n_blocks, const int64_t* a_off, c
         if (!(thr[0] > cell_lo(0))) lut_ok = false;
     }
     P->lut_emin = emin;
-    auto fail = [&](int code, const char* m) { xdemhip_pairs_destroy(P); return xd_fail(ctx, code, m); };
-#define XD_ALLOC(ptr, bytes) if (hipMalloc(reinterpret_cast<void**>(&(ptr)), (bytes) ? (bytes) : 8) != hipSuccess) return fail(XDEMHIP_ENOMEM, "hipMalloc failed")
-    XD_ALLOC(P->a_off, sizeof(int64_t) * (n_blocks + 1));
-    XD_ALLOC(P->wg_off, sizeof(int64_t) * (n_blocks + 1));
-    XD_ALLOC(P->wg_off_big, sizeof(int64_t) * (n_blocks + 1));
-    XD_ALLOC(P->thr, sizeof(double) * n_bins);
-    XD_ALLOC(P->sums, sizeof(double) * n_bins);
-    XD_ALLOC(P->counts, 8 * n_bins);
-    XD_ALLOC(P->hist, 8 * (size_t)n_bins * SEL_RADIX);
-    XD_ALLOC(P->hist2, 8 * (size_t)n_bins * SEL_RADIX);
-    XD_ALLOC(P->prefix, 8 * n_bins);
-    XD_ALLOC(P->succ, 8 * n_bins);
-    if (!pd) XD_ALLOC(P->b_off, sizeof(int64_t) * (n_blocks + 1));
-    (void)hipMemcpyAsync(P->a_off, a_off, sizeof(int64_t) * (n_blocks + 1), hipMemcpyHostToDevice, ctx->stream);
-    (void)hipMemcpyAsync(P->wg_off, wg.data(), sizeof(int64_t) * (n_blocks + 1), hipMemcpyHostToDevice, ctx->stream);
-    (void)hipMemcpyAsync(P->wg_off_big, wgb.data(), sizeof(int64_t) * (n_blocks + 1), hipMemcpyHostToDevice, ctx->stream);
-    (void)hipMemcpyAsync(P->thr, thr.data(), sizeof(double) * n_bins, hipMemcpyHostToDevice, ctx->stream);
-    if (lut_ok) {
-        XD_ALLOC(P->lut, LUT_N);
-        (void)hipMemcpyAsync(P->lut, lut.data(), LUT_N, hipMemcpyHostToDevice, ctx->stream);
+    // (every host array read below outlives the synchronisation that ends the uploads)
+    const char* who = "xdemhip_pairs_create";
+    const size_t offs = sizeof(int64_t) * (size_t)(n_blocks + 1), nbin = (size_t)n_bins;
+    XdOwned& mem = P->mem;
+    GridInfo gi;
+    P->a_off = mem.keep(a_off, offs, XDEMHIP_HOST, who);
+    P->wg_off = mem.keep(wg.data(), offs, XDEMHIP_HOST, who);
+    P->wg_off_big = mem.keep(wgb.data(), offs, XDEMHIP_HOST, who);
+    P->thr = mem.keep(thr.data(), 8 * nbin, XDEMHIP_HOST, who);
+    P->sums = mem.take<double>(nbin, who);
+    P->counts = mem.take<unsigned long long>(nbin, who);
+    P->hist = mem.take<unsigned long long>(nbin * SEL_RADIX, who);
+    P->hist2 = mem.take<unsigned long long>(nbin * SEL_RADIX, who);
+    P->prefix = mem.take(8 * nbin, who);
+    P->succ = mem.take(8 * nbin, who);
+    P->b_off = mem.keep(b_off, offs, XDEMHIP_HOST, who);   // (null for a pdist set)
+    if (lut_ok) P->lut = mem.keep(lut.data(), LUT_N, XDEMHIP_HOST, who);
+    P->ax = mem.keep(ax, 8 * (size_t)na, memspace, who);
+    P->ay = mem.keep(ay, 8 * (size_t)na, memspace, who);
+    P->av = mem.keep(av, es * (size_t)na, memspace, who);
+    if (!pd || memspace == XDEMHIP_DEVICE) {
+        P->bx = mem.keep(bx, 8 * (size_t)nbt, memspace, who);
+        P->by = mem.keep(by, 8 * (size_t)nbt, memspace, who);
+        P->bv = mem.keep(bv, es * (size_t)nbt, memspace, who);
     }
-    if (!pd) (void)hipMemcpyAsync(P->b_off, b_off, sizeof(int64_t) * (n_blocks + 1), hipMemcpyHostToDevice, ctx->stream);
     if (memspace == XDEMHIP_HOST) {
         // NaN values never pair (the kernel tests for them); knowing that there are none lets full tiles skip the test
         auto any_nan = [&](const void* v, int64_t n) {
@@ -1308,39 +1296,19 @@ int xdemhip_pairs_create(xdemhip_ctx* ctx, int n_blocks, const int64_t* a_off, c
             return false;
         };
         P->has_nan = (any_nan(av, na) || (!pd && any_nan(bv, nbt))) ? 1 : 0;
-        P->own = true;
-        XD_ALLOC(P->ax, 8 * na); XD_ALLOC(P->ay, 8 * na); XD_ALLOC(P->av, es * na);
-        (void)hipMemcpyAsync(P->ax, ax, 8 * na, hipMemcpyHostToDevice, ctx->stream);
-        (void)hipMemcpyAsync(P->ay, ay, 8 * na, hipMemcpyHostToDevice, ctx->stream);
-        (void)hipMemcpyAsync(P->av, av, es * na, hipMemcpyHostToDevice, ctx->stream);
-        if (!pd) {
-            XD_ALLOC(P->bx, 8 * nbt); XD_ALLOC(P->by, 8 * nbt); XD_ALLOC(P->bv, es * nbt);
-            (void)hipMemcpyAsync(P->bx, bx, 8 * nbt, hipMemcpyHostToDevice, ctx->stream);
-            (void)hipMemcpyAsync(P->by, by, 8 * nbt, hipMemcpyHostToDevice, ctx->stream);
-            (void)hipMemcpyAsync(P->bv, bv, es * nbt, hipMemcpyHostToDevice, ctx->stream);
-        }
         // raster-sampled points (the reference's samplers draw pixels): integer-lattice kernels
-        GridInfo gi;
         if (lut_ok && ctx->vario_grid != 0 && make_grid(ax, ay, na, pd ? nullptr : bx, pd ? nullptr : by, nbt, thr, gi)) {
-            XD_ALLOC(P->a_xy, 4 * na);
-            XD_ALLOC(P->thr_i, 4 * n_bins);
-            XD_ALLOC(P->lut_i, LUT_G);
-            XD_HIP_CHECK(ctx, hipMemcpy(P->a_xy, gi.a_xy.data(), 4 * (size_t)na, hipMemcpyHostToDevice));
-            XD_HIP_CHECK(ctx, hipMemcpy(P->thr_i, gi.thr_i.data(), 4 * (size_t)n_bins, hipMemcpyHostToDevice));
-            XD_HIP_CHECK(ctx, hipMemcpy(P->lut_i, gi.lut.data(), LUT_G, hipMemcpyHostToDevice));
-            if (!pd) {
-                XD_ALLOC(P->b_xy, 4 * nbt);
-                XD_HIP_CHECK(ctx, hipMemcpy(P->b_xy, gi.b_xy.data(), 4 * (size_t)nbt, hipMemcpyHostToDevice));
-            }
+            P->a_xy = mem.keep(gi.a_xy.data(), 4 * (size_t)na, XDEMHIP_HOST, who);
+            P->thr_i = mem.keep(gi.thr_i.data(), 4 * nbin, XDEMHIP_HOST, who);
+            P->lut_i = mem.keep(gi.lut.data(), LUT_G, XDEMHIP_HOST, who);
+            if (!pd) P->b_xy = mem.keep(gi.b_xy.data(), 4 * (size_t)nbt, XDEMHIP_HOST, who);
             P->lut_i_emin = gi.emin;
             P->grid = true;
         }
-    } else {
-        P->ax = const_cast<double*>(ax); P->ay = const_cast<double*>(ay); P->av = const_cast<void*>(av);
-        P->bx = const_cast<double*>(bx); P->by = const_cast<double*>(by); P->bv = const_cast<void*>(bv);
     }
-#undef XD_ALLOC
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess) return fail(XDEMHIP_EHIP, "upload failed");
+    int rc = mem.rc;
+    if (rc == XDEMHIP_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = xd_fail(ctx, XDEMHIP_EHIP, "upload failed");
+    if (rc) { delete P; return rc; }
     if (n_pairs) *n_pairs = pairs;
     *out = P;
     return XDEMHIP_OK;
@@ -1586,10 +1554,8 @@ int pairs_medians_typed(xdemhip_pairs* P, int64_t* counts, double* medians, bool
                  off_cnt = off_given + 8 * (size_t)nb, off_ctr = off_cnt + 24 * (size_t)nb, off_rbs = off_ctr + 16, off_pref2 = off_rbs + 8,
                  small_bytes = off_pref2 + 8 * (size_t)nb;
     if (P->sel_small_bytes < small_bytes) {
-        if (P->sel_small) (void)hipFree(P->sel_small);
-        P->sel_small = nullptr; P->sel_small_bytes = 0;
-        if (hipMalloc(reinterpret_cast<void**>(&P->sel_small), small_bytes) != hipSuccess) return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed");
-        P->sel_small_bytes = small_bytes;
+        P->sel_small_bytes = P->mem.regrow(P->sel_small, small_bytes, "xdemhip_pairs_medians") ? small_bytes : 0;
+        { const int rc_ = P->mem.status(); if (rc_) return rc_; }
     }
     d_small = P->sel_small;
     SelState<K>* d_st = reinterpret_cast<SelState<K>*>(d_small);
@@ -1607,10 +1573,11 @@ int pairs_medians_typed(xdemhip_pairs* P, int64_t* counts, double* medians, bool
     if (bracket) {
         const size_t need = scratch_size(nb);
         if (P->sel_scratch_bytes < need) {
-            if (P->sel_scratch) (void)hipFree(P->sel_scratch);
-            P->sel_scratch = nullptr; P->sel_scratch_bytes = 0;
-            if (hipMalloc(&P->sel_scratch, need) == hipSuccess) P->sel_scratch_bytes = need;
-            else { (void)hipGetLastError(); bracket = false; }
+            P->mem.drop(P->sel_scratch);
+            P->mem.optional();   // (too little memory: plain passes)
+            P->sel_scratch = P->mem.take(need, "xdemhip_pairs_medians");
+            bracket = P->mem.all_or_none(P->sel_scratch);
+            P->sel_scratch_bytes = bracket ? need : 0;
         }
         scratch = P->sel_scratch;
     }
@@ -1659,24 +1626,21 @@ int pairs_medians_typed(xdemhip_pairs* P, int64_t* counts, double* medians, bool
                 const long long need = (long long)(want < most ? want : most);
                 uint64_t got = 1;
                 if (P->cand_cap < need) {
-                    if (P->cand_v) (void)hipFree(P->cand_v);
-                    if (P->cand_b) (void)hipFree(P->cand_b);
-                    P->cand_v = nullptr; P->cand_b = nullptr; P->cand_cap = 0;
-                    if (hipMalloc(&P->cand_v, (size_t)need * sizeof(TC)) != hipSuccess ||
-                        hipMalloc(reinterpret_cast<void**>(&P->cand_b), (size_t)need * 2) != hipSuccess) {
-                        (void)hipGetLastError();
-                        got = 0;
-                    } else {
-                        P->cand_cap = need;
-                    }
+                    P->mem.drop(P->cand_v);
+                    P->mem.drop(P->cand_b);
+                    P->mem.optional();
+                    P->cand_v = P->mem.take((size_t)need * sizeof(TC), "xdemhip_pairs_medians");
+                    P->cand_b = P->mem.take<uint16_t>((size_t)need, "xdemhip_pairs_medians");
+                    got = P->mem.all_or_none(P->cand_v, P->cand_b) ? 1 : 0;
+                    P->cand_cap = got ? need : 0;
                 }
                 if (ctx->allreduce && ctx->allreduce(&got, 1, XDEMHIP_RED_MIN_U64, ctx->allreduce_user) != 0) {
                     cleanup();
                     return xd_fail(ctx, XDEMHIP_EHIP, "all-reduce hook failed");
                 }
-                if (!got) {
-                    if (P->cand_v) (void)hipFree(P->cand_v);
-                    if (P->cand_b) (void)hipFree(P->cand_b);
+                if (!got) {   // (another rank's shortage: this rank's buffers go too)
+                    P->mem.drop(P->cand_v);
+                    P->mem.drop(P->cand_b);
                     P->cand_v = nullptr; P->cand_b = nullptr; P->cand_cap = 0;
                     bracket = false;
                 }

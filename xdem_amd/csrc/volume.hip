@@ -30,8 +30,8 @@ struct xdemhip_hypso {
     xdemhip_ctx* ctx = nullptr;
     int t_f32 = 1, r_f32 = 1;
     int64_t n = 0, L = 2;   // L: size of the label tables (2^20 with labels, 2 without: "label 1")
-    void *ddem = nullptr, *ref = nullptr, *labels = nullptr, *mask = nullptr;
-    bool own_ddem = false, own_ref = false, own_labels = false, own_mask = false;
+    XdOwned mem;            // every device buffer of the plan but the caller's own device arrays
+    void *ddem = nullptr, *ref = nullptr, *labels = nullptr, *mask = nullptr;   // the caller's device arrays, or owned copies of its host arrays
     int32_t* rank_of = nullptr;   // [L] rank of a kept label, -1 otherwise (rebuilt by every call that takes a list of labels)
     int32_t* grp = nullptr;       // [n] group of every pixel in the last xdemhip_hypso_segments call, -1: in none
     bool grouped = false;
@@ -321,35 +321,22 @@ int xdemhip_hypso_create(xdemhip_ctx* ctx, const void* ddem, int ddem_dtype, con
     if (n < 1 || n >= ((int64_t)1 << 32)) return xd_fail(ctx, XDEMHIP_EINVAL, "xdemhip_hypso_create: 1 to 2^32 - 1 pixels");
     XD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     xdemhip_hypso* P = new xdemhip_hypso;
-    P->ctx = ctx; P->n = n;
+    P->ctx = P->mem.ctx = ctx; P->n = n;
     P->t_f32 = ddem_dtype == XDEMHIP_F32; P->r_f32 = ref_dtype == XDEMHIP_F32;
     P->L = labels ? HYP_LABEL_LIMIT : 2;
-    int rc = xd_upload_keep(ctx, ddem, (size_t)n * (P->t_f32 ? 4 : 8), memspace, &P->ddem, &P->own_ddem);
-    if (rc == XDEMHIP_OK) rc = xd_upload_keep(ctx, ref, (size_t)n * (P->r_f32 ? 4 : 8), memspace, &P->ref, &P->own_ref);
-    if (rc == XDEMHIP_OK && labels) rc = xd_upload_keep(ctx, labels, (size_t)n * 4, memspace, &P->labels, &P->own_labels);
-    if (rc == XDEMHIP_OK && mask) rc = xd_upload_keep(ctx, mask, (size_t)n, memspace, &P->mask, &P->own_mask);
-    if (rc == XDEMHIP_OK && hipMalloc(reinterpret_cast<void**>(&P->rank_of), (size_t)P->L * 4) != hipSuccess) {
-        (void)hipGetLastError();
-        rc = xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed (xdemhip_hypso_create)");
-    }
+    P->ddem = P->mem.keep(ddem, (size_t)n * (P->t_f32 ? 4 : 8), memspace, "xdemhip_hypso_create");
+    P->ref = P->mem.keep(ref, (size_t)n * (P->r_f32 ? 4 : 8), memspace, "xdemhip_hypso_create");
+    P->labels = P->mem.keep(labels, (size_t)n * 4, memspace, "xdemhip_hypso_create");
+    P->mask = P->mem.keep(mask, (size_t)n, memspace, "xdemhip_hypso_create");
+    P->rank_of = P->mem.take<int32_t>((size_t)P->L, "xdemhip_hypso_create");
+    int rc = P->mem.rc;
     if (rc == XDEMHIP_OK) rc = xd_sync(ctx);   // (the caller's host arrays may go once this returns)
     if (rc) { xdemhip_hypso_destroy(P); return rc; }
     *out = P;
     return XDEMHIP_OK;
 }
 
-void xdemhip_hypso_destroy(xdemhip_hypso* P) {
-    if (!P) return;
-    (void)hipSetDevice(P->ctx->device);
-    (void)hipStreamSynchronize(P->ctx->stream);
-    if (P->own_ddem && P->ddem) (void)hipFree(P->ddem);
-    if (P->own_ref && P->ref) (void)hipFree(P->ref);
-    if (P->own_labels && P->labels) (void)hipFree(P->labels);
-    if (P->own_mask && P->mask) (void)hipFree(P->mask);
-    if (P->rank_of) (void)hipFree(P->rank_of);
-    if (P->grp) (void)hipFree(P->grp);
-    delete P;
-}
+void xdemhip_hypso_destroy(xdemhip_hypso* P) { delete P; }   // (its owner frees the device buffers)
 
 int xdemhip_hypso_label_stats(xdemhip_hypso* P, int64_t cap, int32_t* ids, int64_t* counts, double* extremes, int64_t* n_found,
                               int64_t* n_bad_labels, int64_t* n_ref_invalid) {
@@ -405,11 +392,8 @@ int xdemhip_hypso_segments(xdemhip_hypso* P, int n_kept, const int32_t* ids, int
     const int64_t n = P->n;
     const int n_groups = n_kept * nb;
     P->grouped = false;
-    if (!P->grp && hipMalloc(reinterpret_cast<void**>(&P->grp), (size_t)n * 4) != hipSuccess) {
-        (void)hipGetLastError();
-        P->grp = nullptr;
-        return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc failed (xdemhip_hypso_segments)");
-    }
+    if (!P->grp) P->grp = P->mem.take<int32_t>((size_t)n, "xdemhip_hypso_segments");
+    { const int rc_ = P->mem.status(); if (rc_) return rc_; }
     const size_t es = P->t_f32 ? 4 : 8;
     unsigned long long total = 0;   // (a copy's destination: declared before the buffers)
     XdBuffers buf(ctx, "xdemhip_hypso_segments");
