@@ -30,7 +30,7 @@ def main() -> None:
     a = ap.parse_args()
     import torch
 
-    from xdem_amd import _lib, coreg, rigid
+    from xdem_amd import _args, _lib, coreg, rigid
 
     ctx = _lib.default_context()
     N = a.n
@@ -62,8 +62,8 @@ def main() -> None:
     for i in range(a.reps + 1):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        ctx.check(ctx._L.xdemhip_apply_matrix_rst(ctx.handle, tba.data_ptr(), _lib.F32, N, N, rigid._c6(t6), rigid._c6(m.ravel()),
-                                                  rigid._c6(cen), res.data_ptr(), _lib.DEVICE))
+        ctx.check(ctx._L.xdemhip_apply_matrix_rst(ctx.handle, tba.data_ptr(), _lib.F32, N, N, _args.c_doubles(t6), _args.c_doubles(m.ravel()),
+                                                  _args.c_doubles(cen), res.data_ptr(), _lib.DEVICE))
         ctx.synchronize()
         ms.append((time.perf_counter() - t0) * 1e3)
     out["regrid_ms"] = round(float(np.median(ms[1:])), 3)

@@ -1,17 +1,20 @@
 """What ``xdem_amd.coreg`` (NuthKaab) and ``xdem_amd.biascorr`` (Deramp, VerticalShift) share: the random subsample of the valid
-pixels, the raster-pair front of their device plans, the plans' lifetime, ``apply_translation``, and the steps' common base with the
-pipeline they form (``xdem.coreg.CoregPipeline``, base.py:2008-2019, 2880-3190).  Both modules re-export what their users import."""
+pixels, ``apply_translation``, and the steps' common base with the pipeline they form (``xdem.coreg.CoregPipeline``, base.py:2008-2019,
+2880-3190).  The raster-pair front of their device plans (``_args.raster_pair``) and the plans' lifetime (``_lib._Plan``) are
+re-exported here.  Both modules re-export what their users import."""
 from __future__ import annotations
 
 import copy as _copy
 import inspect
 import logging
 import warnings
-from typing import Any, NamedTuple
+from typing import Any
 
 import numpy as np
 
-from . import _lib
+from . import _args, _lib
+from ._args import RasterPair, raster_pair  # noqa: F401  (the plans' front; imported from here by the modules that build plans)
+from ._lib import _Plan  # noqa: F401  (and their lifetime)
 
 NO_VALID = ("There is no valid points common to the input and auxiliary data (bias variables, or "
             "derivatives required for this method, for example slope, aspect, etc).")
@@ -61,73 +64,6 @@ def draw(plan, subsample, random_state) -> int:
     return plan.subsample(ranks)
 
 
-# ---- the device plans' front and lifetime -------------------------------------------------------------------------------------------
-class RasterPair(NamedTuple):
-    ref: int                 # pointers for the library's create call
-    tba: int
-    inlier: int | None
-    dtype: np.dtype
-    code: int                # _lib.F32 / _lib.F64
-    shape: tuple
-    memspace: int            # _lib.HOST / _lib.DEVICE
-    keep: tuple              # the arrays the pointers point into: alive at least until the create call returns
-
-
-def raster_pair(ref, tba, inlier_mask) -> RasterPair:
-    """Two rasters on one grid and an optional inlier mask, as a plan's create call takes them.  ``ref`` / ``tba``: 2-D arrays
-    (promoted to float64 if either is float64, else to float32, when their dtypes differ or are not float), or contiguous 2-D float32 /
-    float64 CUDA tensors of one dtype, never copied (the plan keeps them alive; the current torch stream is synchronised).  The mask
-    goes as uint8: next to device rasters a host mask is uploaded and a device mask converted, on the rasters' device."""
-    if hasattr(ref, "is_cuda"):
-        import torch
-
-        if not (ref.is_cuda and tba.is_cuda and ref.is_contiguous() and tba.is_contiguous() and ref.dtype == tba.dtype
-                and ref.shape == tba.shape and ref.dim() == 2 and ref.dtype in (torch.float32, torch.float64)):
-            raise ValueError("device inputs must be contiguous 2D float32 / float64 CUDA tensors of the same shape and dtype")
-        inl = None
-        if inlier_mask is not None:
-            inl = inlier_mask if hasattr(inlier_mask, "is_cuda") else torch.from_numpy(np.ascontiguousarray(inlier_mask, dtype=np.uint8))
-            inl = inl.to(device=ref.device, dtype=torch.uint8).contiguous()
-        torch.cuda.current_stream(ref.device).synchronize()
-        dtype = np.dtype(np.float32 if ref.dtype == torch.float32 else np.float64)
-        return RasterPair(ref.data_ptr(), tba.data_ptr(), inl.data_ptr() if inl is not None else None, dtype,
-                          _lib.F32 if dtype == np.float32 else _lib.F64, tuple(ref.shape), _lib.DEVICE, (ref, tba, inl))
-    ref, tba = np.ascontiguousarray(ref), np.ascontiguousarray(tba)
-    if ref.shape != tba.shape or ref.ndim != 2:
-        raise ValueError("ref and tba must be 2D arrays of the same shape")
-    if ref.dtype != tba.dtype or ref.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
-        dt = np.float64 if np.float64 in (ref.dtype, tba.dtype) else np.float32
-        ref, tba = ref.astype(dt), tba.astype(dt)
-    inl = None if inlier_mask is None else np.ascontiguousarray(inlier_mask, dtype=np.uint8)
-    return RasterPair(ref.ctypes.data, tba.ctypes.data, inl.ctypes.data if inl is not None else None, ref.dtype,
-                      _lib.F32 if ref.dtype == np.float32 else _lib.F64, ref.shape, _lib.HOST, (ref, tba, inl))
-
-
-class _Plan:
-    """Lifetime of a device plan: ``close`` (also on leaving a ``with`` block, and at collection) calls the library's ``_DESTROY``."""
-
-    _DESTROY = ""
-
-    def close(self) -> None:
-        if getattr(self, "handle", None):
-            if getattr(self.ctx, "handle", None):   # (a context that is already gone took its plans with it)
-                getattr(self.ctx._L, self._DESTROY)(self.handle)
-            self.handle = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def __del__(self):  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
 def apply_translation(elev: np.ndarray, shift_x: float, shift_y: float, shift_z: float, resolution, resample: bool = True,
                       ctx: _lib.Context | None = None) -> np.ndarray:
     """Apply a pure translation to a DEM array (``Coreg.apply`` for ``shift_x / shift_y / shift_z``): with
@@ -135,9 +71,7 @@ def apply_translation(elev: np.ndarray, shift_x: float, shift_y: float, shift_z:
     (``_apply_matrix_rst`` case 2 + ``_reproject_horizontal_shift_samecrs``, xdem/coreg/base.py:1522-1570, 1615-1655):
     ``out(r, c) = elev(r + shift_y / res_y, c - shift_x / res_x) + shift_z``.  Without resampling only ``shift_z`` is
     added (the reference then just moves the geotransform)."""
-    arr = np.ascontiguousarray(elev.filled(np.nan) if isinstance(elev, np.ma.MaskedArray) else elev)
-    if arr.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
-        arr = arr.astype(np.float32)
+    arr = _args.host_float(elev)
     from .spatialstats import _count_finite   # (np.isfinite over the raster on the library's host threads: 7 ms against 0.1 s at 20000^2)
 
     if _count_finite(arr)[0] == 0:
@@ -147,9 +81,8 @@ def apply_translation(elev: np.ndarray, shift_x: float, shift_y: float, shift_z:
     res = (float(resolution), float(resolution)) if np.isscalar(resolution) else (float(resolution[0]), float(resolution[1]))
     ctx = ctx or _lib.default_context()
     out = np.empty_like(arr)
-    ctx.check(ctx._L.xdemhip_shift_bilinear(ctx.handle, arr.ctypes.data, _lib.F32 if arr.dtype == np.float32 else _lib.F64,
-                                            arr.shape[0], arr.shape[1], float(shift_y) / res[1], -float(shift_x) / res[0],
-                                            float(shift_z), out.ctypes.data, _lib.HOST))
+    ctx.check(ctx._L.xdemhip_shift_bilinear(ctx.handle, _args.ptr(arr), _args.code(arr), arr.shape[0], arr.shape[1], float(shift_y) / res[1],
+                                            -float(shift_x) / res[0], float(shift_z), _args.ptr(out), _lib.HOST))
     return out
 
 

@@ -161,7 +161,6 @@ def lib() -> ctypes.CDLL:
                                        ctypes.c_void_p, ctypes.c_int]
         L.xdemhip_shift_bilinear.argtypes = [c_ctx, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_double,
                                              ctypes.c_double, ctypes.c_double, ctypes.c_void_p, ctypes.c_int]
-        L.xdemhip_set_allreduce.argtypes = [c_ctx, ctypes.c_void_p, ctypes.c_void_p]
         L.xdemhip_nk_set_rows.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, c_i64p]
         L.xdemhip_nk_set_statistic.argtypes = [ctypes.c_void_p, ctypes.c_int]
         L.xdemhip_nk_route_counts.argtypes = [ctypes.c_void_p, c_i64p, c_i64p]
@@ -480,9 +479,7 @@ class Context:
         self._hook = CB(hook)  # keep alive
         self.check(self._L.xdemhip_set_allreduce(self.handle, ctypes.cast(self._hook, ctypes.c_void_p), None))
         if device_side is None:
-            import torch.distributed as dist
-
-            device_side = dist.get_backend(None if group == "world" else group) == "nccl"
+            device_side = dist.get_backend(pg) == "nccl"
         if device_side:
             CBD = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p)
             self._dev_hook = CBD(make_device_reduce_hook(group, self.device))
@@ -566,7 +563,7 @@ class Context:
                                "vario_grid", "vario_runs", "vario_sort", "hypso_seg_lds", "pts_tile_order", "bw_seg_lds", "vec_seg_reg", "vec_seg_lds", "vec_stage_times"))
 
     def set_option(self, name: str, value: int) -> None:
-        """Option of the library (``xdemhip_set_option``: the fourteen names of include/xdemhip.h), e.g. ``("selection", 1)`` -- or,
+        """Option of the library (``xdemhip_set_option``: the names listed in include/xdemhip.h), e.g. ``("selection", 1)`` -- or,
         for the names of include/xdemhip_test.h, a test switch between internal routes (``xdemhip_set_test_switch``)."""
         fn = self._L.xdemhip_set_test_switch if name in self.TEST_SWITCHES else self._L.xdemhip_set_option
         self.check(fn(self.handle, name.encode(), int(value)))
@@ -612,6 +609,32 @@ class Context:
             self.handle = None
 
     def __del__(self) -> None:  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _Plan:
+    """Lifetime of an object that holds a library handle made on a context (``self.ctx``, ``self.handle``, adopted by the context):
+    ``close`` -- also on leaving a ``with`` block, at collection and when the context closes -- calls the library's ``_DESTROY`` once."""
+
+    _DESTROY = ""
+
+    def close(self) -> None:
+        if getattr(self, "handle", None):
+            if getattr(self.ctx, "handle", None):   # (a context that is already gone took its plans with it)
+                getattr(self.ctx._L, self._DESTROY)(self.handle)
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):  # pragma: no cover
         try:
             self.close()
         except Exception:

@@ -28,7 +28,9 @@ from typing import Any, Callable
 import numpy as np
 import scipy.optimize
 
-from . import _lib
+from . import _args, _lib
+from ._args import nan_filled as _host_array  # noqa: F401  (the name bincorr, rigid and the test helpers know it by)
+from ._args import plane_in_space  # noqa: F401
 from ._coregbase import NO_VALID, CoregPipeline, _Plan, _Step, _with_transform, apply_translation, draw, raster_pair  # noqa: F401
 
 MAX_DEVICE_ORDER = 5
@@ -45,36 +47,6 @@ def polynomial_2d(xx, *params):
     return np.polynomial.polynomial.polyval2d(xx[0], xx[1], c)
 
 
-def _host_array(a):
-    if a is None:
-        return None
-    return np.asarray(a.filled(np.nan) if isinstance(a, np.ma.MaskedArray) else a)
-
-
-def plane_in_space(plane, device):
-    """A float32 / float64 plane where a call reads it: on ``device`` (a torch device: a contiguous CUDA tensor, uploaded or moved
-    if need be, the current stream synchronised) or, with ``device`` None, on the host (a contiguous NumPy array).  Other dtypes
-    become float64.  Returns (pointer, dtype code, shape, the array to keep alive)."""
-    if device is not None:
-        import torch
-
-        if hasattr(plane, "is_cuda"):
-            t = plane
-        else:
-            with warnings.catch_warnings():
-                warnings.simplefilter("ignore", UserWarning)   # (a read-only array is only read)
-                t = torch.from_numpy(np.ascontiguousarray(_host_array(plane)))
-        if t.dtype not in (torch.float32, torch.float64):
-            t = t.to(torch.float64)
-        t = t.to(device).contiguous()
-        torch.cuda.current_stream(t.device).synchronize()
-        return t.data_ptr(), (_lib.F32 if t.dtype == torch.float32 else _lib.F64), tuple(t.shape), t
-    t = np.ascontiguousarray(plane.cpu().numpy() if hasattr(plane, "is_cuda") else _host_array(plane))
-    if t.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
-        t = t.astype(np.float64)
-    return t.ctypes.data, (_lib.F32 if t.dtype == np.float32 else _lib.F64), tuple(t.shape), t
-
-
 # ---- the device plan --------------------------------------------------------------------------------------------------------
 class DhPlan(_Plan):
     """Device-resident elevation difference of two rasters (``xdemhip_dh_plan``): valid mask, optional random subsample, and the
@@ -86,7 +58,7 @@ class DhPlan(_Plan):
     def __init__(self, ref, tba, inlier_mask=None, ctx: _lib.Context | None = None):
         self.handle = None
         self.drawn = False
-        if not hasattr(ref, "is_cuda"):
+        if not _args.is_tensor(ref):
             ref, tba, inlier_mask = _host_array(ref), _host_array(tba), _host_array(inlier_mask)
         p = raster_pair(ref, tba, inlier_mask)   # (checked before a device is asked for: what is no raster pair is refused anywhere)
         if p.memspace == _lib.HOST and p.keep[2] is not None and p.keep[2].shape != p.shape:
@@ -108,7 +80,7 @@ class DhPlan(_Plan):
         formed on the device (``xdemhip_dh_subsample``).  Returns their number."""
         ranks = np.ascontiguousarray(ranks, dtype=np.int64)
         k = ctypes.c_int64()
-        self.ctx.check(self.ctx._L.xdemhip_dh_subsample(self.handle, ranks.ctypes.data, int(ranks.size), _lib.HOST, ctypes.byref(k)))
+        self.ctx.check(self.ctx._L.xdemhip_dh_subsample(self.handle, _args.ptr(ranks), int(ranks.size), _lib.HOST, ctypes.byref(k)))
         self.drawn = True
         self.n_selected = int(k.value)
         return self.n_selected
@@ -122,9 +94,8 @@ class DhPlan(_Plan):
         m = np.empty((2 * order + 1, 2 * order + 1), dtype=np.float64)
         r = np.empty((order + 1, order + 1), dtype=np.float64)
         cnt = ctypes.c_int64()
-        dp = ctypes.POINTER(ctypes.c_double)
-        self.ctx.check(self.ctx._L.xdemhip_dh_poly_moments(self.handle, order, int(row_offset), H_global, W_global, m.ctypes.data_as(dp),
-                                                           r.ctypes.data_as(dp), ctypes.byref(cnt)))
+        self.ctx.check(self.ctx._L.xdemhip_dh_poly_moments(self.handle, order, int(row_offset), H_global, W_global, _args.dp(m), _args.dp(r),
+                                                           ctypes.byref(cnt)))
         return m, r, int(cnt.value)
 
     def median(self) -> tuple[float, int]:
@@ -140,8 +111,7 @@ class DhPlan(_Plan):
         col = np.empty(k, dtype=np.int64) if coords else None
         row = np.empty(k, dtype=np.int64) if coords else None
         cnt = ctypes.c_int64()
-        self.ctx.check(self.ctx._L.xdemhip_dh_values(self.handle, dh.ctypes.data, col.ctypes.data if coords else None,
-                                                     row.ctypes.data if coords else None, _lib.HOST, ctypes.byref(cnt)))
+        self.ctx.check(self.ctx._L.xdemhip_dh_values(self.handle, _args.ptr(dh), _args.ptr(col), _args.ptr(row), _lib.HOST, ctypes.byref(cnt)))
         if int(cnt.value) != k:
             raise _lib.XdemHipError(f"xdemhip_dh_values returned {cnt.value} values, expected {k}")
         return (dh, col, row) if coords else dh
@@ -191,15 +161,13 @@ class DhPlan(_Plan):
             tdt = {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64}
             dh = torch.empty(k, dtype=tdt[np.dtype(self.dtype)], device=dev)
             cols = [torch.empty(k, dtype=tdt[d], device=dev) for d in dts]
-            ptrs, dh_ptr, space = [c.data_ptr() for c in cols], dh.data_ptr(), _lib.DEVICE
         else:
             dh = np.empty(k, dtype=self.dtype)
             cols = [np.empty(k, dtype=d) for d in dts]
-            ptrs, dh_ptr, space = [c.ctypes.data for c in cols], dh.ctypes.data, _lib.HOST
         arr = (_lib.VarSrc * max(n_var, 1))(*sources)
-        outs = (ctypes.c_void_p * max(n_var, 1))(*ptrs)
+        outs = (ctypes.c_void_p * max(n_var, 1))(*[_args.ptr(c) for c in cols])
         cnt = ctypes.c_int64()
-        self.ctx.check(self.ctx._L.xdemhip_dh_var_columns(self.handle, n_var, arr, dh_ptr, outs, space, ctypes.byref(cnt)))
+        self.ctx.check(self.ctx._L.xdemhip_dh_var_columns(self.handle, n_var, arr, _args.ptr(dh), outs, _args.space(dh), ctypes.byref(cnt)))
         if int(cnt.value) != k:
             raise _lib.XdemHipError(f"xdemhip_dh_var_columns returned {cnt.value} values, expected {k}")
         return dh, cols
@@ -222,7 +190,7 @@ class DhPlan(_Plan):
         k = self.n_selected
         dh = np.empty(k, dtype=self.dtype)
         cnt = ctypes.c_int64()
-        self.ctx.check(self.ctx._L.xdemhip_dh_shift_values(self.handle, float(shift_x), float(shift_y), res[0], res[1], dh.ctypes.data,
+        self.ctx.check(self.ctx._L.xdemhip_dh_shift_values(self.handle, float(shift_x), float(shift_y), res[0], res[1], _args.ptr(dh),
                                                            _lib.HOST, ctypes.byref(cnt)))
         if int(cnt.value) != k:
             raise _lib.XdemHipError(f"xdemhip_dh_shift_values returned {cnt.value} values, expected {k}")
@@ -286,32 +254,24 @@ def poly2d_apply(elev, params, row_offset: int = 0, ctx: _lib.Context | None = N
         raise ValueError("The parameters of the 2D polynomial should have a length equal to order^2, see np.polyval2d for more details.")
     if K - 1 > MAX_DEVICE_ORDER:
         raise NotImplementedError(f"poly_order > {MAX_DEVICE_ORDER} is not supported on the device")
-    dp = ctypes.POINTER(ctypes.c_double)
-    if hasattr(elev, "is_cuda"):
+    if _args.is_tensor(elev):
         import torch
 
-        if not (elev.is_cuda and elev.dim() == 2 and elev.is_contiguous() and elev.dtype in (torch.float32, torch.float64)):
-            raise ValueError("device elev must be a contiguous 2D float32 / float64 CUDA tensor")
+        _args.device_float(elev, "device elev must be a contiguous 2D float32 / float64 CUDA tensor")
         if out is None:
             out = torch.empty_like(elev, memory_format=torch.contiguous_format)
-        elif not (hasattr(out, "is_cuda") and out.is_cuda and out.is_contiguous() and out.shape == elev.shape and out.dtype == elev.dtype
+        elif not (_args.is_tensor(out) and out.is_cuda and out.is_contiguous() and out.shape == elev.shape and out.dtype == elev.dtype
                   and out.device == elev.device):
             raise ValueError("out must be a contiguous CUDA tensor of elev's shape, dtype and device")
         ctx = ctx or _lib.default_context(elev.device.index)
-        with ctx.call_lock:
-            ctx.set_stream(torch.cuda.current_stream(elev.device).cuda_stream)
-            ctx.check(ctx._L.xdemhip_poly2d_apply(ctx.handle, elev.data_ptr(), _lib.F32 if elev.dtype == torch.float32 else _lib.F64,
-                                                  elev.shape[0], elev.shape[1], int(row_offset), params.ctypes.data_as(dp), K - 1,
-                                                  out.data_ptr(), _lib.DEVICE))
-        return out
-    ctx = ctx or _lib.default_context()
-    arr = np.ascontiguousarray(_host_array(elev))
-    if arr.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
-        arr = arr.astype(np.float32)
-    res = np.empty_like(arr)
-    ctx.check(ctx._L.xdemhip_poly2d_apply(ctx.handle, arr.ctypes.data, _lib.F32 if arr.dtype == np.float32 else _lib.F64, arr.shape[0],
-                                          arr.shape[1], int(row_offset), params.ctypes.data_as(dp), K - 1, res.ctypes.data, _lib.HOST))
-    return res
+    else:
+        ctx = ctx or _lib.default_context()
+        elev = _args.host_float(elev)
+        out = np.empty_like(elev)
+    with _args.torch_stream_scope(ctx, elev):
+        ctx.check(ctx._L.xdemhip_poly2d_apply(ctx.handle, _args.ptr(elev), _args.code(elev), elev.shape[0], elev.shape[1], int(row_offset),
+                                              _args.dp(params), K - 1, _args.ptr(out), _args.space(elev)))
+    return out
 
 
 def _check_weights(weights) -> None:
@@ -401,8 +361,8 @@ class Deramp(_Step):
         if fit_func is polynomial_2d:
             out = poly2d_apply(elev, params)
         else:   # a custom surface: evaluated on the host, as upstream does
-            arr = np.asarray(_host_array(elev))
-            if arr.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+            arr = _host_array(elev)
+            if arr.dtype not in _args.FLOATS:
                 arr = arr.astype(np.float32)
             xx, yy = np.meshgrid(np.arange(0, arr.shape[1]), np.arange(0, arr.shape[0]))
             out = (arr + fit_func((xx, yy), *params)).astype(arr.dtype)

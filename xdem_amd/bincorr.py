@@ -28,9 +28,10 @@ from typing import Any, Callable
 import numpy as np
 import scipy.optimize
 
-from . import _lib
+from . import _args, _lib
+from ._args import is_tensor, nan_filled
 from ._coregbase import _Step, _with_transform, draw
-from .biascorr import DhPlan, _check_weights, _host_array, plane_in_space
+from .biascorr import DhPlan, _check_weights
 from .fit import fit_workflows, polynomial_1d, robust_norder_polynomial_fit, sumsin_1d
 
 MAX_FUSED_VARS = 3
@@ -87,7 +88,7 @@ def _source(var: _Var, plane_ptr=None, plane_code=None) -> _lib.VarSrc:
 def _host_plane(var: _Var, elev: np.ndarray) -> np.ndarray:
     """The variable as a host plane (the host routes of ``apply``)."""
     if var.kind == "plane":
-        return np.asarray(var.plane.cpu().numpy() if hasattr(var.plane, "is_cuda") else _host_array(var.plane))
+        return var.plane.cpu().numpy() if is_tensor(var.plane) else nan_filled(var.plane)
     if var.kind == "rotated":
         c, s, rx, ry, off = var.rot
         H, W = elev.shape
@@ -104,53 +105,44 @@ def corr_apply(elev, kind: int, variables: list, n_tab, a=None, b=None, table=No
     ``_lib.CORR_POLY`` / ``_lib.CORR_SUMSIN`` (``table`` = the parameters).  Returns (out, pixels in a bin without a row)."""
     if len(variables) > MAX_FUSED_VARS:
         raise NotImplementedError(f"the fused apply takes at most {MAX_FUSED_VARS} variables, got {len(variables)}")
-    device = hasattr(elev, "is_cuda")
-    keep = []
+    device = is_tensor(elev)
     if device:
         import torch
 
-        if not (elev.is_cuda and elev.dim() == 2 and elev.is_contiguous() and elev.dtype in (torch.float32, torch.float64)):
-            raise ValueError("device elev must be a contiguous 2D float32 / float64 CUDA tensor")
+        _args.device_float(elev, "device elev must be a contiguous 2D float32 / float64 CUDA tensor")
         out = torch.empty_like(elev, memory_format=torch.contiguous_format)
-        shape, code, e_ptr, o_ptr, space = tuple(elev.shape), (_lib.F32 if elev.dtype == torch.float32 else _lib.F64), elev.data_ptr(), out.data_ptr(), _lib.DEVICE
         ctx = ctx or _lib.default_context(elev.device.index)
     else:
-        arr = np.ascontiguousarray(_host_array(elev))
-        if arr.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
-            arr = arr.astype(np.float32)
-        if arr.ndim != 2:
+        elev = _args.host_float(elev)
+        if elev.ndim != 2:
             raise ValueError("elev must be a 2D array")
-        out = np.empty_like(arr)
-        keep.append(arr)
-        shape, code, e_ptr, o_ptr, space = arr.shape, (_lib.F32 if arr.dtype == np.float32 else _lib.F64), arr.ctypes.data, out.ctypes.data, _lib.HOST
+        out = np.empty_like(elev)
         ctx = ctx or _lib.default_context()
-    srcs = []
+    shape = tuple(elev.shape)
+    keep, srcs = [], []
     for v in variables:
         if v.kind != "plane":
             srcs.append(_source(v))
             continue
-        p_ptr, p_code, p_shape, t = plane_in_space(v.plane, elev.device if device else None)
-        if p_shape != tuple(shape):
-            raise ValueError(f"a bias variable has shape {p_shape}, the raster {tuple(shape)}")
+        p_ptr, p_code, p_shape, t = _args.plane_in_space(v.plane, elev.device if device else None)
+        if p_shape != shape:
+            raise ValueError(f"a bias variable has shape {p_shape}, the raster {shape}")
         keep.append(t)
         srcs.append(_source(v, p_ptr, p_code))
     n_var = len(srcs)
     arr_src = (_lib.VarSrc * n_var)(*srcs)
     n_tab = [int(n) for n in n_tab]
     nt = (ctypes.c_int * len(n_tab))(*n_tab)
-    dp = ctypes.POINTER(ctypes.c_double)
     as_d = lambda x: None if x is None else np.ascontiguousarray(x, dtype=np.float64)  # noqa: E731
     a, b, table = as_d(a), as_d(b), as_d(table)
     decided = None if decided is None else np.ascontiguousarray(decided, dtype=np.uint8)
-    ptr = lambda x: None if x is None else x.ctypes.data_as(dp)  # noqa: E731
     missing = ctypes.c_int64()
     with ctx.call_lock:
         if device:
-            import torch
-
-            torch.cuda.current_stream(elev.device).synchronize()   # (the inputs are complete; the call itself returns synchronised)
-        rc = ctx._L.xdemhip_corr_apply(ctx.handle, e_ptr, code, shape[0], shape[1], int(kind), n_var, arr_src, nt, ptr(a), ptr(b), ptr(table),
-                                       None if decided is None else decided.ctypes.data_as(ctypes.c_char_p), o_ptr, ctypes.byref(missing), space)
+            _args.synchronize_torch(elev)   # (the inputs are complete; the call itself returns synchronised)
+        rc = ctx._L.xdemhip_corr_apply(ctx.handle, _args.ptr(elev), _args.code(elev), shape[0], shape[1], int(kind), n_var, arr_src, nt,
+                                       _args.dp(a), _args.dp(b), _args.dp(table), _args.chars(decided), _args.ptr(out), ctypes.byref(missing),
+                                       _args.space(elev))
     ctx.check(rc)
     del keep
     return out, int(missing.value)
@@ -188,7 +180,7 @@ def _bin_or_and_fit_nd(fit_or_bin: str, params: dict, values, columns: dict, wei
     if fit_or_bin in ["fit", "bin_and_fit"]:
         if "random_state" not in inspect.getfullargspec(params["fit_optimizer"]).args and "random_state" in kwargs:
             kwargs.pop("random_state")
-    to_host = lambda c: c.cpu().numpy() if hasattr(c, "is_cuda") else np.asarray(c)  # noqa: E731
+    to_host = lambda c: c.cpu().numpy() if is_tensor(c) else np.asarray(c)  # noqa: E731
     df, results = None, None
     if fit_or_bin == "fit":
         logging.debug("Estimating alignment along variables %s by fitting with function %s.", ", ".join(names), params["fit_func"].__name__)
@@ -362,7 +354,7 @@ class BiasCorr(_Step):
             interp = interp_nd_binning(df=df, list_var_names=names, statistic=fb["bin_statistic"], min_count=min_count)
             return corr_apply(elev, _lib.CORR_GRID, var_list, [len(g) for g in interp.grid], a=np.concatenate(interp.grid), table=interp.values)[0]
         # per bin: the lookup of get_perbin_nd_binning (upstream calls it with its default min_count = 0 here, biascorr.py:302-307)
-        elev_dtype = np.dtype(np.float32 if "float32" in str(elev.dtype) else np.float64) if hasattr(elev, "is_cuda") else _elev_host(elev).dtype
+        elev_dtype = np.dtype(np.float32 if "float32" in str(elev.dtype) else np.float64) if is_tensor(elev) else _elev_host(elev).dtype
         dts = [_var_dtype(v, elev_dtype) for v in var_list]
         stat_name = fb["bin_statistic"] if isinstance(fb["bin_statistic"], str) else fb["bin_statistic"].__name__
         if stat_name not in df.columns:
@@ -386,16 +378,12 @@ class BiasCorr(_Step):
 
 
 def _elev_host(elev) -> np.ndarray:
-    arr = np.asarray(elev.cpu().numpy() if hasattr(elev, "is_cuda") else _host_array(elev))
-    return arr if arr.dtype in (np.dtype(np.float32), np.dtype(np.float64)) else arr.astype(np.float32)
+    arr = elev.cpu().numpy() if is_tensor(elev) else nan_filled(elev)
+    return arr if arr.dtype in _args.FLOATS else arr.astype(np.float32)
 
 
 def _like(elev, out: np.ndarray):
-    if hasattr(elev, "is_cuda"):
-        import torch
-
-        return torch.from_numpy(out).to(elev.device)
-    return out
+    return _args.same_space(out, elev)
 
 
 def _var_dtype(v: _Var, elev_dtype: np.dtype) -> np.dtype:
@@ -404,8 +392,8 @@ def _var_dtype(v: _Var, elev_dtype: np.dtype) -> np.dtype:
         return np.dtype(np.float64)
     if v.kind == "raster":
         return elev_dtype
-    dt = np.dtype(str(v.plane.dtype).replace("torch.", ""))
-    return dt if dt in (np.dtype(np.float32), np.dtype(np.float64)) else np.dtype(np.float64)
+    dt = _args.np_dtype(v.plane)
+    return dt if dt in _args.FLOATS else np.dtype(np.float64)
 
 
 # ---- DirectionalBias ---------------------------------------------------------------------------------------------------------------
@@ -451,11 +439,11 @@ class TerrainBias(BiasCorr):
         from . import terrain
 
         res = _resolution(resolution)
-        if hasattr(raster, "is_cuda"):
+        if is_tensor(raster):
             if res[0] != res[1]:
                 raise ValueError(f"The terrain attributes on the device take one resolution for X and Y ({res} was given).")
             return _Var("plane", terrain.terrain_attributes_device(raster, [attr], resolution=res[0])[0])
-        return _Var("plane", terrain.get_terrain_attribute(_host_array(raster), attr, resolution=res))
+        return _Var("plane", terrain.get_terrain_attribute(nan_filled(raster), attr, resolution=res))
 
     def _fit_vars(self, ref, bias_vars, resolution) -> dict:
         attr = self.meta["inputs"]["specific"]["terrain_attribute"]

@@ -27,8 +27,9 @@ from typing import Any
 
 import numpy as np
 
-from . import _lib
-from ._coregbase import _Plan, raster_pair
+from . import _args, _lib
+from ._args import is_tensor, nan_filled, raster_pair
+from ._lib import _Plan
 
 BATCHED_DEFAULT = True   # tests: False sends an eligible step down the loop route
 
@@ -69,10 +70,6 @@ def _transform6(transform, resolution) -> tuple[float, ...]:
     return (rx, 0.0, 0.0, 0.0, -ry, 0.0)
 
 
-def _filled(a):
-    return a.filled(np.nan) if isinstance(a, np.ma.MaskedArray) else a
-
-
 class BWPlan(_Plan):
     """Device-resident state of the Nuth-Kaab fits of all tiles of a tiling (``xdemhip_bw_plan``).  ``n_valid``: valid pixels per tile."""
 
@@ -88,9 +85,8 @@ class BWPlan(_Plan):
         self.n_tiles = int(self.tiles.shape[0])
         h = ctypes.c_void_p()
         nv = np.zeros(self.n_tiles, dtype=np.int64)
-        ip = ctypes.POINTER(ctypes.c_int64)
         self.ctx.check(self.ctx._L.xdemhip_bw_create(self.ctx.handle, p.ref, p.tba, p.inlier, p.code, p.shape[0], p.shape[1], self.n_tiles,
-                                                     self.tiles.ctypes.data_as(ip), p.memspace, ctypes.byref(h), nv.ctypes.data_as(ip)))
+                                                     _args.i64p(self.tiles), p.memspace, ctypes.byref(h), _args.i64p(nv)))
         self.handle = h
         self.n_valid = nv
 
@@ -99,7 +95,7 @@ class BWPlan(_Plan):
         sizes = (self.tiles[:, 1] - self.tiles[:, 0]) * (self.tiles[:, 3] - self.tiles[:, 2])
         total = int(sizes.sum())
         st, asp, valid = np.empty(total, dtype=self.dtype), np.empty(total, dtype=self.dtype), np.empty(total, dtype=np.uint8)
-        self.ctx.check(self.ctx._L.xdemhip_bw_get_aux(self.handle, st.ctypes.data, asp.ctypes.data, valid.ctypes.data))
+        self.ctx.check(self.ctx._L.xdemhip_bw_get_aux(self.handle, _args.ptr(st), _args.ptr(asp), _args.ptr(valid)))
         out, off = [], 0
         for (r0, r1, c0, c1), n in zip(self.tiles, sizes):
             shape = (int(r1 - r0), int(c1 - c0))
@@ -122,12 +118,10 @@ class BWPlan(_Plan):
         sx, sy = np.ascontiguousarray(shift_x, dtype=np.float64), np.ascontiguousarray(shift_y, dtype=np.float64)
         if not (act.size == sx.size == sy.size == self.n_tiles) or out["edges"].shape != (self.n_tiles, n_bins + 1):
             raise ValueError("one entry per tile expected")
-        dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)
-        self.ctx.check(self.ctx._L.xdemhip_bw_nk_step(self.handle, act.ctypes.data, sx.ctypes.data_as(dp), sy.ctypes.data_as(dp), float(res[0]),
-                                                      float(res[1]), n_bins, out["vshift"].ctypes.data_as(dp), out["n_valid"].ctypes.data_as(ip),
-                                                      out["y_mean"].ctypes.data_as(dp), out["y_std"].ctypes.data_as(dp),
-                                                      out["edges"].ctypes.data_as(dp), out["counts"].ctypes.data_as(ip),
-                                                      out["medians"].ctypes.data_as(dp)))
+        dp, ip = _args.dp, _args.i64p
+        self.ctx.check(self.ctx._L.xdemhip_bw_nk_step(self.handle, _args.ptr(act), dp(sx), dp(sy), float(res[0]), float(res[1]), n_bins,
+                                                      dp(out["vshift"]), ip(out["n_valid"]), dp(out["y_mean"]), dp(out["y_std"]),
+                                                      dp(out["edges"]), ip(out["counts"]), dp(out["medians"])))
         return out
 
 
@@ -139,28 +133,22 @@ def warp_affine_field(dem, transform6, coeff_x, coeff_y, coeff_z, ctx: _lib.Cont
     if (1.0 + cx[0]) * (1.0 + cy[1]) - cx[1] * cy[0] == 0.0:
         raise ValueError("The shift field is singular: I + [[a_x, b_x], [a_y, b_y]] has no inverse.")
     t6 = np.array(transform6, dtype=np.float64)
-    dp = ctypes.POINTER(ctypes.c_double)
-    if hasattr(dem, "is_cuda"):
+    device = is_tensor(dem)
+    if device:
         import torch
 
-        if not (dem.is_cuda and dem.is_contiguous() and dem.dim() == 2 and dem.dtype in (torch.float32, torch.float64)):
-            raise ValueError("a device input must be a contiguous 2D float32 / float64 CUDA tensor")
-        torch.cuda.current_stream(dem.device).synchronize()
+        _args.device_float(dem, "a device input must be a contiguous 2D float32 / float64 CUDA tensor")
+        _args.synchronize_torch(dem)
         out = torch.empty_like(dem)
-        ctx.check(ctx._L.xdemhip_bw_apply(ctx.handle, dem.data_ptr(), _lib.F32 if dem.dtype == torch.float32 else _lib.F64, dem.shape[0], dem.shape[1],
-                                          t6.ctypes.data_as(dp), cx.ctypes.data_as(dp), cy.ctypes.data_as(dp), cz.ctypes.data_as(dp),
-                                          out.data_ptr(), _lib.DEVICE))
+    else:
+        dem = _args.host_float(dem)
+        if dem.ndim != 2:
+            raise ValueError("the elevation array must be 2D")
+        out = np.empty_like(dem)
+    ctx.check(ctx._L.xdemhip_bw_apply(ctx.handle, _args.ptr(dem), _args.code(dem), dem.shape[0], dem.shape[1], _args.dp(t6), _args.dp(cx),
+                                      _args.dp(cy), _args.dp(cz), _args.ptr(out), _args.space(dem)))
+    if device:
         ctx.synchronize()
-        return out
-    arr = np.ascontiguousarray(_filled(dem))
-    if arr.ndim != 2:
-        raise ValueError("the elevation array must be 2D")
-    if arr.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
-        arr = arr.astype(np.float32)
-    out = np.empty_like(arr)
-    ctx.check(ctx._L.xdemhip_bw_apply(ctx.handle, arr.ctypes.data, _lib.F32 if arr.dtype == np.float32 else _lib.F64, arr.shape[0], arr.shape[1],
-                                      t6.ctypes.data_as(dp), cx.ctypes.data_as(dp), cy.ctypes.data_as(dp), cz.ctypes.data_as(dp),
-                                      out.ctypes.data, _lib.HOST))
     return out
 
 
@@ -255,7 +243,7 @@ class BlockwiseCoreg:
         sx, sy, sz = np.full(n, np.nan), np.full(n, np.nan), np.full(n, np.nan)
 
         def cut(a, r0, r1, c0, c1):   # (the steps' fit takes host arrays: a tile of a device raster is fetched)
-            return a[r0:r1, c0:c1].cpu().numpy() if hasattr(a, "is_cuda") else np.ascontiguousarray(a[r0:r1, c0:c1])
+            return a[r0:r1, c0:c1].cpu().numpy() if is_tensor(a) else np.ascontiguousarray(a[r0:r1, c0:c1])
 
         def all_invalid(a) -> bool:
             return not bool(np.isfinite(a).any())
@@ -281,9 +269,9 @@ class BlockwiseCoreg:
         grid -- NumPy, or contiguous CUDA tensors of one dtype -- whose georeferencing comes from ``transform`` or from ``resolution``."""
         t6 = _transform6(transform, resolution)
         res = (abs(t6[0]), abs(t6[4]))
-        ref, tba = _filled(reference_elev), _filled(to_be_aligned_elev)
-        if not hasattr(ref, "is_cuda"):
-            ref, tba = np.asarray(ref), np.asarray(tba)
+        ref, tba = reference_elev, to_be_aligned_elev
+        if not is_tensor(ref):
+            ref, tba = nan_filled(ref), nan_filled(tba)
         if tuple(ref.shape) != tuple(tba.shape) or len(ref.shape) != 2:
             raise ValueError("ref and tba must be 2D arrays of the same shape")
         self.meta["inputs"] = self.procstep.meta["inputs"]

@@ -28,7 +28,7 @@ from typing import Any, Callable
 import numpy as np
 import scipy.optimize
 
-from . import _lib
+from . import _args, _lib
 from . import epc as _epc
 from ._coregbase import NO_VALID, CoregPipeline, _Plan, _Step, apply_translation, draw, raster_pair  # noqa: F401
 from ._coregbase import subsample_ranks, subsample_valid_mask  # noqa: F401
@@ -146,10 +146,9 @@ class NKPlan(_Plan):
         med = np.empty(n_bins, dtype=np.float64)
         vshift, ymean, ystd = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
         nv = ctypes.c_int64()
-        dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)
         rc = self.ctx._L.xdemhip_nk_step(self.handle, float(shift_x), float(shift_y), float(res[0]), float(res[1]), int(n_bins),
                                          ctypes.byref(vshift), ctypes.byref(nv), ctypes.byref(ymean), ctypes.byref(ystd),
-                                         edges.ctypes.data_as(dp), counts.ctypes.data_as(ip), med.ctypes.data_as(dp))
+                                         _args.dp(edges), _args.i64p(counts), _args.dp(med))
         if rc != _lib.OK:
             self._raise_step_error(rc)
         return {"vshift": vshift.value, "n_valid": int(nv.value), "y_mean": ymean.value, "y_std": ystd.value,
@@ -169,10 +168,9 @@ class NKPlan(_Plan):
         edges = np.empty(n_bins + 1, dtype=np.float64)
         vshift, ymean, ystd = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
         nv = ctypes.c_int64()
-        dp = ctypes.POINTER(ctypes.c_double)
         rc = self.ctx._L.xdemhip_nk_step_values(self.handle, float(shift_x), float(shift_y), float(res[0]), float(res[1]), int(n_bins),
                                                 ctypes.byref(vshift), ctypes.byref(nv), ctypes.byref(ymean), ctypes.byref(ystd),
-                                                edges.ctypes.data_as(dp), y.ctypes.data, bins.ctypes.data, _lib.HOST)
+                                                _args.dp(edges), _args.ptr(y), _args.ptr(bins), _lib.HOST)
         if rc != _lib.OK:
             self._raise_step_error(rc)
         ok = (bins != 0xFFFF) & np.isfinite(y)
@@ -204,10 +202,9 @@ class NKPlan(_Plan):
         sums = np.empty(10, dtype=np.float64)
         vshift, ymean, ystd = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
         nv = ctypes.c_int64()
-        dp = ctypes.POINTER(ctypes.c_double)
         rc = self.ctx._L.xdemhip_nk_step_fit(self.handle, float(shift_x), float(shift_y), float(res[0]), float(res[1]),
                                              ctypes.byref(vshift), ctypes.byref(nv), ctypes.byref(ymean), ctypes.byref(ystd),
-                                             sums.ctypes.data_as(dp))
+                                             _args.dp(sums))
         if rc != _lib.OK:
             self._raise_step_error(rc)
         return {"vshift": vshift.value, "n_valid": int(nv.value), "y_mean": ymean.value, "y_std": ystd.value, "sums": sums}
@@ -224,7 +221,6 @@ class NKPlan(_Plan):
 
     def set_bin_edges(self, edges) -> None:
         """Explicit aspect-bin edges (``bin_sizes={"aspect": edges}`` upstream); ``None`` restores SciPy's automatic edges."""
-        dp = ctypes.POINTER(ctypes.c_double)
         if edges is None:
             self.ctx.check(self.ctx._L.xdemhip_nk_set_bin_edges(self.handle, None, 0, 0))
             self._n_custom_bins = None
@@ -232,7 +228,7 @@ class NKPlan(_Plan):
         e = np.ascontiguousarray(edges, dtype=np.float64).ravel()
         # SciPy's rightmost-edge rule rounds to `decimal` digits, from the smallest spacing of the dtype-cast edges
         decimal = int(-np.log10(np.diff(e.astype(self.dtype)).min())) + 6
-        self.ctx.check(self.ctx._L.xdemhip_nk_set_bin_edges(self.handle, e.ctypes.data_as(dp), int(e.size), decimal))
+        self.ctx.check(self.ctx._L.xdemhip_nk_set_bin_edges(self.handle, _args.dp(e), int(e.size), decimal))
         self._n_custom_bins = int(e.size) - 1
 
     def set_statistic(self, bin_statistic) -> None:
@@ -247,7 +243,7 @@ class NKPlan(_Plan):
         st = np.empty(self.shape, dtype=self.dtype)
         asp = np.empty(self.shape, dtype=self.dtype)
         valid = np.empty(self.shape, dtype=np.uint8)
-        self.ctx.check(self.ctx._L.xdemhip_nk_get_aux(self.handle, st.ctypes.data, asp.ctypes.data, valid.ctypes.data))
+        self.ctx.check(self.ctx._L.xdemhip_nk_get_aux(self.handle, _args.ptr(st), _args.ptr(asp), _args.ptr(valid)))
         return st, asp, valid.astype(bool)
 
     def subsample(self, ranks: np.ndarray) -> int:
@@ -256,7 +252,7 @@ class NKPlan(_Plan):
         (``xdemhip_nk_subsample``).  Whole-raster plans of one process only.  Returns the new number of valid pixels."""
         ranks = np.ascontiguousarray(ranks, dtype=np.int64)
         nv = ctypes.c_int64()
-        self.ctx.check(self.ctx._L.xdemhip_nk_subsample(self.handle, ranks.ctypes.data, int(ranks.size), _lib.HOST, ctypes.byref(nv)))
+        self.ctx.check(self.ctx._L.xdemhip_nk_subsample(self.handle, _args.ptr(ranks), int(ranks.size), _lib.HOST, ctypes.byref(nv)))
         self.n_valid = int(nv.value)
         return self.n_valid
 
@@ -278,10 +274,8 @@ def binned_median(x: np.ndarray, y: np.ndarray, n_bins: int = 72, ctx: _lib.Cont
     edges = np.empty(n_bins + 1, dtype=np.float64)
     counts = np.empty(n_bins, dtype=np.int64)
     med = np.empty(n_bins, dtype=np.float64)
-    dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)
-    ctx.check(ctx._L.xdemhip_binned_median(ctx.handle, x.ctypes.data, y.ctypes.data, _lib.F32 if dt == np.float32 else _lib.F64,
-                                           x.size, int(n_bins), edges.ctypes.data_as(dp), counts.ctypes.data_as(ip),
-                                           med.ctypes.data_as(dp)))
+    ctx.check(ctx._L.xdemhip_binned_median(ctx.handle, _args.ptr(x), _args.ptr(y), _args.code(dt), x.size, int(n_bins), _args.dp(edges),
+                                           _args.i64p(counts), _args.dp(med)))
     return edges, counts, med
 
 
@@ -572,8 +566,7 @@ class NuthKaab(_TranslationStep):
             self.meta["outputs"]["random"] = {"subsample_final": n_final}
             return self
         res = self._resolution(resolution, transform)
-        ref = np.asarray(reference_elev.filled(np.nan) if isinstance(reference_elev, np.ma.MaskedArray) else reference_elev)
-        tba = np.asarray(to_be_aligned_elev.filled(np.nan) if isinstance(to_be_aligned_elev, np.ma.MaskedArray) else to_be_aligned_elev)
+        ref, tba = _args.nan_filled(reference_elev), _args.nan_filled(to_be_aligned_elev)
         # initial_shift (base.py:2307-2313, 2358-2366): upstream translates the reference by (-sx, -sy), fits, and adds (sx, sy)
         # back to the estimated shift -- i.e. the search starts from shift_x = sx.  Here the iteration itself starts from
         # the offsets (-sx, -sy), which samples the to-be-aligned DEM once at the shifted position instead of resampling

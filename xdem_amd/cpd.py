@@ -22,13 +22,12 @@ from typing import Any
 
 import numpy as np
 
-from . import _lib
+from . import _args, _lib
+from ._args import c_doubles
 from ._coregbase import _Plan, draw
 from .biascorr import DhPlan
 from .icp import _points
-from .rigid import _c6, _iterate_method, _RigidStep, invert_matrix
-
-_DP = ctypes.POINTER(ctypes.c_double)
+from .rigid import _iterate_method, _RigidStep, invert_matrix
 
 N_SUMS = 18
 BAD_WEIGHT = "CPD weight must be in [0, 1)."
@@ -53,7 +52,7 @@ class CpdCloud(_Plan):
         normals, by the same device code."""
         h, cnt = ctypes.c_void_p(), ctypes.c_int64()
         cen, fac = np.empty(3, dtype=np.float64), ctypes.c_double()
-        plan.ctx.check(plan.ctx._L.xdemhip_cpd_create_plan(plan.handle, _c6(t6), int(bool(standardize)), ctypes.byref(h), cen.ctypes.data_as(_DP),
+        plan.ctx.check(plan.ctx._L.xdemhip_cpd_create_plan(plan.handle, c_doubles(t6), int(bool(standardize)), ctypes.byref(h), _args.dp(cen),
                                                            ctypes.byref(fac), ctypes.byref(cnt)))
         out = cls(plan.ctx, h, cnt.value, cnt.value)
         out.centroid, out.std_fac = (float(cen[0]), float(cen[1]), float(cen[2])), float(fac.value)
@@ -65,23 +64,23 @@ class CpdCloud(_Plan):
         ref, tba = _points(ref_points, "ref_points"), _points(tba_points, "tba_points")
         ctx = ctx or _lib.default_context()
         h = ctypes.c_void_p()
-        ctx.check(ctx._L.xdemhip_cpd_create_points(ctx.handle, ref.ctypes.data_as(_DP), ref.shape[1], tba.ctypes.data_as(_DP), tba.shape[1], ctypes.byref(h)))
+        ctx.check(ctx._L.xdemhip_cpd_create_points(ctx.handle, _args.dp(ref), ref.shape[1], _args.dp(tba), tba.shape[1], ctypes.byref(h)))
         return cls(ctx, h, ref.shape[1], tba.shape[1])
 
     def estep(self, matrix=None, sigma2: float | None = None, weight: float = 0.0) -> tuple[np.ndarray, float]:
         """One E-step with the to-be-aligned cloud moved by the 4 x 4 ``matrix`` (``xdemhip_cpd_estep``): ``(sums, sigma2)`` -- the 18
         sums ``Np, muX (3), muY (3), A (9, row by row), xPx, YPY`` of the M-step, and the variance used: ``sigma2``, or with ``None`` the
         mean squared coordinate difference over all pairs."""
-        m16 = None if matrix is None else _c6(np.asarray(matrix, dtype=np.float64).ravel())
+        m16 = None if matrix is None else c_doubles(np.asarray(matrix, dtype=np.float64).ravel())
         s, used = np.empty(N_SUMS, dtype=np.float64), ctypes.c_double()
         self.ctx.check(self.ctx._L.xdemhip_cpd_estep(self.handle, m16, float("nan") if sigma2 is None else float(sigma2), float(weight),
-                                                     s.ctypes.data_as(_DP), ctypes.byref(used)))
+                                                     _args.dp(s), ctypes.byref(used)))
         return s, float(used.value)
 
     def terms(self) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
         """``(P1 (M), Pt1 (N), PX (3, M))`` of the last E-step (``xdemhip_cpd_terms``)."""
         p1, pt1, px = np.empty(self.m, dtype=np.float64), np.empty(self.n, dtype=np.float64), np.empty((3, self.m), dtype=np.float64)
-        self.ctx.check(self.ctx._L.xdemhip_cpd_terms(self.handle, p1.ctypes.data_as(_DP), pt1.ctypes.data_as(_DP), px.ctypes.data_as(_DP)))
+        self.ctx.check(self.ctx._L.xdemhip_cpd_terms(self.handle, _args.dp(p1), _args.dp(pt1), _args.dp(px)))
         return p1, pt1, px
 
 

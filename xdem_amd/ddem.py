@@ -15,20 +15,17 @@ from typing import Any
 import numpy as np
 
 from . import volume
+from ._args import is_tensor
 from .dem import DEM
 from .vector import Vector
 
 _GDAL_METHODS = ("idw", "local_hypsometric")
 
 
-def _is_tensor(x) -> bool:
-    return volume._is_tensor(x)
-
-
 def _has_voids(data) -> bool:
     """A masked or a non-finite pixel: what a fill fills.  (Upstream's test in ``filled_data``, ddem.py:128, looks for NaN and the
     mask and lets an infinity pass; here an infinity is a void on every route, as the stack's subtraction pass counts it.)"""
-    if _is_tensor(data):
+    if is_tensor(data):
         return not bool(data.isfinite().all().item())
     if isinstance(data, np.ma.MaskedArray) and np.any(np.ma.getmaskarray(data)):
         return True
@@ -37,7 +34,7 @@ def _has_voids(data) -> bool:
 
 def raster_of(data, transform, crs=None, nodata=None) -> DEM:
     """A DEM around `data` as it is -- a device tensor stays one (``DEM(...)`` itself makes a host array of what it gets)."""
-    if not _is_tensor(data):
+    if not is_tensor(data):
         return DEM.from_array(data, transform, crs, nodata)
     if data.ndim != 2:
         raise ValueError("DEM data must be 2D")
@@ -56,15 +53,15 @@ def mask_as_array(mask, like=None) -> Any:
     if isinstance(mask, Vector):
         if like is None:
             raise ValueError("a Vector mask needs the raster it is burnt into")
-        return mask.create_mask(like, device=_is_tensor(like.data))
+        return mask.create_mask(like, device=is_tensor(like.data))
     if isinstance(mask, DEM):
         data = mask.data
-        if _is_tensor(data):
+        if is_tensor(data):
             top = data[~data.isnan()].max() if data.is_floating_point() else data.max()
             return data == (top if top.item() not in (0, False) else True)
         top = np.nanmax(data)
         return np.asarray(data == (top if top not in [0, False] else True)).squeeze()
-    if _is_tensor(mask) or isinstance(mask, np.ndarray):
+    if is_tensor(mask) or isinstance(mask, np.ndarray):
         return mask
     raise TypeError(f"Raster has invalid type: {type(mask)}. Expected one of: ['xdem_amd.DEM', 'numpy.ndarray', 'torch.Tensor']")
 
@@ -86,7 +83,7 @@ class dDEM(DEM):
 
     def copy(self, new_array=None) -> "dDEM":
         if new_array is None:
-            new_array = self.data.clone() if _is_tensor(self.data) else self.data.copy()
+            new_array = self.data.clone() if is_tensor(self.data) else self.data.copy()
         return dDEM.from_array(new_array, self.transform, self.crs, self.start_time, self.end_time)
 
     @property
@@ -101,14 +98,14 @@ class dDEM(DEM):
             voids = _has_voids(self.data)
         if voids:
             return None
-        return self.data if _is_tensor(self.data) else np.asarray(self.data)
+        return self.data if is_tensor(self.data) else np.asarray(self.data)
 
     @filled_data.setter
     def filled_data(self, array) -> None:
-        size = array.numel() if _is_tensor(array) else np.size(array)
-        data_size = self.data.numel() if _is_tensor(self.data) else self.data.size
+        size = array.numel() if is_tensor(array) else np.size(array)
+        data_size = self.data.numel() if is_tensor(self.data) else self.data.size
         assert data_size == size, f"Array shape '{tuple(array.shape)}' differs from the data shape '{tuple(self.data.shape)}'"
-        self._filled_data = array.reshape(tuple(self.data.shape)) if _is_tensor(array) else np.asarray(array).reshape(self.data.shape)
+        self._filled_data = array.reshape(tuple(self.data.shape)) if is_tensor(array) else np.asarray(array).reshape(self.data.shape)
 
     @property
     def fill_method(self) -> str:

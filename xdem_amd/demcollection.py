@@ -26,32 +26,31 @@ import numpy as np
 import pandas as pd
 import scipy.interpolate
 
-from . import _lib, volume
+from . import _args, _lib, volume
+from ._args import dp, i32p, i64p, is_tensor, ptr
 from .ddem import dDEM
 from .dem import DEM
 from .vector import Vector, union_mask
 
-_is_tensor = volume._is_tensor
-_I64P = ctypes.POINTER(ctypes.c_int64)
-_I32P = ctypes.POINTER(ctypes.c_int32)
-_DP = ctypes.POINTER(ctypes.c_double)
 MAX_PLANES = 1024   # (STK_MAX_PLANES of csrc/demstack.hip)
 INPUTS, DDEMS, FILLED = 0, 1, 2
 
 
-class StackPlan:
+class StackPlan(_lib._Plan):
     """T planes of one grid on the device with the dDEM and filled planes made from them: ``xdemhip_stack`` of include/xdemhip.h."""
+
+    _DESTROY = "xdemhip_stack_destroy"
 
     def __init__(self, planes, ref_index: int, ctx: _lib.Context | None = None):
         if not 1 <= len(planes) <= MAX_PLANES:
             raise ValueError(f"a stack holds 1 to {MAX_PLANES} DEMs; got {len(planes)}")
-        flat = [volume._float_plane(p, "dems") for p in planes]
-        self.on_device = _is_tensor(flat[0])
-        if any(_is_tensor(p) != self.on_device for p in flat):
+        flat = [_args.flat_float(p, "dems") for p in planes]
+        self.on_device = is_tensor(flat[0])
+        if any(is_tensor(p) != self.on_device for p in flat):
             raise ValueError("the DEMs of a stack must all be host arrays or all be device tensors")
         if any(p.shape != flat[0].shape for p in flat):
             raise ValueError("the DEMs of a stack must have the same number of pixels")
-        self.dtype = np.result_type(*[volume._np_dtype(p) for p in flat])   # (what NumPy makes of ref - dem; mixed: float64 throughout)
+        self.dtype = np.result_type(*[_args.np_dtype(p) for p in flat])   # (what NumPy makes of ref - dem; mixed: float64 throughout)
         if self.on_device:
             import torch
 
@@ -65,49 +64,29 @@ class StackPlan:
 
     def _start(self, ctx) -> None:
         self.ctx = ctx or _lib.default_context(self.inputs[0].device.index if self.on_device else None)
-        self.space = _lib.DEVICE if self.on_device else _lib.HOST
+        self.space = _args.space(self.inputs[0])
         self._after_torch()
         h = ctypes.c_void_p()
-        table = (ctypes.c_void_p * self.T)(*[volume._ptr(p).value for p in self.inputs])
+        table = (ctypes.c_void_p * self.T)(*[ptr(p) for p in self.inputs])
         with self.ctx.call_lock:
-            self.ctx.check(self.ctx._L.xdemhip_stack_create(self.ctx.handle, table, self.T, _lib.F32 if self.dtype == np.float32 else _lib.F64,
-                                                            self.n, self.ref_index, self.space, ctypes.byref(h)))
+            self.ctx.check(self.ctx._L.xdemhip_stack_create(self.ctx.handle, table, self.T, _args.code(self.dtype), self.n, self.ref_index,
+                                                            self.space, ctypes.byref(h)))
         self.handle = h
         self.ctx.adopt(self)
-
-    def close(self) -> None:
-        if getattr(self, "handle", None):
-            self.ctx._L.xdemhip_stack_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self) -> None:  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
 
     def _after_torch(self) -> None:
         """Every pass begins here.  The library launches on its own stream, which does not order against torch's, and what a pass reads
         -- the inputs, the masks, and the dDEM and filled planes, which on the device are the caller's own tensors and may have been
         written to since the last pass -- is made on torch's: wait for it.  The calls themselves return synchronised."""
         if self.on_device:
-            import torch
-
-            torch.cuda.current_stream(self.inputs[0].device).synchronize()
+            _args.synchronize_torch(self.inputs[0])
 
     def _counts(self):
         return np.empty(self.T, np.int64), np.empty(self.T, np.int64)
 
     def set_masks(self, masks, mask_ids) -> None:
         """`masks`: distinct boolean arrays / tensors of n pixels; `mask_ids`: per plane the index of its mask, -1 for every pixel."""
-        self.masks = [volume._mask_plane(m, self.inputs[0]) for m in masks]   # (device masks are used in place: kept alive here)
+        self.masks = [_args.flat_mask(m, self.inputs[0]) for m in masks]   # (device masks are used in place: kept alive here)
         if any(m.shape[0] != self.n for m in self.masks):
             raise ValueError("a mask must have the same number of pixels as the DEMs")
         self.mask_ids = np.ascontiguousarray(mask_ids, dtype=np.int32)
@@ -115,9 +94,9 @@ class StackPlan:
         self._set_masks()
 
     def _set_masks(self) -> None:
-        table = (ctypes.c_void_p * max(1, len(self.masks)))(*[volume._ptr(m).value for m in self.masks])
+        table = (ctypes.c_void_p * max(1, len(self.masks)))(*[ptr(m) for m in self.masks])
         with self.ctx.call_lock:
-            self.ctx.check(self.ctx._L.xdemhip_stack_set_masks(self.handle, table, len(self.masks), self.mask_ids.ctypes.data_as(_I32P), self.space))
+            self.ctx.check(self.ctx._L.xdemhip_stack_set_masks(self.handle, table, len(self.masks), i32p(self.mask_ids), self.space))
 
     def subtract(self, can_equal=None):
         """(pixels that differ from the reference, non-finite dDEM pixels) per plane; planes without a differing pixel are zeroed,
@@ -127,8 +106,7 @@ class StackPlan:
         out = self._empty()
         self._after_torch()
         with self.ctx.call_lock:
-            self.ctx.check(self.ctx._L.xdemhip_stack_subtract(self.handle, flags.ctypes.data_as(_I32P), volume._ptr(out), self.space,
-                                                              differ.ctypes.data_as(_I64P), bad.ctypes.data_as(_I64P)))
+            self.ctx.check(self.ctx._L.xdemhip_stack_subtract(self.handle, i32p(flags), ptr(out), self.space, i64p(differ), i64p(bad)))
         self._out = {DDEMS: self._frozen(out)}
         return differ, bad
 
@@ -138,7 +116,7 @@ class StackPlan:
         lo, hi = np.empty(self.T, np.float64), np.empty(self.T, np.float64)
         self._after_torch()
         with self.ctx.call_lock:
-            self.ctx.check(self.ctx._L.xdemhip_stack_stats(self.handle, inl.ctypes.data_as(_I64P), lo.ctypes.data_as(_DP), hi.ctypes.data_as(_DP)))
+            self.ctx.check(self.ctx._L.xdemhip_stack_stats(self.handle, i64p(inl), dp(lo), dp(hi)))
         return inl, lo, hi
 
     def segments(self, nbs, edges):
@@ -149,8 +127,7 @@ class StackPlan:
         counts, med = np.empty((self.T, nb_max), np.int64), np.empty((self.T, nb_max), np.float64)
         self._after_torch()
         with self.ctx.call_lock:
-            self.ctx.check(self.ctx._L.xdemhip_stack_segments(self.handle, nb_max, nbs.ctypes.data_as(_I32P), edges.ctypes.data_as(_DP),
-                                                              counts.ctypes.data_as(_I64P), med.ctypes.data_as(_DP)))
+            self.ctx.check(self.ctx._L.xdemhip_stack_segments(self.handle, nb_max, i32p(nbs), dp(edges), i64p(counts), dp(med)))
         return counts, med
 
     def fill(self, ms, xs, ys):
@@ -164,9 +141,8 @@ class StackPlan:
         out = self._empty()
         self._after_torch()
         with self.ctx.call_lock:
-            self.ctx.check(self.ctx._L.xdemhip_stack_fill(self.handle, xs.shape[1], ms.ctypes.data_as(_I32P), xs.ctypes.data_as(_DP), ys.ctypes.data_as(_DP),
-                                                          volume._ptr(out), self.space, n_mask.ctypes.data_as(_I64P), n_fin.ctypes.data_as(_I64P),
-                                                          sums.ctypes.data_as(_DP)))
+            self.ctx.check(self.ctx._L.xdemhip_stack_fill(self.handle, xs.shape[1], i32p(ms), dp(xs), dp(ys), ptr(out), self.space, i64p(n_mask),
+                                                          i64p(n_fin), dp(sums)))
         self._out[FILLED] = self._frozen(out)
         return n_mask, n_fin, sums
 
@@ -174,13 +150,12 @@ class StackPlan:
         """The series figures of the INPUTS, DDEMS or FILLED planes over `mask` (one for all planes), or over every plane's own mask."""
         n_mask, n_fin = self._counts()
         sums = np.empty(self.T, np.float64)
-        m = None if mask is None else volume._mask_plane(mask, self.inputs[0])
+        m = None if mask is None else _args.flat_mask(mask, self.inputs[0])
         if m is not None and m.shape[0] != self.n:
             raise ValueError("a mask must have the same number of pixels as the DEMs")
         self._after_torch()   # (the mask's conversion, and whatever the caller wrote into the planes)
         with self.ctx.call_lock:
-            self.ctx.check(self.ctx._L.xdemhip_stack_series(self.handle, int(which), None if m is None else volume._ptr(m), self.space,
-                                                            n_mask.ctypes.data_as(_I64P), n_fin.ctypes.data_as(_I64P), sums.ctypes.data_as(_DP)))
+            self.ctx.check(self.ctx._L.xdemhip_stack_series(self.handle, int(which), ptr(m), self.space, i64p(n_mask), i64p(n_fin), dp(sums)))
         return n_mask, n_fin, sums
 
     def _empty(self):
@@ -194,7 +169,7 @@ class StackPlan:
     def _frozen(out):
         """A host copy of the stack's planes is read-only: the device keeps computing on its own planes, so a pixel written into the
         copy would be lost on it (a device array IS the stack's plane; to change a dDEM on the host, give it a new array)."""
-        if not _is_tensor(out):
+        if not is_tensor(out):
             out.setflags(write=False)
         return out
 
@@ -212,11 +187,11 @@ def _raster_like(data, like: DEM) -> DEM:
 
 
 def _address(x) -> tuple:
-    return (x.data_ptr() if _is_tensor(x) else x.__array_interface__["data"][0], tuple(x.shape), str(x.dtype))
+    return (ptr(x), tuple(x.shape), str(x.dtype))
 
 
 def _is_outline(x) -> bool:
-    return _is_tensor(x) or isinstance(x, (np.ndarray, Vector))
+    return is_tensor(x) or isinstance(x, (np.ndarray, Vector))
 
 
 def plane_model(counts: np.ndarray, medians: np.ndarray, zbins: np.ndarray, dtype: np.dtype):
@@ -336,7 +311,7 @@ class DEMCollection:
         """`parts` with their Vectors burnt into the dDEM's grid, in the memspace of its data: two Vectors in one union call.  The masks
         are kept, so a part is the same array every time it is asked for (the plans tell masks apart by address)."""
         grid = (tuple(ddem.data.shape), tuple(self.reference_dem.transform))
-        device = _is_tensor(ddem.data)
+        device = is_tensor(ddem.data)
         key = (tuple(id(part) for part in parts), outlines_filter, grid, device)
         if key not in self._burnt:
             chosen = tuple(part.query(outlines_filter) if outlines_filter is not None else part for part in parts)
@@ -351,7 +326,7 @@ class DEMCollection:
     def _mask_of(parts: tuple, shape: tuple):
         if len(parts) == 2:
             a, b = parts
-            mask = (a.bool() | b.bool()) if _is_tensor(a) else np.logical_or(a, b)
+            mask = (a.bool() | b.bool()) if is_tensor(a) else np.logical_or(a, b)
         elif len(parts) == 1:
             mask = parts[0]
         else:
@@ -402,7 +377,7 @@ class DEMCollection:
         """What tells that device planes were written to in place: torch's version counter, which a tensor shares with its views (the
         dDEMs' ``filled_data``).  Host planes are read-only.  Sums made before such a write are not reused: the next series reads
         the planes as they are."""
-        return planes._version if _is_tensor(planes) else 0
+        return planes._version if is_tensor(planes) else 0
 
     def _fill_stack(self) -> None:
         plan = self._plan

@@ -19,11 +19,9 @@ from typing import Any
 
 import numpy as np
 
-from . import _lib
-from ._coregbase import _Plan
-
-_DP = ctypes.POINTER(ctypes.c_double)
-_IP = ctypes.POINTER(ctypes.c_int64)
+from . import _args, _lib
+from ._args import is_tensor
+from ._lib import _Plan
 
 NK_NO_MORE_VALID = ("The subsample contains no more valid values. This can happen is the horizontal shift to "
                     "correct is very large, or if the algorithm diverged. To ensure all possible points can "
@@ -43,7 +41,7 @@ class _Geometry:
 
 
 def _column(v, name: str):
-    if hasattr(v, "is_cuda"):
+    if is_tensor(v):
         if v.dim() != 1:
             raise ValueError(f"EPC: column '{name}' must be 1-D")
         return v
@@ -122,12 +120,10 @@ def split_pair(reference_elev, to_be_aligned_elev):
 
 
 def _host_raster(raster):
-    arr = np.asarray(raster.filled(np.nan) if isinstance(raster, np.ma.MaskedArray) else raster)
+    arr = _args.host_float(raster)
     if arr.ndim != 2:
         raise ValueError("the raster of a raster-point pair must be a 2D array")
-    if arr.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
-        arr = arr.astype(np.float32)
-    return np.ascontiguousarray(arr)
+    return arr
 
 
 class PtsPlan(_Plan):
@@ -141,41 +137,29 @@ class PtsPlan(_Plan):
                  ctx: _lib.Context | None = None):
         self.handle = None
         t6 = transform6(transform)
-        if hasattr(raster, "is_cuda"):
+        if is_tensor(raster):
             import torch
 
-            if not (raster.is_cuda and raster.is_contiguous() and raster.dim() == 2 and raster.dtype in (torch.float32, torch.float64)):
-                raise ValueError("a device raster must be a contiguous 2D float32 / float64 CUDA tensor")
-            dev = raster.device
+            _args.device_float(raster, "a device raster must be a contiguous 2D float32 / float64 CUDA tensor")
 
             def col(v, dt):
-                v = v if hasattr(v, "is_cuda") else torch.from_numpy(np.ascontiguousarray(v))
-                return v.to(device=dev, dtype=dt).contiguous()
+                v = v if is_tensor(v) else torch.from_numpy(np.ascontiguousarray(v))
+                return v.to(device=raster.device, dtype=dt).contiguous()
 
             cols = (col(x, torch.float64), col(y, torch.float64), col(z, raster.dtype))
-            inl = None
-            if inlier_mask is not None:
-                inl = inlier_mask if hasattr(inlier_mask, "is_cuda") else torch.from_numpy(np.ascontiguousarray(inlier_mask, dtype=np.uint8))
-                inl = inl.to(device=dev, dtype=torch.uint8).contiguous()
-                if tuple(inl.shape) != tuple(raster.shape):
-                    raise ValueError("inlier_mask must have the shape of the raster")
-            torch.cuda.current_stream(dev).synchronize()
-            self._keep = (raster, cols, inl)
-            self.dtype = np.dtype(np.float32 if raster.dtype == torch.float32 else np.float64)
-            ptrs = (raster.data_ptr(), *(c.data_ptr() for c in cols), inl.data_ptr() if inl is not None else None)
-            space, n_pts, shape = _lib.DEVICE, int(cols[0].numel()), tuple(raster.shape)
         else:
-            arr = _host_raster(raster)
-            host = lambda v: v.cpu().numpy() if hasattr(v, "is_cuda") else v   # noqa: E731
+            raster = _host_raster(raster)
+            host = lambda v: v.cpu().numpy() if is_tensor(v) else v   # noqa: E731
             cols = (np.ascontiguousarray(host(x), dtype=np.float64), np.ascontiguousarray(host(y), dtype=np.float64),
-                    np.ascontiguousarray(host(z), dtype=arr.dtype))
-            inl = None if inlier_mask is None else np.ascontiguousarray(host(inlier_mask), dtype=np.uint8)
-            if inl is not None and inl.shape != arr.shape:
-                raise ValueError("inlier_mask must have the shape of the raster")
-            self._keep = (arr, cols, inl)
-            self.dtype = arr.dtype
-            ptrs = (arr.ctypes.data, *(c.ctypes.data for c in cols), inl.ctypes.data if inl is not None else None)
-            space, n_pts, shape = _lib.HOST, int(cols[0].size), arr.shape
+                    np.ascontiguousarray(host(z), dtype=raster.dtype))
+        inl = None if inlier_mask is None else _args.mask_u8(inlier_mask, raster)
+        if inl is not None and tuple(inl.shape) != tuple(raster.shape):
+            raise ValueError("inlier_mask must have the shape of the raster")
+        if is_tensor(raster):
+            _args.synchronize_torch(raster)
+        self._keep = (raster, cols, inl)
+        self.dtype = _args.np_dtype(raster)
+        space, n_pts, shape = _args.space(raster), int(cols[0].numel() if is_tensor(raster) else cols[0].size), tuple(raster.shape)
         if not (len(cols[0]) == len(cols[1]) == len(cols[2])):
             raise ValueError("the cloud's columns must have one length")
         self.shape, self.n_points, self.pts_is_ref, self.transform6 = shape, n_pts, bool(pts_is_ref), t6
@@ -190,9 +174,9 @@ class PtsPlan(_Plan):
         self.ctx.adopt(self)
         h, nv = ctypes.c_void_p(), ctypes.c_int64()
         t = np.asarray(t6, dtype=np.float64)
-        self.ctx.check(self.ctx._L.xdemhip_pts_create(self.ctx.handle, ptrs[0], ptrs[4], _lib.F32 if self.dtype == np.float32 else _lib.F64,
-                                                      shape[0], shape[1], t.ctypes.data_as(_DP), ptrs[1], ptrs[2], ptrs[3], n_pts,
-                                                      int(self.pts_is_ref), int(bool(with_nk_aux)), space, ctypes.byref(h), ctypes.byref(nv)))
+        self.ctx.check(self.ctx._L.xdemhip_pts_create(self.ctx.handle, _args.ptr(raster), _args.ptr(inl), _args.code(raster), shape[0], shape[1],
+                                                      _args.dp(t), *(_args.ptr(c) for c in cols), n_pts, int(self.pts_is_ref),
+                                                      int(bool(with_nk_aux)), space, ctypes.byref(h), ctypes.byref(nv)))
         self.handle = h
         self.n_valid = self.n_selected = int(nv.value)
 
@@ -206,7 +190,7 @@ class PtsPlan(_Plan):
         kept in cloud order (``xdemhip_pts_subsample``).  Returns their number."""
         ranks = np.ascontiguousarray(ranks, dtype=np.int64)
         k = ctypes.c_int64()
-        self.ctx.check(self.ctx._L.xdemhip_pts_subsample(self.handle, ranks.ctypes.data, int(ranks.size), _lib.HOST, ctypes.byref(k)))
+        self.ctx.check(self.ctx._L.xdemhip_pts_subsample(self.handle, _args.ptr(ranks), int(ranks.size), _lib.HOST, ctypes.byref(k)))
         self.n_selected = int(k.value)
         return self.n_selected
 
@@ -215,7 +199,7 @@ class PtsPlan(_Plan):
         idx = np.empty(self.n_selected, dtype=np.int64)
         if self.n_selected:
             cnt = ctypes.c_int64()
-            self.ctx.check(self.ctx._L.xdemhip_pts_selection(self.handle, idx.ctypes.data, ctypes.byref(cnt)))
+            self.ctx.check(self.ctx._L.xdemhip_pts_selection(self.handle, _args.ptr(idx), ctypes.byref(cnt)))
         return idx
 
     # ---- evaluations ----
@@ -228,9 +212,8 @@ class PtsPlan(_Plan):
             raise _lib.XdemHipError("no valid points")
         outs = [np.empty(k, dtype=self.dtype) for _ in range(3 if aux else 1)]
         cnt = ctypes.c_int64()
-        self.ctx.check(self.ctx._L.xdemhip_pts_shift_values(self.handle, float(shift_x), float(shift_y), outs[0].ctypes.data,
-                                                            outs[1].ctypes.data if aux else None, outs[2].ctypes.data if aux else None,
-                                                            _lib.HOST, ctypes.byref(cnt)))
+        ptrs = [_args.ptr(o) for o in outs] + [None] * (3 - len(outs))
+        self.ctx.check(self.ctx._L.xdemhip_pts_shift_values(self.handle, float(shift_x), float(shift_y), *ptrs, _lib.HOST, ctypes.byref(cnt)))
         if int(cnt.value) != k:
             raise _lib.XdemHipError(f"xdemhip_pts_shift_values returned {cnt.value} values, expected {k}")
         return tuple(outs) if aux else outs[0]
@@ -256,7 +239,7 @@ class PtsPlan(_Plan):
         decimal = int(-np.log10(np.diff(e.astype(self.dtype)).min())) + 6   # SciPy's rightmost-edge rule, from the dtype-cast edges
         self._custom_edges, self._n_custom_bins = e.astype(self.dtype), int(e.size) - 1
         if self.handle:
-            self.ctx.check(self.ctx._L.xdemhip_pts_set_bin_edges(self.handle, e.ctypes.data_as(_DP), int(e.size), decimal))
+            self.ctx.check(self.ctx._L.xdemhip_pts_set_bin_edges(self.handle, _args.dp(e), int(e.size), decimal))
 
     def set_statistic(self, bin_statistic) -> None:
         """Statistic of the aspect bins: ``np.nanmedian`` / ``np.median`` are exact selections on the device; any other callable
@@ -289,7 +272,7 @@ class PtsPlan(_Plan):
         no dh): ``xdemhip_pts_step_y``."""
         y = np.empty(self.n_selected, dtype=self.dtype)
         cnt = ctypes.c_int64()
-        self.ctx.check(self.ctx._L.xdemhip_pts_step_y(self.handle, y.ctypes.data, _lib.HOST, ctypes.byref(cnt)))
+        self.ctx.check(self.ctx._L.xdemhip_pts_step_y(self.handle, _args.ptr(y), _lib.HOST, ctypes.byref(cnt)))
         if int(cnt.value) != y.size:
             raise _lib.XdemHipError(f"xdemhip_pts_step_y returned {cnt.value} values, expected {y.size}")
         return y
@@ -301,8 +284,7 @@ class PtsPlan(_Plan):
         vshift, ymean, ystd = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
         nv = ctypes.c_int64()
         rc = self.ctx._L.xdemhip_pts_nk_step(self.handle, float(shift_x), float(shift_y), n_bins, ctypes.byref(vshift), ctypes.byref(nv),
-                                             ctypes.byref(ymean), ctypes.byref(ystd), edges.ctypes.data_as(_DP), counts.ctypes.data_as(_IP),
-                                             med.ctypes.data_as(_DP))
+                                             ctypes.byref(ymean), ctypes.byref(ystd), _args.dp(edges), _args.i64p(counts), _args.dp(med))
         if rc != _lib.OK:
             msg = self.ctx._L.xdemhip_last_error(self.ctx.handle).decode()
             if "no more valid values" in msg:
@@ -361,7 +343,7 @@ class PtsPlan(_Plan):
 def apply_matrix_pts(x, y, z, matrix, invert: bool = False, centroid=None, ctx: _lib.Context | None = None):
     """``p' = M (p - centroid) + centroid`` for the points of three columns (``_apply_matrix_pts_arr``; ``xdemhip_apply_matrix_pts``):
     float64 NumPy columns out."""
-    host = lambda v: v.cpu().numpy() if hasattr(v, "is_cuda") else v   # noqa: E731
+    host = lambda v: v.cpu().numpy() if is_tensor(v) else v   # noqa: E731
     x, y, z = (np.ascontiguousarray(host(v), dtype=np.float64) for v in (x, y, z))
     m = np.ascontiguousarray(matrix, dtype=np.float64)
     if m.shape != (4, 4):
@@ -371,9 +353,8 @@ def apply_matrix_pts(x, y, z, matrix, invert: bool = False, centroid=None, ctx: 
         return tuple(out)
     ctx = ctx or _lib.default_context()
     cen = None if centroid is None else np.ascontiguousarray([float(v) for v in centroid], dtype=np.float64)
-    ctx.check(ctx._L.xdemhip_apply_matrix_pts(ctx.handle, x.ctypes.data, y.ctypes.data, z.ctypes.data, int(x.size), m.ctypes.data_as(_DP),
-                                              cen.ctypes.data_as(_DP) if cen is not None else None, int(bool(invert)), out[0].ctypes.data,
-                                              out[1].ctypes.data, out[2].ctypes.data, _lib.HOST))
+    ctx.check(ctx._L.xdemhip_apply_matrix_pts(ctx.handle, *(_args.ptr(v) for v in (x, y, z)), int(x.size), _args.dp(m), _args.dp(cen),
+                                              int(bool(invert)), *(_args.ptr(o) for o in out), _lib.HOST))
     return tuple(out)
 
 

@@ -23,13 +23,11 @@ from typing import Any, Callable
 import numpy as np
 import scipy.optimize
 
-from . import _lib
+from . import _args, _lib
+from ._args import c_doubles
 from ._coregbase import _Plan, draw
 from .biascorr import DhPlan
-from .rigid import _c6, _iterate, _RigidStep, matrix_from_translations_rotations, solve_scaled, translations_rotations_from_matrix
-
-_DP = ctypes.POINTER(ctypes.c_double)
-_IP = ctypes.POINTER(ctypes.c_int64)
+from .rigid import _iterate, _RigidStep, matrix_from_translations_rotations, solve_scaled, translations_rotations_from_matrix
 
 METHODS = ("point-to-point", "point-to-plane")
 BAD_METHOD = "ICP method must be 'point-to-point' or 'point-to-plane'."
@@ -45,7 +43,7 @@ def icp_normals(plan: DhPlan, t6, fetch: bool = True):
     affine.py:1062-1081).  The call narrows the plan's valid mask to the pixels where the three are finite -- before any draw."""
     outs = [np.empty(plan.shape, dtype=plan.dtype) if fetch else None for _ in range(3)]
     nv = ctypes.c_int64()
-    plan.ctx.check(plan.ctx._L.xdemhip_dh_icp_normals(plan.handle, _c6(t6), *(o.ctypes.data if fetch else None for o in outs), _lib.HOST,
+    plan.ctx.check(plan.ctx._L.xdemhip_dh_icp_normals(plan.handle, c_doubles(t6), *(_args.ptr(o) for o in outs), _lib.HOST,
                                                       ctypes.byref(nv)))
     plan.n_valid = int(nv.value)
     if not plan.drawn:
@@ -70,8 +68,8 @@ class IcpCloud(_Plan):
         its axes (``_standardize_epc``, affine.py:296-328): ``.centroid``, ``.std_fac``."""
         h, cnt = ctypes.c_void_p(), ctypes.c_int64()
         cen, fac = np.empty(3, dtype=np.float64), ctypes.c_double()
-        plan.ctx.check(plan.ctx._L.xdemhip_icp_create_plan(plan.handle, _c6(t6), int(bool(with_normals)), int(bool(standardize)), ctypes.byref(h),
-                                                           cen.ctypes.data_as(_DP), ctypes.byref(fac), ctypes.byref(cnt)))
+        plan.ctx.check(plan.ctx._L.xdemhip_icp_create_plan(plan.handle, c_doubles(t6), int(bool(with_normals)), int(bool(standardize)), ctypes.byref(h),
+                                                           _args.dp(cen), ctypes.byref(fac), ctypes.byref(cnt)))
         out = cls(plan.ctx, h, cnt.value, cnt.value, with_normals)
         out.centroid, out.std_fac = (float(cen[0]), float(cen[1]), float(cen[2])), float(fac.value)
         return out
@@ -85,30 +83,29 @@ class IcpCloud(_Plan):
             raise ValueError("normals must have the shape of ref_points")
         ctx = ctx or _lib.default_context()
         h = ctypes.c_void_p()
-        ctx.check(ctx._L.xdemhip_icp_create_points(ctx.handle, ref.ctypes.data_as(_DP), ref.shape[1], qry.ctypes.data_as(_DP), qry.shape[1],
-                                                   None if nrm is None else nrm.ctypes.data_as(_DP), ctypes.byref(h)))
+        ctx.check(ctx._L.xdemhip_icp_create_points(ctx.handle, _args.dp(ref), ref.shape[1], _args.dp(qry), qry.shape[1], _args.dp(nrm),
+                                                   ctypes.byref(h)))
         return cls(ctx, h, ref.shape[1], qry.shape[1], nrm is not None)
 
     def cloud(self) -> np.ndarray:
         """(7, n): x, y, ref, tba, nx, ny, nz as standardised (clouds made from a plan)."""
         out = np.empty((7, self.n), dtype=np.float64)
-        self.ctx.check(self.ctx._L.xdemhip_icp_cloud(self.handle, out.ctypes.data_as(_DP)))
+        self.ctx.check(self.ctx._L.xdemhip_icp_cloud(self.handle, _args.dp(out)))
         return out
 
     def grid(self) -> tuple[float, float, float, int, int]:
         """(x0, y0, h, columns, rows) of the search grid over the reference cloud (``xdemhip_icp_grid``)."""
         f, n = np.empty(3, dtype=np.float64), np.empty(2, dtype=np.int64)
-        self.ctx.check(self.ctx._L.xdemhip_icp_grid(self.handle, f.ctypes.data_as(_DP), n.ctypes.data_as(_IP)))
+        self.ctx.check(self.ctx._L.xdemhip_icp_grid(self.handle, _args.dp(f), _args.i64p(n)))
         return float(f[0]), float(f[1]), float(f[2]), int(n[0]), int(n[1])
 
     def query(self, matrix=None, fetch: bool = True):
         """Nearest reference point of every query point moved by ``matrix``: ``(dist, ind)`` as ``KDTree.query(k=1)`` returns them
         (``xdemhip_icp_query``); with ``fetch=False`` the result stays on the device for ``pairs``."""
-        m16 = None if matrix is None else _c6(np.asarray(matrix, dtype=np.float64).ravel())
+        m16 = None if matrix is None else c_doubles(np.asarray(matrix, dtype=np.float64).ravel())
         dist = np.empty(self.m, dtype=np.float64) if fetch else None
         ind = np.empty(self.m, dtype=np.int64) if fetch else None
-        self.ctx.check(self.ctx._L.xdemhip_icp_query(self.handle, m16, ind.ctypes.data_as(_IP) if fetch else None,
-                                                     dist.ctypes.data_as(_DP) if fetch else None))
+        self.ctx.check(self.ctx._L.xdemhip_icp_query(self.handle, m16, _args.i64p(ind), _args.dp(dist)))
         return (dist, ind) if fetch else None
 
     def set_pairs(self, ind, dist) -> None:
@@ -116,7 +113,7 @@ class IcpCloud(_Plan):
         ind, dist = np.ascontiguousarray(ind, dtype=np.int64), np.ascontiguousarray(dist, dtype=np.float64)
         if ind.shape != (self.m,) or dist.shape != (self.m,):
             raise ValueError("ind and dist must hold one entry per query point")
-        self.ctx.check(self.ctx._L.xdemhip_icp_set_pairs(self.handle, ind.ctypes.data_as(_IP), dist.ctypes.data_as(_DP)))
+        self.ctx.check(self.ctx._L.xdemhip_icp_set_pairs(self.handle, _args.i64p(ind), _args.dp(dist)))
 
     def pairs(self, picky: bool, fetch: bool = False):
         """Select the pairs of the fit (``xdemhip_icp_pairs``): their number, and with ``fetch`` the kept (query, reference) indexes."""
@@ -125,7 +122,7 @@ class IcpCloud(_Plan):
             self.ctx.check(self.ctx._L.xdemhip_icp_pairs(self.handle, int(bool(picky)), ctypes.byref(k), None, None))
             return int(k.value)
         q, r = np.empty(self.m, dtype=np.int64), np.empty(self.m, dtype=np.int64)
-        self.ctx.check(self.ctx._L.xdemhip_icp_pairs(self.handle, int(bool(picky)), ctypes.byref(k), q.ctypes.data_as(_IP), r.ctypes.data_as(_IP)))
+        self.ctx.check(self.ctx._L.xdemhip_icp_pairs(self.handle, int(bool(picky)), ctypes.byref(k), _args.i64p(q), _args.i64p(r)))
         return int(k.value), q[: k.value].copy(), r[: k.value].copy()
 
     def sums(self, step, method: str) -> tuple[np.ndarray, int]:
@@ -133,14 +130,14 @@ class IcpCloud(_Plan):
         nine moments of the moved points (x^2, y^2, z^2, xy, xz, yz, x, y, z)."""
         s = np.empty(N_SUMS, dtype=np.float64)
         cnt = ctypes.c_int64()
-        self.ctx.check(self.ctx._L.xdemhip_icp_sums(self.handle, _c6(np.asarray(step, dtype=np.float64).ravel()), METHODS.index(method),
-                                                    s.ctypes.data_as(_DP), ctypes.byref(cnt)))
+        self.ctx.check(self.ctx._L.xdemhip_icp_sums(self.handle, c_doubles(np.asarray(step, dtype=np.float64).ravel()), METHODS.index(method),
+                                                    _args.dp(s), ctypes.byref(cnt)))
         return s, int(cnt.value)
 
     def values(self, k: int) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
         """``(ref, trans, norms)``, each (3, k) float64: the kept pairs as upstream hands them to ``_icp_fit`` (``xdemhip_icp_values``)."""
         out = np.empty((9, k), dtype=np.float64)
-        self.ctx.check(self.ctx._L.xdemhip_icp_values(self.handle, out.ctypes.data_as(_DP)))
+        self.ctx.check(self.ctx._L.xdemhip_icp_values(self.handle, _args.dp(out)))
         return out[:3], out[3:6], out[6:]
 
 

@@ -29,11 +29,10 @@ from typing import Any, Callable
 import numpy as np
 import scipy.optimize
 
-from . import _lib
+from . import _args, _lib
+from ._args import c_doubles
 from ._coregbase import _Step, _with_transform, apply_translation, draw
-from .biascorr import DhPlan, _check_weights, _host_array
-
-_DP = ctypes.POINTER(ctypes.c_double)
+from .biascorr import DhPlan, _check_weights
 
 LZD_NO_VALID = ("The subsample contains no more valid values. This can happen if the affine transformation to "
                 "correct is larger than the data extent, or if the algorithm diverged. To ensure all possible points can "
@@ -128,10 +127,6 @@ def _transform6(transform, resolution, shape) -> tuple[float, ...]:
     return t
 
 
-def _c6(t) -> Any:
-    return np.ascontiguousarray(t, dtype=np.float64).ctypes.data_as(_DP)
-
-
 # ---- apply_matrix -------------------------------------------------------------------------------------------------------------------
 def apply_matrix(elev, matrix, invert: bool = False, centroid=None, resample: bool = True, resampling: str = "linear", transform=None,
                  z_name: str = "z", *, ctx: _lib.Context | None = None):
@@ -148,11 +143,9 @@ def apply_matrix(elev, matrix, invert: bool = False, centroid=None, resample: bo
     matrix = np.asarray(matrix, dtype=np.float64)
     if invert:
         matrix = invert_matrix(matrix)
-    arr = np.ascontiguousarray(_host_array(elev))
+    arr = _args.host_float(elev)
     if arr.ndim != 2:
         raise ValueError("elev must be a 2D array")
-    if arr.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
-        arr = arr.astype(np.float32)
     if np.count_nonzero(np.isfinite(arr)) == 0:
         raise ValueError("Input DEM has all nans.")
     dx, dy, dz = (float(v) for v in matrix[:3, 3])
@@ -174,9 +167,9 @@ def apply_matrix(elev, matrix, invert: bool = False, centroid=None, resample: bo
         raise ValueError("the DEM must be at least 2 x 2 pixels for a regrid")
     ctx = ctx or _lib.default_context()
     out = np.empty_like(arr)
-    cen = None if centroid is None else _c6([float(v) for v in centroid])
-    ctx.check(ctx._L.xdemhip_apply_matrix_rst(ctx.handle, arr.ctypes.data, _lib.F32 if arr.dtype == np.float32 else _lib.F64, arr.shape[0],
-                                              arr.shape[1], _c6(t6), _c6(matrix.ravel()), cen, out.ctypes.data, _lib.HOST))
+    cen = None if centroid is None else c_doubles([float(v) for v in centroid])
+    ctx.check(ctx._L.xdemhip_apply_matrix_rst(ctx.handle, _args.ptr(arr), _args.code(arr), arr.shape[0], arr.shape[1], c_doubles(t6),
+                                              c_doubles(matrix.ravel()), cen, _args.ptr(out), _lib.HOST))
     return out, transform
 
 
@@ -184,7 +177,7 @@ def apply_matrix(elev, matrix, invert: bool = False, centroid=None, resample: bo
 def lzd_gradients(plan: DhPlan, t6) -> tuple[np.ndarray, np.ndarray]:
     """(gradx, grady) = (gradient_x / res_x, -gradient_y / res_y) of ``np.gradient(ref)`` in the plan's dtype (``xdemhip_dh_lzd_gradients``)."""
     gx, gy = np.empty(plan.shape, dtype=plan.dtype), np.empty(plan.shape, dtype=plan.dtype)
-    plan.ctx.check(plan.ctx._L.xdemhip_dh_lzd_gradients(plan.handle, _c6(t6), gx.ctypes.data, gy.ctypes.data, _lib.HOST))
+    plan.ctx.check(plan.ctx._L.xdemhip_dh_lzd_gradients(plan.handle, c_doubles(t6), _args.ptr(gx), _args.ptr(gy), _lib.HOST))
     return gx, gy
 
 
@@ -192,7 +185,7 @@ def lzd_centroid(plan: DhPlan, t6) -> tuple[tuple[float, float, float], int]:
     """((mean x, mean y, mean tba), count) over the plan's selected pixels (``xdemhip_dh_lzd_centroid``)."""
     c = np.empty(3, dtype=np.float64)
     cnt = ctypes.c_int64()
-    plan.ctx.check(plan.ctx._L.xdemhip_dh_lzd_centroid(plan.handle, _c6(t6), c.ctypes.data_as(_DP), ctypes.byref(cnt)))
+    plan.ctx.check(plan.ctx._L.xdemhip_dh_lzd_centroid(plan.handle, c_doubles(t6), _args.dp(c), ctypes.byref(cnt)))
     return (float(c[0]), float(c[1]), float(c[2])), int(cnt.value)
 
 
@@ -201,8 +194,8 @@ def lzd_normal(plan: DhPlan, t6, matrix, centroid) -> tuple[np.ndarray, int]:
     and sum dh over the pixels that stay valid under ``matrix``."""
     s = np.empty(29, dtype=np.float64)
     cnt = ctypes.c_int64()
-    plan.ctx.check(plan.ctx._L.xdemhip_dh_lzd_normal(plan.handle, _c6(t6), _c6(np.asarray(matrix, dtype=np.float64).ravel()), _c6(centroid),
-                                                     s.ctypes.data_as(_DP), ctypes.byref(cnt)))
+    plan.ctx.check(plan.ctx._L.xdemhip_dh_lzd_normal(plan.handle, c_doubles(t6), c_doubles(np.asarray(matrix, dtype=np.float64).ravel()), c_doubles(centroid),
+                                                     _args.dp(s), ctypes.byref(cnt)))
     return s, int(cnt.value)
 
 
@@ -212,8 +205,8 @@ def lzd_values(plan: DhPlan, t6, matrix, centroid) -> np.ndarray:
     n = plan.n_selected
     out = np.empty((6, max(n, 1)), dtype=np.float64)
     cnt = ctypes.c_int64()
-    plan.ctx.check(plan.ctx._L.xdemhip_dh_lzd_values(plan.handle, _c6(t6), _c6(np.asarray(matrix, dtype=np.float64).ravel()), _c6(centroid),
-                                                     out.ctypes.data_as(_DP), ctypes.byref(cnt)))
+    plan.ctx.check(plan.ctx._L.xdemhip_dh_lzd_values(plan.handle, c_doubles(t6), c_doubles(np.asarray(matrix, dtype=np.float64).ravel()), c_doubles(centroid),
+                                                     _args.dp(out), ctypes.byref(cnt)))
     return np.ascontiguousarray(out[:, : int(cnt.value)])
 
 
@@ -322,7 +315,7 @@ class _RigidStep(_Step):
                                       f" only available for translation coregistrations such as NuthKaab.")
         if resampling not in ("bilinear", "linear"):
             raise NotImplementedError(f"resampling={resampling!r}: only \"linear\" is implemented for matrices with a rotation.")
-        arr = _host_array(elev)
+        arr = _args.nan_filled(elev)
         t6 = _transform6(transform, resolution, np.shape(arr))
         out, _ = apply_matrix(arr, self.to_matrix(), centroid=self.meta["outputs"]["affine"]["centroid"], resample=True, resampling="linear",
                               transform=t6)

@@ -26,7 +26,8 @@ from typing import Any, Callable, TypedDict
 
 import numpy as np
 
-from . import _lib
+from . import _args, _lib
+from ._args import dp, i64p, ptr
 
 _ESTIMATORS = ("matheron", "cressie", "dowd")
 
@@ -64,8 +65,7 @@ def _count_finite(values: np.ndarray, want_mask: bool = False) -> tuple[int, np.
         L = _lib.host_library()
         n = ctypes.c_int64()
         mask = np.empty(values.shape, dtype=np.bool_) if want_mask else None
-        rc = L.xdemhip_host_count_finite(values.ctypes.data, _lib.F32 if values.dtype == np.float32 else _lib.F64, int(values.size),
-                                         _host_threads(), ctypes.byref(n), None if mask is None else mask.ctypes.data)
+        rc = L.xdemhip_host_count_finite(ptr(values), _args.code(values), int(values.size), _host_threads(), ctypes.byref(n), ptr(mask))
         if rc != 0:
             raise _lib.XdemHipError(f"xdemhip_host_count_finite: status {rc}")
         return int(n.value), mask
@@ -132,10 +132,8 @@ def _native_equidistant_blocks(values2d: np.ndarray, valid2d, gsd: float, centre
     idx = np.empty((runs, nr, samples), dtype=np.int64)
     cnt = np.empty((runs, nr), dtype=np.int64)
     vmask = None if valid2d is None else np.ascontiguousarray(valid2d, dtype=np.bool_).view(np.uint8)
-    i64p, dp = ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_double)
-    rc = L.xdemhip_host_ring_sample(None if vmask is None else vmask.ctypes.data, ny, nx, float(gsd), runs, cx.ctypes.data_as(i64p),
-                                    cy.ctypes.data_as(i64p), nr, lo.ctypes.data_as(dp), hi.ctypes.data_as(dp), int(samples),
-                                    ctypes.c_uint64(seed & (2**64 - 1)), thr, idx.ctypes.data_as(i64p), cnt.ctypes.data_as(i64p))
+    rc = L.xdemhip_host_ring_sample(ptr(vmask), ny, nx, float(gsd), runs, i64p(cx), i64p(cy), nr, dp(lo), dp(hi), int(samples),
+                                    ctypes.c_uint64(seed & (2**64 - 1)), thr, i64p(idx), i64p(cnt))
     if rc != 0:
         raise _lib.XdemHipError(f"xdemhip_host_ring_sample: status {rc}")
     # runs whose centre disk or rings came out empty are dropped (as the NumPy form drops them)
@@ -146,14 +144,13 @@ def _native_equidistant_blocks(values2d: np.ndarray, valid2d, gsd: float, centre
     a_off = np.concatenate(([0], np.cumsum(na[keep]))).astype(np.int64)
     b_off = np.concatenate(([0], np.cumsum(nb[keep]))).astype(np.int64)
     vals = np.ascontiguousarray(values2d)
-    dt = _lib.F32 if vals.dtype == np.float32 else _lib.F64
+    dt = _args.code(vals)
 
     def gather(off, flat):   # -> (x, y, v) in the order drawn, (x, y, v) in Morton order
         outs = [np.empty(flat.size, dtype=np.float64), np.empty(flat.size, dtype=np.float64), np.empty(flat.size, dtype=vals.dtype),
                 np.empty(flat.size, dtype=np.float64), np.empty(flat.size, dtype=np.float64), np.empty(flat.size, dtype=vals.dtype)]
-        rc_ = L.xdemhip_host_gather_points(vals.ctypes.data, dt, nx, float(gsd), int(off.size - 1), off.ctypes.data_as(i64p),
-                                           flat.ctypes.data_as(i64p), thr, outs[0].ctypes.data_as(dp), outs[1].ctypes.data_as(dp),
-                                           outs[2].ctypes.data, outs[3].ctypes.data_as(dp), outs[4].ctypes.data_as(dp), outs[5].ctypes.data)
+        rc_ = L.xdemhip_host_gather_points(ptr(vals), dt, nx, float(gsd), int(off.size - 1), i64p(off), i64p(flat), thr, dp(outs[0]),
+                                           dp(outs[1]), ptr(outs[2]), dp(outs[3]), dp(outs[4]), ptr(outs[5]))
         if rc_ != 0:
             raise _lib.XdemHipError(f"xdemhip_host_gather_points: status {rc_}")
         return outs
@@ -170,7 +167,7 @@ def _native_equidistant_blocks(values2d: np.ndarray, valid2d, gsd: float, centre
     return out
 
 
-class PairSet:
+class PairSet(_lib._Plan):
     """Device-resident pair blocks + lag edges (``xdemhip_pairs``).  ``blocks`` is a list of (ax, ay, av, bx, by, bv)
     (every a with every b) or (ax, ay, av) (all i < j)."""
 
@@ -215,12 +212,11 @@ class PairSet:
                 keep = [off(0), cat(bl, 0, np.float64), cat(bl, 1, np.float64), cat(bl, 2, vdt)]
                 if not pd:
                     keep += [off(3), cat(bl, 3, np.float64), cat(bl, 4, np.float64), cat(bl, 5, vdt)]
-            p = [a.ctypes.data for a in keep] + ([None] * 4 if pd else [])
+            p = [ptr(a) for a in keep] + ([None] * 4 if pd else [])
             h, n_pairs = ctypes.c_void_p(), ctypes.c_int64()
             self.ctx.check(self.ctx._L.xdemhip_pairs_create(
                 self.ctx.handle, len(bl), p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7],
-                _lib.F32 if vdt == np.float32 else _lib.F64, self.edges.ctypes.data, self.nb, _lib.HOST, ctypes.byref(h),
-                ctypes.byref(n_pairs)))
+                _args.code(vdt), ptr(self.edges), self.nb, _lib.HOST, ctypes.byref(h), ctypes.byref(n_pairs)))
             return h, int(n_pairs.value)
 
         self.handle = self.handle_sel = None
@@ -267,22 +263,18 @@ class PairSet:
     def sums(self, kind: int):
         s = np.zeros(self.nb, dtype=np.float64)
         c = np.zeros(self.nb, dtype=np.int64)
-        self.ctx.check(self.ctx._L.xdemhip_pairs_sums(self.handle, kind, s.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                                                     c.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        self.ctx.check(self.ctx._L.xdemhip_pairs_sums(self.handle, kind, dp(s), i64p(c)))
         return s, c
 
     def hist(self, shift: int, first: bool, prefix: np.ndarray | None) -> np.ndarray:
         h = np.zeros((self.nb, 256), dtype=np.uint64)
-        u64p = ctypes.POINTER(ctypes.c_uint64)
-        pp = np.ascontiguousarray(prefix, dtype=np.uint64).ctypes.data_as(u64p) if prefix is not None else None
-        self.ctx.check(self.ctx._L.xdemhip_pairs_hist(self.handle_sel, shift, int(first), pp, h.ctypes.data_as(u64p)))
+        pp = _args.u64p(np.ascontiguousarray(prefix, dtype=np.uint64)) if prefix is not None else None
+        self.ctx.check(self.ctx._L.xdemhip_pairs_hist(self.handle_sel, shift, int(first), pp, _args.u64p(h)))
         return h
 
     def succ(self, key: np.ndarray) -> np.ndarray:
         out = np.zeros(self.nb, dtype=np.uint64)
-        u64p = ctypes.POINTER(ctypes.c_uint64)
-        self.ctx.check(self.ctx._L.xdemhip_pairs_succ(self.handle_sel, np.ascontiguousarray(key, dtype=np.uint64).ctypes.data_as(u64p),
-                                                     out.ctypes.data_as(u64p)))
+        self.ctx.check(self.ctx._L.xdemhip_pairs_succ(self.handle_sel, _args.u64p(np.ascontiguousarray(key, dtype=np.uint64)), _args.u64p(out)))
         return out
 
     def close(self) -> None:
@@ -306,12 +298,6 @@ class PairSet:
         if hs and (not h or hs.value != h.value):
             self.ctx._L.xdemhip_pairs_destroy(hs)
         self.handle = self.handle_sel = None
-
-    def __del__(self):  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _key_to_value(key: np.ndarray, bits: int) -> np.ndarray:
@@ -348,8 +334,7 @@ def class_medians(pairs: PairSet, group=None):
     try:
         counts = np.zeros(pairs.nb, dtype=np.int64)
         med = np.full(pairs.nb, np.nan)
-        ctx.check(ctx._L.xdemhip_pairs_medians(pairs.handle_sel, counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
-                                               med.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
+        ctx.check(ctx._L.xdemhip_pairs_medians(pairs.handle_sel, i64p(counts), dp(med)))
     finally:
         if hooked:
             ctx.set_allreduce(None)
@@ -1056,12 +1041,8 @@ class _DeviceColumn:
     ``size``) without the values leaving the device; ``host()`` fetches them once if a host-evaluated statistic needs them."""
 
     def __init__(self, tensor):
-        import torch
-
-        if not (tensor.is_cuda and tensor.dim() == 1 and tensor.is_contiguous() and tensor.dtype in (torch.float32, torch.float64)):
-            raise ValueError("device columns must be contiguous 1-D float32 / float64 CUDA tensors")
-        self.tensor = tensor
-        self.dtype = np.dtype(np.float32 if tensor.dtype == torch.float32 else np.float64)
+        self.tensor = _args.device_float(tensor, "device columns must be contiguous 1-D float32 / float64 CUDA tensors", ndim=1)
+        self.dtype = _args.np_dtype(tensor)
         self.size = int(tensor.numel())
         self._host = None
 
@@ -1071,13 +1052,15 @@ class _DeviceColumn:
         return self._host
 
 
-class BinStatsPlan:
+class BinStatsPlan(_lib._Plan):
     """Device-resident values + explanatory variables of one ``nd_binning`` call (``xdemhip_binstats``).  ``values`` / ``list_var``:
     NumPy arrays (uploaded), or 1-D CUDA tensors of one length (read in place and kept alive by the plan: the columns a dh plan
     gathers on the device, ``DhPlan.var_columns``)."""
 
+    _DESTROY = "xdemhip_binstats_destroy"
+
     def __init__(self, values, list_var: list, ctx: _lib.Context | None = None):
-        device = hasattr(values, "is_cuda")
+        device = _args.is_tensor(values)
         self.ctx = ctx or (_lib.default_context(values.device.index) if device else _lib.default_context())
         self.ctx.adopt(self)
         L = self.ctx._L
@@ -1089,40 +1072,32 @@ class BinStatsPlan:
             return np.ascontiguousarray(a)
 
         if device:
-            if not all(hasattr(v, "is_cuda") for v in list_var):
+            if not all(_args.is_tensor(v) for v in list_var):
                 raise ValueError("values on the device need every explanatory variable on the device")
-            import torch
-
-            torch.cuda.current_stream(values.device).synchronize()   # (the library reads the columns on the context's stream)
+            _args.synchronize_torch(values)   # (the library reads the columns on the context's stream)
             self._dev_values = _DeviceColumn(values)
             self.vars = [_DeviceColumn(v) for v in list_var]
-            n = self._dev_values.size
-            space = _lib.DEVICE
-            ptr = lambda a: a.tensor.data_ptr()  # noqa: E731
         else:
             self._dev_values = None
             self._values = prep(values)
             self.vars = [prep(v) for v in list_var]
-            n = self._values.size
-            space = _lib.HOST
-            ptr = lambda a: a.ctypes.data  # noqa: E731
         first = self._dev_values if device else self._values
+        n, space = first.size, _args.space(values)
         if any(v.size != n for v in self.vars):
             raise ValueError("values and explanatory variables must have the same number of elements")
         self.size = n
         h = ctypes.c_void_p()
-        code = lambda a: _lib.F32 if a.dtype == np.float32 else _lib.F64  # noqa: E731
-        self.ctx.check(L.xdemhip_binstats_create(self.ctx.handle, ptr(first), code(first), n, space, ctypes.byref(h)))
+        data = lambda a: getattr(a, "tensor", a)  # noqa: E731  (the array or tensor of a column)
+        self.ctx.check(L.xdemhip_binstats_create(self.ctx.handle, ptr(data(first)), _args.code(first), n, space, ctypes.byref(h)))
         self.handle = h
         for v in self.vars:
-            rc = L.xdemhip_binstats_add_var(self.handle, ptr(v), code(v), space)
+            rc = L.xdemhip_binstats_add_var(self.handle, ptr(data(v)), _args.code(v), space)
             if rc < 0:
                 self.ctx.check(rc)
         nv = ctypes.c_int64()
         k = max(len(self.vars), 1)
         vmin, vmax = np.empty(k), np.empty(k)
-        dp = ctypes.POINTER(ctypes.c_double)
-        self.ctx.check(L.xdemhip_binstats_finalize(self.handle, ctypes.byref(nv), vmin.ctypes.data_as(dp), vmax.ctypes.data_as(dp)))
+        self.ctx.check(L.xdemhip_binstats_finalize(self.handle, ctypes.byref(nv), dp(vmin), dp(vmax)))
         self.n_valid = int(nv.value)
         self.var_min, self.var_max = vmin, vmax
 
@@ -1143,14 +1118,12 @@ class BinStatsPlan:
         counts = np.zeros(nb, np.int64)
         med = np.full(nb, np.nan)
         nm = np.full(nb, np.nan)
-        ip, dp, lp = ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)
         ids = (ctypes.c_int * len(var_ids))(*var_ids)
         ne = (ctypes.c_int * len(var_ids))(*[len(e) for e in edges])
         dec = (ctypes.c_int * len(var_ids))(*decimals)
         if self.n_valid > 0:
             self.ctx.check(self.ctx._L.xdemhip_binstats_run(
-                self.handle, len(var_ids), ids, flat.ctypes.data_as(dp), ne, dec, _lib.F32 if sdt == np.float32 else _lib.F64,
-                int(want_nmad), float(nfact), counts.ctypes.data_as(lp), med.ctypes.data_as(dp), nm.ctypes.data_as(dp)))
+                self.handle, len(var_ids), ids, dp(flat), ne, dec, _args.code(sdt), int(want_nmad), float(nfact), i64p(counts), dp(med), dp(nm)))
         return counts.reshape(shape), med.reshape(shape), (nm.reshape(shape) if want_nmad else None), edges
 
     def bin_numbers(self) -> np.ndarray:
@@ -1158,22 +1131,10 @@ class BinStatsPlan:
         finiteness filter or in no bin: for statistics evaluated on the host (``xdemhip_binstats_bin_numbers``)."""
         out = np.empty(self.size, dtype=np.uint16)
         if self.n_valid > 0:
-            self.ctx.check(self.ctx._L.xdemhip_binstats_bin_numbers(self.handle, out.ctypes.data))
+            self.ctx.check(self.ctx._L.xdemhip_binstats_bin_numbers(self.handle, ptr(out)))
         else:
             out[:] = 0xFFFF
         return out
-
-    def close(self) -> None:
-        if getattr(self, "handle", None):
-            if getattr(self.ctx, "handle", None):
-                self.ctx._L.xdemhip_binstats_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def nd_binning(values, list_var, list_var_names, list_var_bins=None, statistics=("count", np.nanmedian, nmad),
@@ -1218,7 +1179,7 @@ def nd_binning(values, list_var, list_var_names, list_var_bins=None, statistics=
         kinds.append(_GPU_STATS[name] if on_device else None)
     want_nmad = "nmad" in kinds
 
-    if hasattr(values, "is_cuda"):   # device columns (a dh plan's gather): binned where they are
+    if _args.is_tensor(values):   # device columns (a dh plan's gather): binned where they are
         plan = BinStatsPlan(values, list(list_var), ctx)
     else:
         plan = BinStatsPlan(np.asarray(values), [np.asarray(v) for v in list_var], ctx)
@@ -1308,13 +1269,11 @@ class GridInterpolant:
             return out.reshape(shape)
         ctx = self.ctx or _lib.default_context()
         nd = len(cols)
-        ptrs = (ctypes.c_void_p * nd)(*[c.ctypes.data for c in cols])
-        dts = (ctypes.c_int * nd)(*[_lib.F32 if c.dtype == np.float32 else _lib.F64 for c in cols])
+        ptrs = (ctypes.c_void_p * nd)(*[ptr(c) for c in cols])
+        dts = (ctypes.c_int * nd)(*[_args.code(c) for c in cols])
         na = (ctypes.c_int * nd)(*[len(a) for a in self.grid])
         axes = np.concatenate(self.grid)
-        dp = ctypes.POINTER(ctypes.c_double)
-        ctx.check(ctx._L.xdemhip_interp_grid_linear(ctx.handle, nd, axes.ctypes.data_as(dp), na, self.values.ctypes.data_as(dp), ptrs,
-                                                    dts, n, self.scale, out.ctypes.data_as(dp), _lib.HOST))
+        ctx.check(ctx._L.xdemhip_interp_grid_linear(ctx.handle, nd, dp(axes), na, dp(self.values), ptrs, dts, n, self.scale, dp(out), _lib.HOST))
         return out.reshape(shape)
 
 
@@ -1325,7 +1284,7 @@ def nmad_device(values: np.ndarray, nfact: float = 1.4826, abs_limit: float = np
         v = v.astype(np.float64)
     ctx = ctx or _lib.default_context()
     med, nm, cnt = ctypes.c_double(), ctypes.c_double(), ctypes.c_int64()
-    ctx.check(ctx._L.xdemhip_nmad(ctx.handle, v.ctypes.data, _lib.F32 if v.dtype == np.float32 else _lib.F64, v.size, float(nfact),
+    ctx.check(ctx._L.xdemhip_nmad(ctx.handle, ptr(v), _args.code(v), v.size, float(nfact),
                                   float(abs_limit), _lib.HOST, ctypes.byref(med), ctypes.byref(nm), ctypes.byref(cnt)))
     return med.value, nm.value, int(cnt.value)
 
@@ -1453,15 +1412,13 @@ def get_perbin_nd_binning(df, list_var, list_var_names, statistic=np.nanmedian, 
     if table is None or out.size == 0:
         return out.reshape(shape)
     ctx = ctx or _lib.default_context()
-    ptrs = (ctypes.c_void_p * n_var)(*[a.ctypes.data for a in arrays])
-    dts = (ctypes.c_int * n_var)(*[_lib.F32 if a.dtype == np.float32 else _lib.F64 for a in arrays])
+    ptrs = (ctypes.c_void_p * n_var)(*[ptr(a) for a in arrays])
+    dts = (ctypes.c_int * n_var)(*[_args.code(a) for a in arrays])
     nint = (ctypes.c_int * n_var)(*counts)
     missing = ctypes.c_int64()
-    dp = ctypes.POINTER(ctypes.c_double)
     with ctx.call_lock:
-        rc = ctx._L.xdemhip_perbin_lookup(ctx.handle, ptrs, dts, n_var, out.size, nint, left.ctypes.data_as(dp), right.ctypes.data_as(dp),
-                                          table.ctypes.data_as(dp), decided.ctypes.data_as(ctypes.c_char_p), 1 if disjoint else 0,
-                                          out.ctypes.data, ctypes.byref(missing), _lib.HOST)
+        rc = ctx._L.xdemhip_perbin_lookup(ctx.handle, ptrs, dts, n_var, out.size, nint, dp(left), dp(right), dp(table), _args.chars(decided),
+                                          1 if disjoint else 0, ptr(out), ctypes.byref(missing), _lib.HOST)
     ctx.check(rc)
     if missing.value:
         if min_count is None and count_col is not None:
@@ -1824,7 +1781,6 @@ def _cov_double_sum(coords_a, errors_a, coords_b, errors_b, params_variogram_mod
         if n not in _COV_MODEL_ID:
             raise NotImplementedError(f"Variogram model '{n}' is not available on the HIP engine (no modified Bessel function there).")
     ctx = ctx or _lib.default_context()
-    dp = ctypes.POINTER(ctypes.c_double)
 
     def col(a, k=None):
         return np.ascontiguousarray(np.asarray(a, dtype=np.float64) if k is None else np.asarray(a, dtype=np.float64)[:, k])
@@ -1845,9 +1801,8 @@ def _cov_double_sum(coords_a, errors_a, coords_b, errors_b, params_variogram_mod
         sm = np.asarray(params_variogram_model["smooth"].values, dtype=np.float64)
         smooth = np.where(np.isfinite(sm), sm, 1.0)
     out = ctypes.c_double()
-    ptr = lambda a: None if a is None else a.ctypes.data_as(dp)  # noqa: E731
-    ctx.check(ctx._L.xdemhip_cov_double_sum(ctx.handle, ptr(ax), ptr(ay), ptr(ae), ax.size, ptr(bx), ptr(by), ptr(be), nb, k, types,
-                                            ptr(rng_), ptr(sil), ptr(np.ascontiguousarray(smooth)), ctypes.byref(out), _lib.HOST))
+    ctx.check(ctx._L.xdemhip_cov_double_sum(ctx.handle, dp(ax), dp(ay), dp(ae), ax.size, dp(bx), dp(by), dp(be), nb, k, types,
+                                            dp(rng_), dp(sil), dp(np.ascontiguousarray(smooth)), ctypes.byref(out), _lib.HOST))
     return float(out.value)
 
 
@@ -2024,33 +1979,29 @@ def convolution(imgs: np.ndarray, filters: np.ndarray, method: str = "scipy", ct
         raise ValueError(f"filters must have three dimensions (n_M, M1, M2), got shape {filt.shape}")
     n_f, m1, m2 = filt.shape
     ctx = ctx or _lib.default_context()
-    dp = ctypes.POINTER(ctypes.c_double)
-    is_tensor = type(imgs).__module__.startswith("torch")
-    if is_tensor:
+    device = _args.is_tensor(imgs)
+    if device:
         import torch
 
         t = imgs.contiguous()
         if t.dim() != 3 or t.dtype not in (torch.float32, torch.float64) or not t.is_cuda:
             raise TypeError("convolution: a device tensor must be a float32 / float64 CUDA tensor of shape (n_N, N1, N2)")
         out = torch.empty((t.shape[0], n_f, t.shape[1], t.shape[2]), dtype=torch.float64, device=t.device)
-        with ctx.call_lock:
-            ctx.set_stream(torch.cuda.current_stream(t.device).cuda_stream)
-            rc = ctx._L.xdemhip_convolution(ctx.handle, t.data_ptr(), _lib.F32 if t.dtype == torch.float32 else _lib.F64, t.shape[0],
-                                            t.shape[1], t.shape[2], filt.ctypes.data_as(dp), n_f, m1, m2, code, out.data_ptr(), _lib.DEVICE)
-        ctx.check(rc)
-        return out
-    arr = np.ascontiguousarray(imgs)
-    if arr.ndim != 3:
-        raise ValueError(f"imgs must have three dimensions (n_N, N1, N2), got shape {arr.shape}")
-    if arr.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
-        raise TypeError(f"convolution: images must be float32 or float64, got {arr.dtype} (with cval=nan SciPy's result for other "
-                        "dtypes is a C cast of NaN; convert the images first)")
-    out = np.empty((arr.shape[0], n_f, arr.shape[1], arr.shape[2]), dtype=np.float64)
-    if out.size == 0:
-        return out
+    else:
+        t = np.ascontiguousarray(imgs)
+        if t.ndim != 3:
+            raise ValueError(f"imgs must have three dimensions (n_N, N1, N2), got shape {t.shape}")
+        if t.dtype not in _args.FLOATS:
+            raise TypeError(f"convolution: images must be float32 or float64, got {t.dtype} (with cval=nan SciPy's result for other "
+                            "dtypes is a C cast of NaN; convert the images first)")
+        out = np.empty((t.shape[0], n_f, t.shape[1], t.shape[2]), dtype=np.float64)
+        if out.size == 0:
+            return out
     with ctx.call_lock:
-        rc = ctx._L.xdemhip_convolution(ctx.handle, arr.ctypes.data, _lib.F32 if arr.dtype == np.float32 else _lib.F64, arr.shape[0],
-                                        arr.shape[1], arr.shape[2], filt.ctypes.data_as(dp), n_f, m1, m2, code, out.ctypes.data, _lib.HOST)
+        if device:
+            ctx.set_stream(torch.cuda.current_stream(t.device).cuda_stream)
+        rc = ctx._L.xdemhip_convolution(ctx.handle, ptr(t), _args.code(t), t.shape[0], t.shape[1], t.shape[2], dp(filt), n_f, m1, m2, code,
+                                        ptr(out), _args.space(t))
     ctx.check(rc)
     return out
 
@@ -2078,9 +2029,8 @@ def mean_filter_nan(img: np.ndarray, kernel_size: int, kernel_shape: str = "circ
     mean = np.empty(arr.shape, dtype=np.float64)
     nvalid = np.empty(arr.shape, dtype=np.float64)
     npx = ctypes.c_int()
-    rc = ctx._L.xdemhip_mean_filter_nan(ctx.handle, arr.ctypes.data, _lib.F32 if arr.dtype == np.float32 else _lib.F64, arr.shape[0],
-                                        arr.shape[1], int(kernel_size), 0 if kernel_shape.lower() == "square" else 1,
-                                        mean.ctypes.data, nvalid.ctypes.data, ctypes.byref(npx), _lib.HOST)
+    rc = ctx._L.xdemhip_mean_filter_nan(ctx.handle, ptr(arr), _args.code(arr), arr.shape[0], arr.shape[1], int(kernel_size),
+                                        0 if kernel_shape.lower() == "square" else 1, ptr(mean), ptr(nvalid), ctypes.byref(npx), _lib.HOST)
     if rc == -5:   # XDEMHIP_EUNSUPPORTED
         raise NotImplementedError(
             f"mean_filter_nan: a {kernel_shape} kernel of size {kernel_size} holds {npx.value if npx.value <= 127 else 'more than 127'} "

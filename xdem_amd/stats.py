@@ -22,7 +22,8 @@ import math
 
 import numpy as np
 
-from . import _lib
+from . import _args, _lib
+from ._args import is_tensor
 
 STAT_KEYS = ("Mean", "Median", "Max", "Min", "Sum", "Sum of squares", "90th percentile", "LE90", "NMAD", "RMSE", "Standard deviation",
              "Valid count", "Total count", "Percentage valid points")
@@ -48,10 +49,6 @@ def resolve_name(name: str) -> str:
     return _NAMES[_norm(name)]
 
 
-def _is_tensor(x) -> bool:
-    return type(x).__module__.startswith("torch") and hasattr(x, "data_ptr")
-
-
 def _lerp(a: float, b: float, n: int, q: float) -> float:
     """NumPy's ``method="linear"`` interpolation between the order statistics `a`, `b` of ranks floor((n - 1) q) and the next, in
     float64 (numpy/lib/_function_base_impl.py: _lerp)."""
@@ -71,14 +68,10 @@ class _Input:
     """What the device call reads: values (NumPy float32 / float64 array or CUDA tensor), the byte masks, nodata, the sizes."""
 
     def __init__(self, values, inlier_mask, nodata):
-        self.tensor = _is_tensor(values)
+        self.tensor = is_tensor(values)
         self.total_mask = None
         if self.tensor:
-            import torch
-
-            if not values.is_cuda or values.dtype not in (torch.float32, torch.float64) or not values.is_contiguous():
-                raise ValueError("a tensor input must be a contiguous float32 or float64 CUDA tensor")
-            self.values = values
+            self.values = _args.device_float(values, "a tensor input must be a contiguous float32 or float64 CUDA tensor", ndim=None)
             self.size = int(values.numel())
             self.shape = tuple(values.shape)
         else:
@@ -88,21 +81,13 @@ class _Input:
                     self.total_mask = np.ascontiguousarray(~m, dtype=np.uint8)
                 values = values.data
             v = np.asarray(getattr(values, "data", values) if not isinstance(values, np.ndarray) else values)
-            if v.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
-                v = v.astype(np.float64)
-            self.values = np.ascontiguousarray(v)
+            self.values = _args.host_float(v, np.float64)
             self.size = int(v.size)
             self.shape = v.shape
         self.inlier = None
         if inlier_mask is not None:
-            inl = getattr(inlier_mask, "data", inlier_mask) if not _is_tensor(inlier_mask) else inlier_mask
-            if self.tensor:
-                import torch
-
-                inl = inl if _is_tensor(inl) else torch.from_numpy(np.ascontiguousarray(np.asarray(inl, dtype=bool)))
-                inl = (inl != 0).to(device=self.values.device, dtype=torch.uint8).contiguous()
-            else:
-                inl = np.ascontiguousarray(np.asarray(inl.cpu() if _is_tensor(inl) else inl, dtype=bool), dtype=np.uint8)
+            inl = getattr(inlier_mask, "data", inlier_mask) if not is_tensor(inlier_mask) else inlier_mask
+            inl = _args.mask_u8(inl, self.values, nonzero=True)
             if tuple(inl.shape) != tuple(self.shape):
                 raise ValueError(f"inlier_mask has shape {tuple(inl.shape)}, the values {tuple(self.shape)}")
             self.inlier = inl
@@ -131,23 +116,10 @@ def _device_stats(inp: _Input, quantiles, ctx: _lib.Context | None = None) -> di
     out = _lib.RasterStatsOut()
     qa = (ctypes.c_double * max(len(qs), 1))(*qs)
     has_nd, nd = (1, inp.nodata) if inp.nodata is not None else (0, 0.0)
-    if inp.tensor:
-        import torch
-
-        v = inp.values
-        with ctx.call_lock:
-            ctx.set_stream(torch.cuda.current_stream(v.device).cuda_stream)
-            try:
-                ctx.check(ctx._L.xdemhip_raster_stats(ctx.handle, v.data_ptr(), _lib.F32 if v.dtype == torch.float32 else _lib.F64, inp.size, None,
-                                                      inp.inlier.data_ptr() if inp.inlier is not None else None, has_nd, nd, qa, len(qs), NFACT,
-                                                      _lib.DEVICE, ctypes.byref(out)))
-            finally:
-                ctx.set_stream(None)
-    else:
-        v = inp.values
-        ptr = lambda a: a.ctypes.data if a is not None else None  # noqa: E731
-        ctx.check(ctx._L.xdemhip_raster_stats(ctx.handle, ptr(v) if inp.size else None, _lib.F32 if v.dtype == np.float32 else _lib.F64, inp.size,
-                                              ptr(inp.total_mask), ptr(inp.inlier), has_nd, nd, qa, len(qs), NFACT, _lib.HOST, ctypes.byref(out)))
+    v = inp.values
+    with _args.torch_stream_scope(ctx, v, reset=True):
+        ctx.check(ctx._L.xdemhip_raster_stats(ctx.handle, _args.ptr(v) if inp.size else None, _args.code(v), inp.size, _args.ptr(inp.total_mask),
+                                              _args.ptr(inp.inlier), has_nd, nd, qa, len(qs), NFACT, _args.space(v), ctypes.byref(out)))
     d = {k: getattr(out, k) for k in ("n", "n_valid", "n_inlier", "min", "max", "sum", "sumsq", "sumdev2", "med_lo", "med_hi", "median", "mad_lo",
                                       "mad_hi", "nmad", "reads")}
     d["q_lo"], d["q_hi"] = list(out.q_lo)[:len(qs)], list(out.q_hi)[:len(qs)]

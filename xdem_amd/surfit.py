@@ -19,7 +19,7 @@ from typing import Any
 
 import numpy as np
 
-from . import _lib, terrain
+from . import _args, _lib, terrain
 
 
 def _engine_stack(dem, names: list[str], out_dtype, engine: str, resolution: float, surface_fit: str = "Florinsky",
@@ -54,9 +54,9 @@ def _engine_stack(dem, names: list[str], out_dtype, engine: str, resolution: flo
         if not group:
             continue
         with ctx.option_scope("terrain_nonfinite", nonfinite):
-            terrain.launch_terrain(ctx, src.ctypes.data, src.dtype, H, W, W, 0, 0, resolution, surface_fit, curv_method, group, tri_method,
+            terrain.launch_terrain(ctx, _args.ptr(src), src.dtype, H, W, W, 0, 0, resolution, surface_fit, curv_method, group, tri_method,
                                    window_size, hillshade_altitude, hillshade_azimuth, hillshade_z_factor, 2, out_dtype,
-                                   {a: stack[planes[a]].ctypes.data for a in group}, _lib.HOST, window_size)
+                                   {a: _args.ptr(stack[planes[a]]) for a in group}, _lib.HOST, window_size)
     for i, a in enumerate(names):   # (a name asked for twice: the same plane twice, as upstream's index lists give)
         if planes[a] != i:
             stack[i] = stack[planes[a]]

@@ -20,7 +20,7 @@ from typing import Any
 
 import numpy as np
 
-from . import _lib
+from . import _args, _lib
 
 # Attribute families as in xdem/terrain/terrain.py:40-84
 available_attributes = [
@@ -170,11 +170,11 @@ def launch_terrain(ctx: _lib.Context, dem_ptr: int, dem_dtype, H: int, W: int, r
         mask |= 1 << ATTR_BIT[a]
     ordered = sorted(set(attribute), key=lambda a: ATTR_BIT[a])
     planes = (ctypes.c_void_p * len(ordered))(*[plane_ptrs[a] for a in ordered])
-    args = (ctx.handle, ctypes.c_void_p(dem_ptr), _lib.F32 if np.dtype(dem_dtype) == np.float32 else _lib.F64, H, W,
+    args = (ctx.handle, ctypes.c_void_p(dem_ptr), _args.code(dem_dtype), H, W,
             row_stride, halo_top, halo_bottom, float(resolution), _FIT_ID[surface_fit.lower()],
             _CURV_ID[curv_method.lower()], mask, _TRI_ID[tri_method.lower()], int(window_size), float(hillshade_altitude),
             float(hillshade_azimuth), float(hillshade_z_factor), (int(degrees) & 3) if isinstance(degrees, int) and not isinstance(degrees, bool) else int(bool(degrees)),
-            _lib.F32 if np.dtype(out_dtype) == np.float32 else _lib.F64, planes, memspace)
+            _args.code(out_dtype), planes, memspace)
     with ctx.call_lock:   # (a launch reads the context's options: not while another thread has one changed for its own call)
         rc = ctx._L.xdemhip_terrain(*args)
     ctx.check(rc)
@@ -289,14 +289,13 @@ def _run_and_wrap(ctx, dem, dem_arr, attribute, outs, H, W, resolution, degrees,
     for arr, names, nonfinite in groups:
         if names:
             with ctx.option_scope("terrain_nonfinite", nonfinite):
-                launch_terrain(ctx, arr.ctypes.data, arr.dtype, H, W, W, 0, 0, resolution, surface_fit, curv_method,
+                launch_terrain(ctx, _args.ptr(arr), arr.dtype, H, W, W, 0, 0, resolution, surface_fit, curv_method,
                                names, tri_method, window_size, hillshade_altitude, hillshade_azimuth, hillshade_z_factor,
-                               degrees, out_dtype, {a: outs[a].ctypes.data for a in set(names)}, _lib.HOST, window_size_fractal)
+                               degrees, out_dtype, {a: _args.ptr(outs[a]) for a in set(names)}, _lib.HOST, window_size_fractal)
     if "texture_shading" in attribute:  # frequency-domain attribute: its own engine (terrain.py:637-644)
         alpha = texture_alpha
-        code = lambda dt: _lib.F32 if np.dtype(dt) == np.float32 else _lib.F64  # noqa: E731
-        ctx.check(ctx._L.xdemhip_texture_shading(ctx.handle, dem_arr.ctypes.data, code(dem_arr.dtype), H, W, float(alpha),
-                                                 code(out_dtype), outs["texture_shading"].ctypes.data, _lib.HOST))
+        ctx.check(ctx._L.xdemhip_texture_shading(ctx.handle, _args.ptr(dem_arr), _args.code(dem_arr), H, W, float(alpha), _args.code(out_dtype),
+                                                 _args.ptr(outs["texture_shading"]), _lib.HOST))
     output_attributes = [outs[a] for a in attribute]
     if _is_raster(dem):
         output_attributes = [
@@ -445,8 +444,8 @@ def terrain_attributes_device(dem, attribute: list[str], resolution: float = 1.0
         out = alloc_planes(len(attribute), H, W, dem.dtype, ctx, dem.device)
     ctx.set_stream(torch.cuda.current_stream(dem.device).cuda_stream)
     assert out.shape == (len(attribute), H, W) and out.stride(2) == 1 and out.stride(1) == W and out.is_cuda
-    ptrs = {a: out[i].data_ptr() for i, a in enumerate(attribute)}  # planes may be row windows of a larger tensor
-    launch_terrain(ctx, dem.data_ptr(), dt, H, W, dem.stride(0), halo_top, halo_bottom, resolution, surface_fit,
+    ptrs = {a: _args.ptr(out[i]) for i, a in enumerate(attribute)}  # planes may be row windows of a larger tensor
+    launch_terrain(ctx, _args.ptr(dem), dt, H, W, dem.stride(0), halo_top, halo_bottom, resolution, surface_fit,
                    curv_method, list(attribute), tri_method, window_size, hillshade_altitude, hillshade_azimuth,
                    hillshade_z_factor, degrees, {torch.float32: np.float32, torch.float64: np.float64}[out.dtype],
                    ptrs, _lib.DEVICE, window_size_fractal)

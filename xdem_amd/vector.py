@@ -25,12 +25,9 @@ from typing import Any
 import numpy as np
 import pandas as pd
 
-from . import _lib
+from . import _args, _lib
 
 Bounds = collections.namedtuple("Bounds", ["left", "bottom", "right", "top"])
-_I64P = ctypes.POINTER(ctypes.c_int64)
-_I32P = ctypes.POINTER(ctypes.c_int32)
-_DP = ctypes.POINTER(ctypes.c_double)
 NORTH_UP = "only north-up transforms (b = d = 0) are supported"
 
 
@@ -138,18 +135,20 @@ class DeviceRasterizer:
     last_count = 0
 
     @staticmethod
-    def _args(table):
+    def _table_args(table, where=None):
+        """The five arguments a vertex table is to the library, read from the arrays or tensors `where` (default: the table's own)."""
         xy, ring_off, poly_of_ring, n_poly = table
-        return (xy.ctypes.data_as(_DP), xy.shape[1], ring_off.ctypes.data_as(_I64P), poly_of_ring.shape[0], poly_of_ring.ctypes.data_as(_I32P))
+        t = (xy, ring_off, poly_of_ring) if where is None else where
+        return (_args.dp(t[0]), xy.shape[1], _args.i64p(t[1]), poly_of_ring.shape[0], _args.i32p(t[2]))
 
     def _out(self, ctx, shape, dtype, device):
         if device:
             import torch
 
             out = torch.empty(shape, dtype=getattr(torch, dtype), device=torch.device("cuda", ctx.device))
-            return out, ctypes.c_void_p(out.data_ptr())
-        out = np.empty(shape, dtype)
-        return out, ctypes.c_void_p(out.ctypes.data)
+        else:
+            out = np.empty(shape, dtype)
+        return out, ctypes.c_void_p(_args.ptr(out))
 
     def _run(self, call, tables, device, ctx):
         """Host tables with a host plane; for a device plane the tables are uploaded through torch and everything stays there."""
@@ -159,13 +158,13 @@ class DeviceRasterizer:
 
             dev = torch.device("cuda", ctx.device)
             args = []
-            for xy, ring_off, por, n_poly in tables:
-                t = [torch.from_numpy(a).to(dev) for a in (xy, ring_off, por)]
+            for table in tables:
+                t = [torch.from_numpy(a).to(dev) for a in table[:3]]
                 keep.append(t)
-                args.append((ctypes.cast(t[0].data_ptr(), _DP), xy.shape[1], ctypes.cast(t[1].data_ptr(), _I64P), por.shape[0], ctypes.cast(t[2].data_ptr(), _I32P)))
+                args.append(self._table_args(table, t))
             torch.cuda.current_stream(dev).synchronize()   # (the library launches on its own stream)
         else:
-            args = [self._args(t) for t in tables]
+            args = [self._table_args(t) for t in tables]
         count = ctypes.c_int64()
         with ctx.call_lock:
             ctx.check(call(args, keep, ctypes.byref(count)))
@@ -198,16 +197,14 @@ class DeviceRasterizer:
         burn = np.ascontiguousarray(burn, dtype=np.int32)
 
         def call(args, keep, count):
+            b = burn
             if device:
                 import torch
 
                 b = torch.from_numpy(burn).to(torch.device("cuda", ctx.device))
                 keep.append(b)
-                torch.cuda.current_stream(b.device).synchronize()
-                bp = ctypes.cast(b.data_ptr(), _I32P)
-            else:
-                bp = burn.ctypes.data_as(_I32P)
-            return L.xdemhip_rasterize(ctx.handle, *args[0], bp, table[3], shape[0], shape[1], tr, ptr, 1, int(out_value), space, count)
+                _args.synchronize_torch(b)
+            return L.xdemhip_rasterize(ctx.handle, *args[0], _args.i32p(b), table[3], shape[0], shape[1], tr, ptr, 1, int(out_value), space, count)
 
         self._run(call, [table], device, ctx)
         return out

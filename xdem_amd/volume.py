@@ -21,46 +21,21 @@ import pandas as pd
 import scipy.interpolate
 import scipy.optimize
 
-from . import _lib
+from . import _args, _lib
+from ._args import code, dp, i32p, i64p, is_tensor, np_dtype, ptr, same_space
+from ._args import flat_float as _float_plane  # (under these names tests/volume_oracle.py builds its plan's inputs too)
+from ._args import flat_mask as _mask_plane
 
 LABEL_LIMIT = 1 << 20
-_DP = ctypes.POINTER(ctypes.c_double)
-_I64P = ctypes.POINTER(ctypes.c_int64)
-_I32P = ctypes.POINTER(ctypes.c_int32)
 
 
 # ---- inputs ------------------------------------------------------------------------------------------------------------------------
-def _is_tensor(x) -> bool:
-    return type(x).__module__.startswith("torch") and hasattr(x, "data_ptr")
-
-
-def _float_plane(x, what: str):
-    """A raster as (array or tensor, flat and contiguous, float32 / float64; masked -> NaN).  Integer rasters become float32, as
-    geoutils' get_array_and_mask makes them."""
-    if _is_tensor(x):
-        import torch
-
-        if not x.is_cuda:
-            raise ValueError(f"{what}: a tensor input must live on the GPU (pass host data as a NumPy array)")
-        if x.dtype not in (torch.float32, torch.float64):
-            x = x.to(torch.float32)
-        return x.contiguous().reshape(-1)
-    if isinstance(x, np.ma.MaskedArray):
-        data = np.array(x.data, dtype=x.dtype if x.dtype in (np.float32, np.float64) else np.float32)
-        data[np.ma.getmaskarray(x)] = np.nan
-        x = data
-    x = np.asarray(x)
-    if x.dtype not in (np.float32, np.float64):
-        x = x.astype(np.float32)
-    return np.ascontiguousarray(x).reshape(-1)
-
-
 def _labels_plane(x, like):
     """A glacier index map as flat int32 in the memspace of `like`; integral values in [0, 2^20) only."""
     def bad(lo, hi):
         return ValueError(f"glacier_index_map: labels must lie in [0, 2^20 = {LABEL_LIMIT}); found {lo} .. {hi}")
 
-    if _is_tensor(x):
+    if is_tensor(x):
         import torch
 
         x = x.contiguous().reshape(-1)
@@ -84,58 +59,18 @@ def _labels_plane(x, like):
         if lo < 0 or hi >= LABEL_LIMIT:
             raise bad(lo, hi)
         x = np.ascontiguousarray(x.astype(np.int32, copy=False))
-    if _is_tensor(like) and not _is_tensor(x):
-        import torch
-
-        x = torch.from_numpy(x).to(like.device)
-    elif not _is_tensor(like) and _is_tensor(x):
-        x = x.cpu().numpy()
-    return x
-
-
-def _mask_plane(x, like):
-    if _is_tensor(x):
-        import torch
-
-        x = x.contiguous().reshape(-1).to(torch.bool).to(torch.uint8)
-        return x if _is_tensor(like) else x.cpu().numpy()
-    x = np.ascontiguousarray(np.asarray(x).reshape(-1).astype(bool)).view(np.uint8)
-    if _is_tensor(like):
-        import torch
-
-        return torch.from_numpy(x.copy()).to(like.device)
-    return x
-
-
-def _same_space(x, like):
-    if _is_tensor(like) and not _is_tensor(x):
-        import torch
-
-        return torch.from_numpy(x).to(like.device)
-    if not _is_tensor(like) and _is_tensor(x):
-        return x.cpu().numpy()
-    return x
-
-
-def _np_dtype(x) -> np.dtype:
-    return np.dtype(str(x.dtype).replace("torch.", ""))
-
-
-def _ptr(x):
-    return ctypes.c_void_p(x.data_ptr() if _is_tensor(x) else x.ctypes.data)
-
-
-def _code(x) -> int:
-    return _lib.F32 if _np_dtype(x) == np.float32 else _lib.F64
+    return same_space(x, like)
 
 
 # ---- the labelled engine ---------------------------------------------------------------------------------------------------------------
-class HypsoPlan:
+class HypsoPlan(_lib._Plan):
     """One (dDEM, reference) pair on the device with its optional label map or mask: ``xdemhip_hypso`` of include/xdemhip.h."""
+
+    _DESTROY = "xdemhip_hypso_destroy"
 
     def __init__(self, ddem, ref, labels=None, mask=None, ctx: _lib.Context | None = None):
         self.ddem = _float_plane(ddem, "ddem")
-        self.ref = _same_space(_float_plane(ref, "ref_dem"), self.ddem)
+        self.ref = same_space(_float_plane(ref, "ref_dem"), self.ddem)
         if self.ddem.shape != self.ref.shape:
             raise ValueError("the dDEM and the reference DEM must have the same number of pixels")
         self.labels = None if labels is None else _labels_plane(labels, self.ddem)
@@ -144,39 +79,18 @@ class HypsoPlan:
             if extra is not None and extra.shape != self.ddem.shape:
                 raise ValueError("the label map / mask must have the same number of pixels as the rasters")
         self.n = int(self.ddem.shape[0])
-        self.on_device = _is_tensor(self.ddem)
+        self.on_device = is_tensor(self.ddem)
         self.ctx = ctx or _lib.default_context(self.ddem.device.index if self.on_device else None)
-        self.space = _lib.DEVICE if self.on_device else _lib.HOST
+        self.space = _args.space(self.ddem)
         if self.on_device:
-            import torch
-
-            torch.cuda.current_stream(self.ddem.device).synchronize()   # (the inputs are complete; the calls return synchronised)
+            _args.synchronize_torch(self.ddem)   # (the inputs are complete; the calls return synchronised)
         h = ctypes.c_void_p()
         with self.ctx.call_lock:
             self.ctx.check(self.ctx._L.xdemhip_hypso_create(
-                self.ctx.handle, _ptr(self.ddem), _code(self.ddem), _ptr(self.ref), _code(self.ref),
-                None if self.labels is None else _ptr(self.labels), None if self.mask is None else _ptr(self.mask), self.n, self.space,
-                ctypes.byref(h)))
+                self.ctx.handle, ptr(self.ddem), code(self.ddem), ptr(self.ref), code(self.ref), ptr(self.labels), ptr(self.mask),
+                self.n, self.space, ctypes.byref(h)))
         self.handle = h
         self.ctx.adopt(self)
-
-    def close(self) -> None:
-        if getattr(self, "handle", None):
-            self.ctx._L.xdemhip_hypso_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self) -> None:  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
 
     def label_stats(self) -> dict:
         """Per label that occurs (ascending): pixels, inliers, min / max of the reference over its pixels and over its inliers; and
@@ -188,8 +102,7 @@ class HypsoPlan:
         found, bad, ref_bad = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
         with self.ctx.call_lock:
             self.ctx.check(self.ctx._L.xdemhip_hypso_label_stats(
-                self.handle, cap, ids.ctypes.data_as(_I32P), cnt.ctypes.data_as(_I64P), ext.ctypes.data_as(_DP), ctypes.byref(found),
-                ctypes.byref(bad), ctypes.byref(ref_bad)))
+                self.handle, cap, i32p(ids), i64p(cnt), dp(ext), ctypes.byref(found), ctypes.byref(bad), ctypes.byref(ref_bad)))
         if bad.value:
             raise ValueError(f"glacier_index_map: {bad.value} labels outside [0, 2^20 = {LABEL_LIMIT})")
         k = int(found.value)
@@ -208,15 +121,14 @@ class HypsoPlan:
         sd = np.empty((len(ids), nb), np.float64) if want_std else None
         with self.ctx.call_lock:
             self.ctx.check(self.ctx._L.xdemhip_hypso_segments(
-                self.handle, len(ids), ids.ctypes.data_as(_I32P), nb, edges.ctypes.data_as(_DP), int(want_std), counts.ctypes.data_as(_I64P),
-                med.ctypes.data_as(_DP), None if sd is None else sd.ctypes.data_as(_DP)))
+                self.handle, len(ids), i32p(ids), nb, dp(edges), int(want_std), i64p(counts), dp(med), dp(sd)))
         return counts, med, sd
 
     def groups(self) -> np.ndarray:
         """The group (rank * nb + bin - 1, or -1) of every pixel in the last ``segments`` call, on the host."""
         out = np.empty(self.n, np.int32)
         with self.ctx.call_lock:
-            self.ctx.check(self.ctx._L.xdemhip_hypso_groups(self.handle, ctypes.c_void_p(out.ctypes.data), _lib.HOST))
+            self.ctx.check(self.ctx._L.xdemhip_hypso_groups(self.handle, ptr(out), _lib.HOST))
         return out
 
     def fill(self, mode: int, ids, xs: np.ndarray, ys: np.ndarray, round_to_ref: bool, out_dtype: np.dtype):
@@ -234,13 +146,12 @@ class HypsoPlan:
             out = np.empty(self.n, out_dtype)
         with self.ctx.call_lock:
             self.ctx.check(self.ctx._L.xdemhip_hypso_fill(
-                self.handle, int(mode), len(ids), ids.ctypes.data_as(_I32P), m, xs.ctypes.data_as(_DP),
-                ys.ctypes.data_as(_DP), int(round_to_ref), _ptr(out), _lib.F32 if out_dtype == np.float32 else _lib.F64, self.space))
+                self.handle, int(mode), len(ids), i32p(ids), m, dp(xs), dp(ys), int(round_to_ref), ptr(out), code(out_dtype), self.space))
         return out
 
 
 def _host(x) -> np.ndarray:
-    return x.cpu().numpy() if _is_tensor(x) else x
+    return x.cpu().numpy() if is_tensor(x) else x
 
 
 _DEVICE_MEDIANS = (np.median, np.nanmedian)
@@ -317,7 +228,7 @@ def _binning_of(plan: HypsoPlan, bins, kind, aggregation_function, over_inliers:
     """hypsometric_binning on the one label of `plan`.  over_inliers: the caller handed upstream only the inlier pixels (so the edges
     come from their extremes); otherwise from every pixel with a valid reference."""
     st = plan.label_stats()
-    dt = _np_dtype(plan.ref)
+    dt = np_dtype(plan.ref)
     key = ("inlier_ref_min", "inlier_ref_max") if over_inliers else ("ref_min", "ref_max")
     empty = len(st["ids"]) == 0 or np.isnan(st[key[0]][0])
     if empty and not isinstance(bins, np.ndarray) and kind in ("fixed", "count", "quantile"):
@@ -335,7 +246,7 @@ def _binning_of(plan: HypsoPlan, bins, kind, aggregation_function, over_inliers:
 
     zbins = _zbins(kind, bins, ref_min, ref_max, ref_valid)
     nb = zbins.shape[0] - 1
-    vdt = _np_dtype(plan.ddem)
+    vdt = np_dtype(plan.ddem)
     if nb < 1 or empty:
         return _binning_frame(zbins, np.full(max(nb, 0), np.nan, dtype=vdt), np.zeros(max(nb, 0), dtype=int))
     if np.any(np.diff(np.asarray(zbins, dtype=np.float64)) < 0):
@@ -419,15 +330,12 @@ def _area_counts(ref, timeframe: int, xs: np.ndarray, ys: np.ndarray, bins: np.n
     nb = bins.shape[0] - 1
     counts = np.zeros(nb, np.int64)
     xs, ys, bins = np.ascontiguousarray(xs), np.ascontiguousarray(ys), np.ascontiguousarray(bins)
-    ctx = _lib.default_context(ref.device.index if _is_tensor(ref) else None)
-    if _is_tensor(ref):
-        import torch
-
-        torch.cuda.current_stream(ref.device).synchronize()
+    ctx = _lib.default_context(ref.device.index if is_tensor(ref) else None)
+    if is_tensor(ref):
+        _args.synchronize_torch(ref)
     with ctx.call_lock:
-        ctx.check(ctx._L.xdemhip_hypso_area(ctx.handle, _ptr(ref), _code(ref), int(ref.shape[0]), timeframe, int(xs.shape[0]),
-                                           xs.ctypes.data_as(_DP), ys.ctypes.data_as(_DP), nb, bins.ctypes.data_as(_DP),
-                                           counts.ctypes.data_as(_I64P), _lib.DEVICE if _is_tensor(ref) else _lib.HOST))
+        ctx.check(ctx._L.xdemhip_hypso_area(ctx.handle, ptr(ref), code(ref), int(ref.shape[0]), timeframe, int(xs.shape[0]), dp(xs), dp(ys),
+                                           nb, dp(bins), i64p(counts), _args.space(ref)))
     return counts
 
 
@@ -444,7 +352,7 @@ def calculate_hypsometry_area(
     must hold no NaN; `pixel_size` is one length or an (x, y) pair.  Returns a Series over the bins' index.
     """
     ref = _float_plane(ref_dem.data if isinstance(ref_dem, np.ma.MaskedArray) else ref_dem, "ref_dem")   # (upstream reads `.data`)
-    nan_count = int(ref.isnan().sum().item()) if _is_tensor(ref) else int(np.count_nonzero(np.isnan(ref)))
+    nan_count = int(ref.isnan().sum().item()) if is_tensor(ref) else int(np.count_nonzero(np.isnan(ref)))
     assert not nan_count, "The given reference DEM has NaNs. No NaNs are allowed to calculate area!"
     if timeframe not in _TIMEFRAMES:
         raise ValueError(f"Argument 'timeframe={timeframe}' is invalid. Choices: ['reference', 'nonreference', 'mean'].")
@@ -476,13 +384,13 @@ def hypsometric_interpolation(voided_ddem, ref_dem, mask):
         st = plan.label_stats()
         if len(st["ids"]) == 0 or st["inliers"][0] == 0:
             warnings.warn("No valid data found within mask, returning copy", UserWarning)
-            return voided_ddem.clone() if _is_tensor(voided_ddem) else np.ma.masked_array(data=voided_ddem)
+            return voided_ddem.clone() if is_tensor(voided_ddem) else np.ma.masked_array(data=voided_ddem)
         gradient = interpolate_hypsometric_bins(_binning_of(plan, 50.0, "fixed", np.median, over_inliers=True))
         model = scipy.interpolate.interp1d(gradient.index.mid, gradient["value"].values, fill_value="extrapolate")
-        out_dtype = np.promote_types(_np_dtype(plan.ddem), _np_dtype(plan.ref))
+        out_dtype = np.promote_types(np_dtype(plan.ddem), np_dtype(plan.ref))
         out = plan.fill(0, [1], np.asarray(model.x, np.float64), np.asarray(model.y, np.float64), True, out_dtype)
     out = out.reshape(shape)
-    if _is_tensor(out):
+    if is_tensor(out):
         return out
     return np.ma.masked_array(out, mask=~np.isfinite(out))
 
@@ -502,7 +410,7 @@ def _regional_signal(plan: HypsoPlan, st: dict, n_bins: int, min_coverage: float
     # upstream's decisions (volume.py:609-635): outlines of fewer than 10 pixels, coverage under the threshold, no inlier at all
     keep = (pix >= 10) & ~((inl / pix) < min_coverage) & (inl > 0)
     kept = ids[keep]
-    dt, vdt = _np_dtype(plan.ref), _np_dtype(plan.ddem)
+    dt, vdt = np_dtype(plan.ref), np_dtype(plan.ddem)
     if len(kept):
         edges = [_zbins("count", n_bins, dt.type(lo), dt.type(hi), None) for lo, hi in zip(st["inlier_ref_min"][keep], st["inlier_ref_max"][keep])]
         g_counts, g_med, _ = plan.segments(kept, np.asarray(edges, dtype=np.float64))
@@ -546,7 +454,7 @@ def regional_glacier_models(plan: HypsoPlan, st: dict, regional_signal: pd.DataF
     fit was made, "coeffs" and the model table "x" = signal.index.mid, "y" = np.poly1d(coeffs)(signal.values).  One grouping pass
     serves all glaciers."""
     ids, pix, inl = st["ids"], st["pixels"], st["inliers"]
-    dt, vdt = _np_dtype(plan.ref), _np_dtype(plan.ddem)
+    dt, vdt = np_dtype(plan.ref), np_dtype(plan.ddem)
     records = [{"id": int(i), "skipped": True} for i in ids]
     passing = [k for k in range(len(ids)) if not (inl[k] / pix[k]) < min_coverage]
     signals = []
@@ -616,5 +524,5 @@ def norm_regional_hypsometric_interpolation(
         ids = [r["id"] for r in fitted]
         xs = np.asarray([r["x"] for r in fitted], dtype=np.float64)
         ys = np.asarray([r["y"] for r in fitted], dtype=np.float64)
-        out = plan.fill(1 if idealized_ddem else 0, ids, xs, ys, False, _np_dtype(plan.ddem))
+        out = plan.fill(1 if idealized_ddem else 0, ids, xs, ys, False, np_dtype(plan.ddem))
     return out.reshape(shape)
