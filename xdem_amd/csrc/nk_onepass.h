@@ -1,7 +1,8 @@
 // nk_onepass.h -- DEVICE code of the one-pass Nuth-Kaab step (the host side is nk_step_onepass in nuthkaab.hip): the fused data
 // pass, the per-bin candidate segments, the value-bucket selection of the median of dh, the predicted brackets, and the exchange
 // kernels of partitioned plans.  Part of nuthkaab.hip's translation unit: included there once, after the definitions it builds on
-// (NkGeom / bi_* of nk_geom.h, DhStats, NkRowTab, nk_nearest, nk_bin_t / BinCacheRec, on_last_edge, make_edges_into).
+// (NkGeom / bi_* of nk_geom.h, DhStats, NkRowTab, nk_nearest, nk_bin_t / BinCacheRec, on_last_edge, make_edges_into; the sizes of
+// the step's device blocks: nk_layout.h; NK_PREDICT_MAX_BINS: nk_policy.h).
 #pragma once
 
 namespace xd {
@@ -214,7 +215,7 @@ __global__ __launch_bounds__(256) void nk_sample_dy_kernel(const T* __restrict__
 // Round 6: the brackets of a step from the host's PREDICTION instead of from samples (nk_step_onepass).  Values in, what the sample
 // selections would have left out: bracket keys of the median of dh and of the bins' medians, the rebase shifts of the candidate
 // selections, v^ and delta.  An empty bin (lo > hi) gets the bracket {0, all-ones} of a bin without sample elements.
-constexpr int NK_PREDICT_MAX_BINS = 128;
+// (NK_PREDICT_MAX_BINS: nk_policy.h, where the prediction is decided)
 template <typename T> struct NkPredicted { T dlo, dhi; T lo[NK_PREDICT_MAX_BINS], hi[NK_PREDICT_MAX_BINS]; };
 template <typename T>
 __global__ __launch_bounds__(64) void nk_predict_kernel(const NkPredicted<T> pr, int nb, typename KeyT<T>::type* klo_d, typename KeyT<T>::type* khi_d,
@@ -577,7 +578,7 @@ __global__ __launch_bounds__(256, (sizeof(T) == 8 ? (RULE == 2 ? 4 : 5) : (RULE 
 // exact order statistic and its successor are settled there by the usual digit passes.  Same integers and the same order of keys
 // as on the other routes: results are identical bit for bit.
 constexpr int BINSEG_U = 16;            // values per thread and round of the scatter (one reservation per bin, workgroup and round)
-constexpr int BINSEG_CTR_STRIDE = 16;   // the per-bin place counters sit one 128-byte line apart (same-line atomics serialise)
+// (BINSEG_CTR_STRIDE, the distance of the per-bin place counters: nk_layout.h)
 struct BinsegMap { double lo, scale; };
 template <typename T, typename K> __device__ __forceinline__ BinsegMap binseg_map(K klo, K khi) {
     BinsegMap m;
@@ -866,9 +867,7 @@ __global__ __launch_bounds__(HIST_THREADS) void nk_bin_select_kernel(const T* __
 // ticket, doing the final part -- needs the keys, plain stores of many workgroups, published by device-scope fences: on this
 // multi-XCD part a fence writes back the issuing XCD's whole L2, 38-55 us for 64 workgroups, measured; a kernel boundary is cheaper.)
 // Same integers, same keys: the result is the generic selection's bit for bit (GPU tests: every route agrees).
-constexpr int DSEL_BUCKETS = 4096;
-constexpr int DSEL_CAP = 8192;        // keys of the chosen bucket (more -- ties en masse -- send the step to the plain route)
-constexpr int DSEL_HDR_WORDS = 4;     // 64-bit words: [0] ~(smallest key IN the bucket), [1] keys appended, [2] ~(smallest key above the bucket), [3] largest key in the bucket; then the histogram
+// (DSEL_BUCKETS, DSEL_CAP, DSEL_HDR_WORDS -- the sizes of this selection's header, histogram and key list: nk_layout.h)
 // Two forms of the monotone bucket map.  VALUE buckets (floor((v - lo) * 4096 / (hi - lo)) in float64) for brackets that straddle
 // zero or span many binades -- there the float KEYS are spread exponentially and most values would sit in a few key buckets.
 // KEY buckets ((key - klo) >> s, s the smallest shift that brings the bracket under 4096 buckets) for brackets inside at most three

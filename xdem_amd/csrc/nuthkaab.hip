@@ -14,6 +14,7 @@
 #include <math.h>
 #include <string.h>
 
+#include <optional>
 #include <vector>
 
 #include "common.h"
@@ -21,6 +22,8 @@
 #include "select_run.h"
 #include "nk_geom.h"
 #include "nk_aux.h"
+#include "nk_layout.h"
+#include "nk_policy.h"
 #include "rank_select.h"
 
 namespace xd {
@@ -477,8 +480,7 @@ struct xdemhip_nk_plan {
     int64_t* ext_idx = nullptr;   // [2][EXT_CAP] pixels with the lowest / highest aspects
     unsigned long long* ext_cnt = nullptr;  // [0..1] list lengths, [2..3] survivors of the current step
     bool ext_ok = false;
-    uint64_t* fz = nullptr;       // device block of the one-pass step (nk_step_onepass): counters, bracket keys, v^, sums
-    size_t fz_bytes = 0;
+    uint64_t* fz = nullptr;       // device block of the one-pass step (nk_layout.h: NkFzLayout): counters, bracket keys, v^, sums
     void* cd_vals = nullptr;      // ... candidates of the median of dh
     int64_t cd_cap = 0;
     void* c_st = nullptr;         // ... slope tangents of the bin candidates (next to ws.c_vals / ws.c_bins)
@@ -488,29 +490,10 @@ struct xdemhip_nk_plan {
     size_t fz_pack_bytes = 0;
     std::vector<unsigned char> fz_host;
     int64_t n_onepass = 0, n_plain = 0;   // steps answered by each route (xdemhip_nk_route_counts)
-    // one-pass route: the sample brackets of the NEXT step are a fraction (code fz_narrow, select.h: sel_narrowed / sel_narrow_unit)
-    // of what the rule for fully correlated sample lines asks (select.h: sel_bracket_halfwidth); set from how far off the bracket
-    // centres the wanted ranks lay in the steps so far, never below fz_unit_min (raised by a miss)
-    int fz_narrow = 0;
-    double fz_unit_min = 0.25;
-    double fz_worst = 0.0;   // largest |wanted rank - bracket centre| seen, in half widths of the FULL rule
-    double fz_off2 = 0.0;    // sum of squares of those offsets over all brackets of all steps so far
-    int64_t fz_offn = 0;
-    // one-pass route, round 6: PREDICTED brackets.  Once a fit has settled its offsets move by a few thousandths of a pixel per
-    // step and the 73 exact medians of the previous step, moved by what the Nuth-Kaab model says the shift does to them, bracket
-    // this step's medians better than a fresh 1/64 sample does -- the two sample kernels and their six digit passes (~0.26 ms of
-    // a 1.66 ms step at C3) are skipped.  What the previous step left (host side; identical on every rank of a partitioned plan):
-    bool pr_have = false;             // ... it answered on the one-pass route and everything below is its record
-    int pr_nb = 0;
-    double pr_sx = 0, pr_sy = 0, pr_rx = 0, pr_ry = 0;   // its shifts and resolutions (georeferenced units)
-    double pr_v = 0, pr_wd = 0;       // its vshift; half width (value) of the last SAMPLED bracket of the median of dh
-    double pr_st = 0;                 // n / sum(1 / slope_tan): the scale that turns a shift in pixels into a change of dh
-    std::vector<double> pr_med, pr_w, pr_mid;   // per bin: exact median of y, half width of the last sampled bracket, centre aspect
-    std::vector<unsigned char> pr_ok; // ... the bin had a median
-    double pr_err = 1e30, pr_err_d = 1e30;   // how far the prediction of the LAST step would have been off (or was), in sampled half widths: bins / median of dh
-    double pr_dpx = 1e30;             // the shift change of the last step, pixels
-    int pr_cooldown = 0;              // sampled steps still to run after a predicted bracket missed
-    int64_t n_predicted = 0, n_predicted_d = 0, n_predict_miss = 0;   // steps with every bracket predicted / with the bracket of the median of dh predicted / reruns after a miss
+    // one-pass route, the two host policies (nk_policy.h): how narrow the sample brackets of the NEXT step may be, and the record
+    // of the previous step from which THIS step's brackets are predicted instead of sampled
+    NkNarrowing narrowing;
+    NkPrediction pred;
     // one-pass step on PARTITIONED plans (reduction hook + xdemhip_set_rank): the two exchange buffers, this rank's own classes and the
     // counters rewritten for the gathered bucket values (nk_mr_* kernels); the ranks' agreement on the route, renewed when what it rests
     // on changes
@@ -705,218 +688,204 @@ int nk_mr_alloc(xdemhip_nk_plan* P, int nb, int world, size_t es) {
     const size_t wa = mx(mx(4, 3 + 3 * (size_t)nb + 5 * (size_t)world + (size_t)world * (DSEL_BUCKETS / 2)), 2 + 2 * (size_t)nb + (size_t)world * nb * (SEL_RADIX / 2));
     const size_t wb = mx((size_t)world * DSEL_HDR_WORDS + (size_t)DSEL_CAP * es / 8, (size_t)nb * MR_GSEG * es / 8);
     const char* who = "exchange buffers of the one-pass step";
-    if (!P->mr_small) P->mr_small = P->mem.take<uint64_t>((size_t)(11 + BINSEG_CTR_STRIDE) * P->ws.nb_max, who);
+    if (!P->mr_small) P->mr_small = P->mem.take<uint64_t>((size_t)NkMrSmallLayout::total_words(P->ws.nb_max), who);
     if (P->mr_a_words < wa) P->mr_a_words = P->mem.regrow(P->mr_a, wa * 8, who) ? wa : 0;
     if (P->mr_b_words < wb) P->mr_b_words = P->mem.regrow(P->mr_b, wb * 8, who) ? wb : 0;
     return P->mem.status();
 }
 
-// ---- host side of the one-pass step (device code: "Round 4: the ONE-PASS step" above) ------------------------------------------
-// *done = false (nothing returned) when the route does not apply or when a bracket missed / a buffer overflowed: the caller
-// then runs the plain route, which needs nothing from here.
-template <typename T>
-int nk_step_onepass(xdemhip_nk_plan* P, const NkGeom& g, int64_t q0, int64_t n, int nb, bool* done, double* vshift, int64_t* n_valid,
-                    double* y_mean, double* y_std, double* edges_out, int64_t* counts, double* medians, bool allow_predict = true) {
+// ---- host side of the one-pass step (device code: nk_onepass.h; the two policies: nk_policy.h; the device blocks: nk_layout.h) ----
+// where a step's results go
+struct NkStepOut { double* vshift; int64_t* n_valid; double *y_mean, *y_std, *edges; int64_t* counts; double* medians; };
+
+// (the step's small results and the ONE table that says where each comes from -- NkStepResults, nk_fetch_bytes: nk_layout.h)
+static_assert(NK_FETCH_MAX <= (int)(sizeof(FzPack::bytes) / sizeof(uint32_t)), "the pack kernel's argument holds every item");
+
+// what became of a step on this route
+enum NkOutcome { NK_STEP_DONE, NK_STEP_PLAIN /* the plain route takes the step */, NK_STEP_AGAIN /* once more, with sampled brackets */ };
+
+// One step on the one-pass route: the context every stage works in, and the stages in the order nk_step_onepass queues them.
+template <typename T> struct NkOnepass {
     typedef typename KeyT<T>::type K;
-    *done = false;
-    xdemhip_ctx* ctx = P->ctx;
-    SelWorkspace* ws = &P->ws;
-    const int64_t rows = P->row1 - P->row0;
-    const int64_t n_slots = ((((n + SEL_LINE - 1) >> SEL_LINE_LOG2) + 63) >> 6) << SEL_LINE_LOG2;
-    const bool mr = ctx->allreduce != nullptr;   // a partitioned plan: this rank's rows, every count and order statistic over all ranks
-    const int world = ctx->world, rank = ctx->rank;
-    bool cannot = !ctx->nk_fused || !P->fz || !P->cd_vals || !P->c_st || !P->bcache || !P->ext_ok || (g.rule > 1 && !P->badbits) || rows <= 0 ||
-                  P->bin_stat != XDEMHIP_BINSTAT_MEDIAN || !(ctx->selection_mode == 0 || ctx->selection_mode == 3) || !ws->d_small ||
-                  (int64_t)P->nbuf * P->W < ws->c_cap ||   // (the kept bin candidates go into per-bin segments of the y raster)
-                  ws->es != sizeof(T) || nb > ws->nb_max || nb > MAX_BINS_PER_SWEEP || n_slots > ws->s_cap ||
-                  (int64_t)(NKZ_CHUNK_MAX + 2) * P->W * (int64_t)sizeof(T) >= ((int64_t)1 << 32);   // (32-bit byte offsets inside a chunk of rows)
-    int64_t n_all = n;   // pixels of all ranks
-    if (mr && (world < 1 || !ctx->nk_fused_dist || !ctx->nk_fused)) return XDEMHIP_OK;   // (not told the ranks / switched off: context-level, the same on every rank)
-    if (mr) {
-        // Every rank must take the same route.  What the decision rests on is either fixed for the plan and its options or derives
-        // from reduced data (ext_ok), so the ranks agree ONCE -- a host all-reduce of (own pixels, "I cannot") -- and again whenever
-        // any of it changes, which it does on all ranks at the same step.
-        const int64_t key[8] = {nb, P->row0, P->row1, (int64_t)P->ext_ok, (int64_t)P->bin_stat, (int64_t)ctx->selection_mode,
-                                (int64_t)(ctx->nk_fused * 4 + ctx->nk_fused_dist * 2), (int64_t)world * 64 + rank};
-        if (memcmp(key, P->mr_key, sizeof key) != 0) {
-            cannot = cannot || !ctx->nk_fused_dist || world < 1 || world > MR_WORLD_MAX || rank < 0 || rank >= world ||
-                     (int64_t)P->nbuf * P->W < ws->c_cap;
-            if (!cannot && nk_mr_alloc(P, nb, world, sizeof(T)) != XDEMHIP_OK) cannot = true;
-            uint64_t v[2] = {(uint64_t)n, (uint64_t)(cannot ? 1 : 0)};
-            const int rc_ = xd_allreduce_host(ctx, v, 2, XDEMHIP_RED_SUM_U64);
-            if (rc_) return rc_;
-            P->mr_nglob = (int64_t)v[0];
-            P->mr_can = v[1] == 0;
-            memcpy(P->mr_key, key, sizeof key);
+    static constexpr int BR_PASSES = 3;
+    xdemhip_nk_plan* const P;
+    xdemhip_ctx* const ctx;
+    SelWorkspace* const ws;
+    const NkGeom& g;
+    const int64_t q0, n;
+    const int nb;
+    const int64_t rows, n_slots;
+    const bool mr;   // a partitioned plan: this rank's rows, every count and order statistic over all ranks
+    const int world, rank;
+    const NkFzLayout<T> fz;
+    NkMrSmallLayout mrs;     // (partitioned plans, once the ranks have agreed on the route -- eligible; null members otherwise)
+    unsigned char* const scratch;
+    T* const d_edges;
+    DhStats* const d_stats;
+    BinCacheRec* const d_rec;
+    const SelState<K>* const d_st;
+    uint64_t* const ext_slots;   // partitioned plans: per-rank slots of min / max aspect and the EXT survivors, behind the two histograms of the dh sample's selection
+    const T *const ref_m, *const tba, *const st_all;
+    T* const s_v;
+    const bool custom;
+    const int last_decimal;
+    const K low_mask;
+    const int narrow;        // the code this step's sample brackets are taken with
+    NkStepBrackets br;       // sampled or predicted brackets (NkPrediction::plan)
+    int n_wg = 0;            // workgroups of the pass
+    int dsel_grid = 0;
+    NkStepResults<T, K, SelState<K>> h;   // (sized by stage_fetch: a step that takes the plain route allocates nothing here)
+
+    NkOnepass(xdemhip_nk_plan* P_, const NkGeom& g_, int64_t q0_, int64_t n_, int nb_)
+        : P(P_), ctx(P_->ctx), ws(&P_->ws), g(g_), q0(q0_), n(n_), nb(nb_), rows(P_->row1 - P_->row0),
+          n_slots(((((n_ + SEL_LINE - 1) >> SEL_LINE_LOG2) + 63) >> 6) << SEL_LINE_LOG2), mr(P_->ctx->allreduce != nullptr), world(P_->ctx->world),
+          rank(P_->ctx->rank), fz(P_->fz, P_->ws.nb_max), mrs(nullptr, P_->ws.nb_max), scratch(static_cast<unsigned char*>(P_->scratch)),
+          d_edges(reinterpret_cast<T*>(scratch)), d_stats(reinterpret_cast<DhStats*>(scratch + OFF_STATS)),
+          d_rec(reinterpret_cast<BinCacheRec*>(scratch + OFF_INFO + 64)), d_st(reinterpret_cast<const SelState<K>*>(scratch + OFF_STATE)),
+          ext_slots(reinterpret_cast<uint64_t*>(scratch + off_hist(2)) + 2 * SEL_RADIX), ref_m(static_cast<const T*>(P_->ref_m)),
+          tba(static_cast<const T*>(P_->tba)), st_all(static_cast<const T*>(P_->slope_tan)), s_v(static_cast<T*>(P_->ws.s_vals)),
+          custom(!P_->custom_edges.empty()), last_decimal(custom ? P_->custom_decimal : NK_AUTO_EDGES),
+          low_mask((K)(((K)1 << (8 * (KeyT<T>::passes - BR_PASSES))) - 1)), narrow(P_->narrowing.narrow) {}
+
+    // ---- does the route apply?  (*go stays false: the caller runs the plain route, which needs nothing from here) ----------------
+    int eligible(bool* go) {
+        *go = false;
+        bool cannot = !ctx->nk_fused || !P->fz || !P->cd_vals || !P->c_st || !P->bcache || !P->ext_ok || (g.rule > 1 && !P->badbits) || rows <= 0 ||
+                      P->bin_stat != XDEMHIP_BINSTAT_MEDIAN || !(ctx->selection_mode == 0 || ctx->selection_mode == 3) || !ws->d_small ||
+                      (int64_t)P->nbuf * P->W < ws->c_cap ||   // (the kept bin candidates go into per-bin segments of the y raster)
+                      ws->es != sizeof(T) || nb > ws->nb_max || nb > MAX_BINS_PER_SWEEP || n_slots > ws->s_cap ||
+                      (int64_t)(NKZ_CHUNK_MAX + 2) * P->W * (int64_t)sizeof(T) >= ((int64_t)1 << 32);   // (32-bit byte offsets inside a chunk of rows)
+        int64_t n_all = n;   // pixels of all ranks
+        if (mr && (world < 1 || !ctx->nk_fused_dist || !ctx->nk_fused)) return XDEMHIP_OK;   // (not told the ranks / switched off: context-level, the same on every rank)
+        if (mr) {
+            // Every rank must take the same route.  What the decision rests on is either fixed for the plan and its options or derives
+            // from reduced data (ext_ok), so the ranks agree ONCE -- a host all-reduce of (own pixels, "I cannot") -- and again whenever
+            // any of it changes, which it does on all ranks at the same step.
+            const int64_t key[8] = {nb, P->row0, P->row1, (int64_t)P->ext_ok, (int64_t)P->bin_stat, (int64_t)ctx->selection_mode,
+                                    (int64_t)(ctx->nk_fused * 4 + ctx->nk_fused_dist * 2), (int64_t)world * 64 + rank};
+            if (memcmp(key, P->mr_key, sizeof key) != 0) {
+                cannot = cannot || !ctx->nk_fused_dist || world < 1 || world > MR_WORLD_MAX || rank < 0 || rank >= world ||
+                         (int64_t)P->nbuf * P->W < ws->c_cap;
+                if (!cannot && nk_mr_alloc(P, nb, world, sizeof(T)) != XDEMHIP_OK) cannot = true;
+                uint64_t v[2] = {(uint64_t)n, (uint64_t)(cannot ? 1 : 0)};
+                const int rc_ = xd_allreduce_host(ctx, v, 2, XDEMHIP_RED_SUM_U64);
+                if (rc_) return rc_;
+                P->mr_nglob = (int64_t)v[0];
+                P->mr_can = v[1] == 0;
+                memcpy(P->mr_key, key, sizeof key);
+            }
+            if (!P->mr_can) return XDEMHIP_OK;
+            n_all = P->mr_nglob;
+            mrs = NkMrSmallLayout(P->mr_small, ws->nb_max);   // (allocated with the agreement: nk_mr_alloc)
+        } else if (cannot) {
+            return XDEMHIP_OK;
         }
-        if (!P->mr_can) return XDEMHIP_OK;
-        n_all = P->mr_nglob;
-    } else if (cannot) {
+        if (n_all < SEL_BRACKET_MIN_N || (ctx->selection_mode == 0 && n_all < SEL_BRACKET_MIN_PER_BIN * nb)) return XDEMHIP_OK;
+        *go = true;
         return XDEMHIP_OK;
     }
-    if (n_all < SEL_BRACKET_MIN_N || (ctx->selection_mode == 0 && n_all < SEL_BRACKET_MIN_PER_BIN * nb)) return XDEMHIP_OK;
-    unsigned char* scratch = static_cast<unsigned char*>(P->scratch);
-    T* d_edges = reinterpret_cast<T*>(scratch);
-    DhStats* d_stats = reinterpret_cast<DhStats*>(scratch + OFF_STATS);
-    BinCacheRec* d_rec = reinterpret_cast<BinCacheRec*>(scratch + OFF_INFO + 64);
-    const SelState<K>* d_st = reinterpret_cast<const SelState<K>*>(scratch + OFF_STATE);
-    const int nbm = ws->nb_max;
-    uint64_t* fz = P->fz;
-    unsigned long long* ctr = reinterpret_cast<unsigned long long*>(fz);   // [1] dh candidates, [2] overflow, [3] miss, [5] y candidates, [6] no survivor in an EXT list
-    uint32_t* rbs_d = reinterpret_cast<uint32_t*>(fz + 8);
-    uint32_t* rbs_y = reinterpret_cast<uint32_t*>(fz + 9);
-    uint64_t* cnt_d = fz + 10;
-    // (fz + 13: ranks of the dh selection, written and read on the device only)
-    K* klo_d = reinterpret_cast<K*>(fz + 14);
-    K* khi_d = reinterpret_cast<K*>(fz + 15);
-    T* d_vhat = reinterpret_cast<T*>(fz + 16);
-    T* d_delta = reinterpret_cast<T*>(fz + 17);
-    double* d_sums = reinterpret_cast<double*>(fz + 18);
-    K* klo_y = reinterpret_cast<K*>(fz + 24);
-    K* khi_y = reinterpret_cast<K*>(fz + 24 + nbm);
-    // (fz + 24 + 2 * nbm: ranks of the bin selections, device only)
-    uint64_t* cls_y = fz + 24 + 3 * nbm;
-    uint64_t* res_y = fz + 24 + 6 * nbm;
-    uint64_t* cnt_y = fz + 24 + 8 * nbm;
-    const bool custom = !P->custom_edges.empty();
-    const int last_decimal = custom ? P->custom_decimal : NK_AUTO_EDGES;
-    if (custom) {  // explicit bin edges: SciPy casts them to the sample dtype (rare path: a blocking copy)
-        std::vector<T> e(P->custom_edges.size());
-        for (size_t k = 0; k < e.size(); ++k) e[k] = (T)P->custom_edges[k];
-        XD_HIP_CHECK(ctx, hipMemcpyAsync(d_edges, e.data(), sizeof(T) * e.size(), hipMemcpyHostToDevice, ctx->stream));
-        { const int rc_ = xd_sync(ctx); if (rc_) return rc_; }
-    }
-    const T* ref_m = static_cast<const T*>(P->ref_m);
-    const T* tba = static_cast<const T*>(P->tba);
-    const T* st_all = static_cast<const T*>(P->slope_tan);
-    static_assert(MAX_BINS_PER_SWEEP <= NK_BINCACHE_MAX_BINS, "the one-pass step's bins fit the byte-wide cache");
-    // 1. min / max aspect of this step from the EXT lists -> edges, freshness of the bin cache; (re)fill of the cache
-    hipLaunchKernelGGL(nk_step_init_kernel, dim3(1), dim3(1024), 0, ctx->stream, d_stats, fz, (int64_t)(P->fz_bytes / 8), P->ext_cnt + 2);
-    hipLaunchKernelGGL((nk_ext_eval_kernel<T>), dim3(EXT_CAP / 256, 2), dim3(256), 0, ctx->stream, ref_m, tba, static_cast<const T*>(P->aspect), g,
-                       P->ext_idx, P->ext_cnt, d_stats, P->ext_cnt + 2);
-    int rc = XDEMHIP_OK;
-    // (partitioned plans: min / max aspect and the survivors of all ranks arrive with the first histogram all-reduce of the dh sample's
-    //  selection below -- per-rank slots behind its two histograms -- so the edges and the bin cache, which only the y^ sample and the
-    //  pass need, follow that selection)
-    uint64_t* ext_slots = reinterpret_cast<uint64_t*>(scratch + off_hist(2)) + 2 * SEL_RADIX;
-    if (mr) hipLaunchKernelGGL(nk_mr_ext_pack_kernel, dim3(1), dim3(64), 0, ctx->stream, d_stats, P->ext_cnt + 2, rank, world, ext_slots);
-    auto edges_and_bins = [&]() -> int {
+
+    // edges from the min / max aspect in d_stats, freshness of the bin cache, (re)fill of the cache
+    int edges_and_bins() {
         hipLaunchKernelGGL((nk_fz_prep_kernel<T>), dim3(1), dim3(64), 0, ctx->stream, d_stats, P->ext_cnt + 2, nb, (int)custom, d_edges, d_rec,
-                           (int)P->bcache_force, ctr);
+                           (int)P->bcache_force, fz.ctr);
         hipLaunchKernelGGL((nk_bin_fill_kernel<T>), dim3(grid_for(ctx, n, 256, 16)), dim3(256), sizeof(T) * (nb + 1), ctx->stream,
                            static_cast<const T*>(P->aspect) + q0, n, d_edges, nb, last_decimal, d_rec, P->bcache + q0);
         hipLaunchKernelGGL((nk_bin_cache_commit_kernel<T>), dim3(1), dim3(64), 0, ctx->stream, d_edges, nb, d_rec);
         XD_HIP_CHECK(ctx, hipGetLastError());
         P->bcache_force = false;
         return XDEMHIP_OK;
-    };
-    if (!mr) { rc = edges_and_bins(); if (rc) return rc; }
-    // Round 6: brackets PREDICTED from the previous step instead of sampled.  A bin median of y = (dh - vshift) / slope_tan moves by
-    // -(dE sin(aspect) + dN cos(aspect)) when the tap position moves by (dE, dN) pixels -- the Nuth-Kaab model itself -- and the
-    // median of dh stays to first order; how well that held is MEASURED at every step (pr_err: the worst miss of the centres in
-    // half widths of the sampled brackets, for the step just finished), and a step is predicted only when the last one would have
-    // been hit with room to spare and the shift change has not grown.  The brackets are then 0.25 ... 1 sampled widths around the
-    // predicted centres; the integer counts of the pass prove them like any sampled bracket, a miss reruns THIS step sampled
-    // (and the next one): exact either way.  Identical decisions on every rank of a partitioned plan (everything is derived from
-    // reduced results and the call's arguments).
-    const double dE = g.dc - P->pr_sx, dN = -(g.dr - P->pr_sy);   // (pr_sx / pr_sy hold the previous tap offsets in pixels)
-    const double dpx = sqrt(dE * dE + dN * dN);
-    // (the measured miss of the centres is proportional to the shift change -- 0.90 / 0.11 / 0.012 half widths at 0.2 / 0.02 / 0.002 px
-    //  on C3: the model's error is its second-order term -- so the miss to EXPECT at this step is the last one scaled by the ratio of
-    //  the shift changes, with a floor for the jitter of the medians themselves)
-    const bool pr_scaled = P->pr_dpx > 0 && P->pr_dpx < 1e29;
-    const double pr_expect = pr_scaled ? fmax(0.02, P->pr_err * (dpx / P->pr_dpx)) : 1e30;      // bin medians
-    const double pr_expect_d = pr_scaled ? fmax(0.02, P->pr_err_d * (dpx / P->pr_dpx)) : 1e30;  // median of dh (assumed not to move)
-    bool predict = allow_predict && ctx->nk_predict != 0 && P->pr_have && P->pr_nb == nb && nb <= NK_PREDICT_MAX_BINS && P->pr_cooldown == 0 &&
-                   pr_expect <= 0.20 && pr_expect_d <= 0.20 && dpx <= 0.05 && P->pr_wd > 0;
-    // ... and on steps that still move too far for the bins, the bracket of the MEDIAN OF DH alone may be predicted: that median
-    // hardly follows the shift (0.19 / 0.29 sampled half widths off at 0.1 / 0.5 px on C3), and without its three digit passes the y^
-    // sample can be taken straight away (the bins' brackets are sampled as ever)
-    const bool predict_d = !predict && allow_predict && ctx->nk_predict != 0 && P->pr_have && P->pr_nb == nb && P->pr_cooldown == 0 &&
-                           pr_expect_d <= 0.35 && dpx <= 0.6 && P->pr_wd > 0;
-    if (P->pr_cooldown > 0 && allow_predict) --P->pr_cooldown;
-    double pr_h = 1.0;   // bracket half widths of this step in sampled half widths
-    T* s_v = static_cast<T*>(ws->s_vals);
-    bool fused = false;
-    constexpr int BR_PASSES = 3;
-    const K low_mask = (K)(((K)1 << (8 * (KeyT<T>::passes - BR_PASSES))) - 1);
-    const int narrow = P->fz_narrow;
-    if (predict) {
-        pr_h = fmin(1.0, fmax(0.25, 2.0 * pr_expect + 0.15));
+    }
+    // partitioned plans: min / max aspect and the EXT survivors of all ranks, once their slots are reduced -> edges and bin cache
+    int edges_and_bins_of_all_ranks() {
+        hipLaunchKernelGGL(nk_mr_ext_unpack_kernel, dim3(1), dim3(64), 0, ctx->stream, ext_slots, world, d_stats, P->ext_cnt + 2);
+        return edges_and_bins();
+    }
+
+    // ---- 1. min / max aspect of this step from the EXT lists -> edges, freshness of the bin cache; (re)fill of the cache ---------
+    int stage_edges() {
+        if (custom) {  // explicit bin edges: SciPy casts them to the sample dtype (rare path: a blocking copy)
+            std::vector<T> e(P->custom_edges.size());
+            for (size_t k = 0; k < e.size(); ++k) e[k] = (T)P->custom_edges[k];
+            XD_HIP_CHECK(ctx, hipMemcpyAsync(d_edges, e.data(), sizeof(T) * e.size(), hipMemcpyHostToDevice, ctx->stream));
+            { const int rc_ = xd_sync(ctx); if (rc_) return rc_; }
+        }
+        static_assert(MAX_BINS_PER_SWEEP <= NK_BINCACHE_MAX_BINS, "the one-pass step's bins fit the byte-wide cache");
+        hipLaunchKernelGGL(nk_step_init_kernel, dim3(1), dim3(1024), 0, ctx->stream, d_stats, fz.base, fz.zeroed_words(fz.nbm), P->ext_cnt + 2);
+        hipLaunchKernelGGL((nk_ext_eval_kernel<T>), dim3(EXT_CAP / 256, 2), dim3(256), 0, ctx->stream, ref_m, tba, static_cast<const T*>(P->aspect), g,
+                           P->ext_idx, P->ext_cnt, d_stats, P->ext_cnt + 2);
+        // (partitioned plans: min / max aspect and the survivors of all ranks arrive with the first histogram all-reduce of the dh sample's
+        //  selection -- per-rank slots behind its two histograms -- so the edges and the bin cache, which only the y^ sample and the
+        //  pass need, follow that selection: edges_and_bins_of_all_ranks in the bracket stages)
+        if (mr) hipLaunchKernelGGL(nk_mr_ext_pack_kernel, dim3(1), dim3(64), 0, ctx->stream, d_stats, P->ext_cnt + 2, rank, world, ext_slots);
+        if (!mr) return edges_and_bins();
+        return XDEMHIP_OK;
+    }
+
+    // ---- 2 + 3, predicted: every bracket from the previous step's medians (NkPrediction::plan) -------------------------------------
+    int launch_predicted(int nb_pred) {
         NkPredicted<T> pr;
-        // (the bracket of the median of dh may not be padded: its half width is the margin delta / slope_tan of EVERY pixel's y, and on
-        //  flat ground a centimetre of it turns whole waves into bin candidates -- session r06h: overflow flag at 0.04 px)
-        const double hd = fmin(1.0, fmax(0.25, 2.0 * pr_expect_d + 0.15)) * P->pr_wd;
-        pr.dlo = (T)(P->pr_v - hd);
-        pr.dhi = (T)(P->pr_v + hd);
-        for (int b = 0; b < nb; ++b) {
-            if (!P->pr_ok[b]) { pr.lo[b] = (T)1; pr.hi[b] = (T)0; continue; }   // (an empty bin stays empty: the aspects do not move)
-            const double c = P->pr_med[b] - (dE * sin(P->pr_mid[b]) + dN * cos(P->pr_mid[b]));
-            const double h = pr_h * P->pr_w[b] + 0.05 * dpx;
-            pr.lo[b] = (T)(c - h);
-            pr.hi[b] = (T)(c + h);
-        }
-        if (mr) {   // min / max aspect and the EXT survivors of all ranks: their own small exchange (they ride on the dh sample's first histogram otherwise)
-            rc = xd_allreduce_device(ctx, ext_slots, 4 * (int64_t)world, XDEMHIP_RED_SUM_U64);
-            if (rc) return rc;
-            hipLaunchKernelGGL(nk_mr_ext_unpack_kernel, dim3(1), dim3(64), 0, ctx->stream, ext_slots, world, d_stats, P->ext_cnt + 2);
-            rc = edges_and_bins();
-            if (rc) return rc;
-        }
-        hipLaunchKernelGGL((nk_predict_kernel<T>), dim3(1), dim3(64), 0, ctx->stream, pr, nb, klo_d, khi_d, rbs_d, d_vhat, d_delta, klo_y, khi_y, rbs_y, ctr);
+        pr.dlo = (T)(P->pred.v - br.hd);
+        pr.dhi = (T)(P->pred.v + br.hd);
+        for (int b = 0; b < nb_pred; ++b) { pr.lo[b] = (T)br.lo[b]; pr.hi[b] = (T)br.hi[b]; }
+        hipLaunchKernelGGL((nk_predict_kernel<T>), dim3(1), dim3(64), 0, ctx->stream, pr, nb_pred, fz.klo_d, fz.khi_d, fz.rbs_d, fz.vhat, fz.delta, fz.klo_y,
+                           fz.khi_y, fz.rbs_y, fz.ctr);
         XD_HIP_CHECK(ctx, hipGetLastError());
-    } else {
-    // 2. sample of dh -> bracket of its median, v^, delta
-    // (round 5: the sample kernels also reset the selection that runs on their sample -- select_reset_slice)
-    if (!predict_d) {
+        return XDEMHIP_OK;
+    }
+    int stage_brackets_predicted() {
+        if (mr) {   // min / max aspect and the EXT survivors of all ranks: their own small exchange (they ride on the dh sample's first histogram otherwise)
+            { const int rc_ = xd_allreduce_device(ctx, ext_slots, 4 * (int64_t)world, XDEMHIP_RED_SUM_U64); if (rc_) return rc_; }
+            { const int rc_ = edges_and_bins_of_all_ranks(); if (rc_) return rc_; }
+        }
+        return launch_predicted(nb);
+    }
+
+    // ---- 2 + 3, sampled: sample of dh -> bracket of its median, v^, delta; then the bins' ----------------------------------------
+    // (the sample kernels also reset the selection that runs on their sample -- select_reset_slice; the passes advance their own
+    //  states and the last one writes the bracket ends -- hist_pass_kernel<T, true>; `fused` tells whether that form ran)
+    int stage_brackets_sampled() {
         hipLaunchKernelGGL((nk_sample_dh_kernel<T>), dim3(grid_for(ctx, n_slots, 256, 8)), dim3(256), 0, ctx->stream, ref_m, tba, g, q0, n,
                            1.0 / (double)P->W, n_slots, s_v, select_reset_plan<K>(scratch, 1, SEL_BRACKET_DUAL));
         XD_HIP_CHECK(ctx, hipGetLastError());
-    }
-    if (predict_d) {
-        // no dh sample in memory and no selection on it: the bracket comes from the previous median, and the y^ sample is formed
-        // straight from the rasters (nk_sample_dy_kernel below)
-        NkPredicted<T> pr;
-        const double hd = fmin(1.0, fmax(0.25, 2.0 * pr_expect_d + 0.15)) * P->pr_wd;
-        pr.dlo = (T)(P->pr_v - hd);
-        pr.dhi = (T)(P->pr_v + hd);
-        if (mr) {
-            rc = xd_allreduce_device(ctx, ext_slots, 4 * (int64_t)world, XDEMHIP_RED_SUM_U64);
-            if (rc) return rc;
-        }
-        hipLaunchKernelGGL((nk_predict_kernel<T>), dim3(1), dim3(64), 0, ctx->stream, pr, 0, klo_d, khi_d, rbs_d, d_vhat, d_delta, klo_y, khi_y, rbs_y, ctr);
-        XD_HIP_CHECK(ctx, hipGetLastError());
-    } else {
-    // (round 5: the passes advance their own states and the last one writes the bracket ends -- hist_pass_kernel<T, true>; `fused`
-    //  tells whether that form ran)
-    rc = select_enqueue<T>(ctx, s_v, nullptr, n_slots, n_slots, nullptr, 1, scratch, SEL_BRACKET_DUAL, nullptr, BR_PASSES, false, nullptr, nullptr,
-                           false, narrow, klo_d, khi_d, rbs_d, low_mask, &fused, true, mr ? 0 : -1, mr ? 4 * (int64_t)world : 0);
-    if (rc) return rc;
-    if (!fused) hipLaunchKernelGGL((bracket_finish_kernel<K>), dim3(1), dim3(64), 0, ctx->stream, d_st, 1, 0, low_mask, klo_d, khi_d, rbs_d);
-    }
-    if (mr) {
-        hipLaunchKernelGGL(nk_mr_ext_unpack_kernel, dim3(1), dim3(64), 0, ctx->stream, ext_slots, world, d_stats, P->ext_cnt + 2);
-        rc = edges_and_bins();
+        bool fused = false;
+        const int rc = select_enqueue<T>(ctx, s_v, nullptr, n_slots, n_slots, nullptr, 1, scratch, SEL_BRACKET_DUAL, nullptr, BR_PASSES, false, nullptr, nullptr,
+                                         false, narrow, fz.klo_d, fz.khi_d, fz.rbs_d, low_mask, &fused, true, mr ? 0 : -1, mr ? 4 * (int64_t)world : 0);
         if (rc) return rc;
+        if (!fused) hipLaunchKernelGGL((bracket_finish_kernel<K>), dim3(1), dim3(64), 0, ctx->stream, d_st, 1, 0, low_mask, fz.klo_d, fz.khi_d, fz.rbs_d);
+        return bin_brackets_sampled(false);
     }
-    // 3. sample of y^ per aspect bin -> brackets of the bin medians (round 5: v^ and delta formed by the sample kernel itself)
-    if (predict_d)
-        hipLaunchKernelGGL((nk_sample_dy_kernel<T>), dim3(grid_for(ctx, n_slots, 256, 8)), dim3(256), 0, ctx->stream, ref_m, tba, g, q0, n,
-                           1.0 / (double)P->W, n_slots, s_v, ws->s_bins, st_all + q0, P->bcache + q0, klo_d, khi_d, d_vhat, d_delta, ctr,
-                           select_reset_plan<K>(scratch, nb, SEL_BRACKET_DUAL));
-    else
-    hipLaunchKernelGGL((nk_sample_y_kernel<T>), dim3(grid_for(ctx, n_slots, 256, 8)), dim3(256), 0, ctx->stream, s_v, ws->s_bins, st_all + q0,
-                       P->bcache + q0, n, n_slots, d_vhat, klo_d, khi_d, d_vhat, d_delta, ctr, select_reset_plan<K>(scratch, nb, SEL_BRACKET_DUAL));
-    XD_HIP_CHECK(ctx, hipGetLastError());
-    rc = select_enqueue<T>(ctx, s_v, nb == 1 ? nullptr : ws->s_bins, n_slots, n_slots, nullptr, nb, scratch, SEL_BRACKET_DUAL, nullptr, BR_PASSES,
-                           false, nullptr, nullptr, false, narrow, klo_y, khi_y, rbs_y, low_mask, &fused, true);
-    if (rc) return rc;
-    if (!fused) hipLaunchKernelGGL((bracket_finish_kernel<K>), dim3(1), dim3(64), 0, ctx->stream, d_st, nb, 0, low_mask, klo_y, khi_y, rbs_y);
-    XD_HIP_CHECK(ctx, hipGetLastError());
-    }   // (sampled brackets)
-    // 4. the one pass
-    int n_wg = 0;
-    {
+
+    // ---- 3. sample of y^ per aspect bin -> brackets of the bin medians (v^ and delta formed by the sample kernel itself) ---------
+    // `from_rasters`: no dh sample in memory -- the y^ sample is formed straight from the rasters
+    int bin_brackets_sampled(bool from_rasters) {
+        if (mr) { const int rc_ = edges_and_bins_of_all_ranks(); if (rc_) return rc_; }
+        if (from_rasters)
+            hipLaunchKernelGGL((nk_sample_dy_kernel<T>), dim3(grid_for(ctx, n_slots, 256, 8)), dim3(256), 0, ctx->stream, ref_m, tba, g, q0, n,
+                               1.0 / (double)P->W, n_slots, s_v, ws->s_bins, st_all + q0, P->bcache + q0, fz.klo_d, fz.khi_d, fz.vhat, fz.delta, fz.ctr,
+                               select_reset_plan<K>(scratch, nb, SEL_BRACKET_DUAL));
+        else
+            hipLaunchKernelGGL((nk_sample_y_kernel<T>), dim3(grid_for(ctx, n_slots, 256, 8)), dim3(256), 0, ctx->stream, s_v, ws->s_bins, st_all + q0,
+                               P->bcache + q0, n, n_slots, fz.vhat, fz.klo_d, fz.khi_d, fz.vhat, fz.delta, fz.ctr, select_reset_plan<K>(scratch, nb, SEL_BRACKET_DUAL));
+        XD_HIP_CHECK(ctx, hipGetLastError());
+        bool fused = false;
+        const int rc = select_enqueue<T>(ctx, s_v, nb == 1 ? nullptr : ws->s_bins, n_slots, n_slots, nullptr, nb, scratch, SEL_BRACKET_DUAL, nullptr, BR_PASSES,
+                                         false, nullptr, nullptr, false, narrow, fz.klo_y, fz.khi_y, fz.rbs_y, low_mask, &fused, true);
+        if (rc) return rc;
+        if (!fused) hipLaunchKernelGGL((bracket_finish_kernel<K>), dim3(1), dim3(64), 0, ctx->stream, d_st, nb, 0, low_mask, fz.klo_y, fz.khi_y, fz.rbs_y);
+        XD_HIP_CHECK(ctx, hipGetLastError());
+        return XDEMHIP_OK;
+    }
+
+    // ---- 2 + 3, the bracket of the median of dh predicted: no dh sample and no selection on it; the bins' brackets sampled -------
+    int stage_brackets_dh_predicted() {
+        if (mr) { const int rc_ = xd_allreduce_device(ctx, ext_slots, 4 * (int64_t)world, XDEMHIP_RED_SUM_U64); if (rc_) return rc_; }
+        { const int rc_ = launch_predicted(0); if (rc_) return rc_; }
+        return bin_brackets_sampled(true);
+    }
+
+    // ---- 4. the one pass --------------------------------------------------------------------------------------------------------
+    int stage_pass() {
         dim3 grid = grid2d(ctx, P->W, rows);
         if ((rows + grid.y - 1) / grid.y > NKZ_CHUNK_MAX) grid.y = (unsigned)((rows + NKZ_CHUNK_MAX - 1) / NKZ_CHUNK_MAX);
         n_wg = (int)(grid.x * grid.y);
@@ -928,298 +897,236 @@ int nk_step_onepass(xdemhip_nk_plan* P, const NkGeom& g, int64_t q0, int64_t n, 
         copies = copies < 1 ? 1 : (copies > 16 ? 16 : copies);
         const size_t lds = (size_t)nb * sizeof(FzPair<T>) + (size_t)((3 * nb) | 1) * 4 * (size_t)copies + 64 * 4;
         T* cy_d = static_cast<T*>(ws->c_vals);
-#define XD_NK_FZ(RULE)                                                                                                               \
-    hipLaunchKernelGGL((nk_fused_kernel<T, RULE>), grid, dim3(256), lds, ctx->stream, ref_m, tba, st_all, P->bcache, g, P->row0, P->row1,  \
-                       P->nbuf, nb, copies, klo_d, khi_d, d_vhat, d_delta, klo_y, khi_y, cnt_d, cls_y, static_cast<T*>(P->cd_vals),   \
-                       P->cd_cap, cy_d, static_cast<T*>(P->c_st), ws->c_bins, ws->c_cap, ctr, P->wg_sums, P->badbits, P->bad_wpr)
+#define XD_NK_FZ(RULE)                                                                                                                     \
+    hipLaunchKernelGGL((nk_fused_kernel<T, RULE>), grid, dim3(256), lds, ctx->stream, ref_m, tba, st_all, P->bcache, g, P->row0, P->row1,        \
+                       P->nbuf, nb, copies, fz.klo_d, fz.khi_d, fz.vhat, fz.delta, fz.klo_y, fz.khi_y, fz.cnt_d, fz.cls_y,                       \
+                       static_cast<T*>(P->cd_vals), P->cd_cap, cy_d, static_cast<T*>(P->c_st), ws->c_bins, ws->c_cap, fz.ctr, P->wg_sums,        \
+                       P->badbits, P->bad_wpr)
         if (g.rule == 0) XD_NK_FZ(0);
         else if (g.rule == 1) XD_NK_FZ(1);
         else XD_NK_FZ(2);
 #undef XD_NK_FZ
         XD_HIP_CHECK(ctx, hipGetLastError());
+        // (few workgroups for the histogram / gather of the dh candidates: every one of them ends with an atomic on ONE word, which
+        //  serialise -- 256 workgroups with an atomic per wave spent 80 us there)
+        dsel_grid = grid_for(ctx, n / 32 + 1, HIST_THREADS * 8, 1);
+        dsel_grid = dsel_grid > 64 ? 64 : dsel_grid;
+        return XDEMHIP_OK;
     }
-    // (partitioned plans: this rank's classes, the counters rewritten for the gathered bucket values, the true counters of the bins)
-    uint64_t* cls_loc = mr ? P->mr_small : nullptr;
-    uint64_t* cls_f = mr ? cls_loc + 3 * nbm : nullptr;
-    uint64_t* res_f = mr ? cls_f + 3 * nbm : nullptr;
-    uint64_t* cnt_true = mr ? res_f + 2 * nbm : nullptr;
-    unsigned long long* segf_ctr = mr ? reinterpret_cast<unsigned long long*>(cnt_true + 3 * nbm) : nullptr;   // [nb] x BINSEG_CTR_STRIDE words
-    // (few workgroups for the histogram / gather of the dh candidates: every one of them ends with an atomic on ONE word, which
-    //  serialise -- 256 workgroups with an atomic per wave spent 80 us there)
-    int dsel_grid = grid_for(ctx, n / 32 + 1, HIST_THREADS * 8, 1);
-    dsel_grid = dsel_grid > 64 ? 64 : dsel_grid;
-    const int64_t words7 = 3 + 3 * (int64_t)nb + 5 * (int64_t)world;
-    uint32_t* mr_rows = mr ? reinterpret_cast<uint32_t*>(P->mr_a + words7) : nullptr;   // [world][DSEL_BUCKETS]
-    if (mr) {
+
+    // ---- 5. exact median of dh among its candidates -> vshift: value buckets of the bracket, three launches (nk_dhsel_*) ---------
+    static size_t dhsel_final_lds() {
+        return (size_t)DSEL_CAP * sizeof(K) + (size_t)(BINSEL_COPIES * (SEL_RADIX + 1) + 1) * 4 + (size_t)(SEL_RADIX + 4 + 16 + 2) * 8;
+    }
+    int stage_median_dh() {
+        const T* cd = static_cast<const T*>(P->cd_vals);
+        const size_t lds = dhsel_final_lds();
+        { const int rc_ = set_big_lds(ctx, nk_dhsel_final_kernel<T>, lds); if (rc_) return rc_; }
+        hipLaunchKernelGGL((nk_dhsel_hist_kernel<T>), dim3(dsel_grid), dim3(HIST_THREADS), 0, ctx->stream, cd, P->cd_cap, fz.ctr + 1, fz.klo_d, fz.khi_d,
+                           fz.dsel_hist(), P->wg_sums, n_wg, fz.sums);
+        hipLaunchKernelGGL((nk_dhsel_gather_kernel<T>), dim3(dsel_grid), dim3(HIST_THREADS), 0, ctx->stream, cd, P->cd_cap, fz.ctr + 1, fz.cnt_d, fz.klo_d,
+                           fz.khi_d, fz.dsel, fz.dsel_keys, fz.ctr);
+        hipLaunchKernelGGL((nk_dhsel_final_kernel<T>), dim3(1), dim3(HIST_THREADS), lds, ctx->stream, P->cd_cap, fz.ctr + 1, fz.cnt_d, fz.klo_d, fz.khi_d, fz.dsel,
+                           fz.dsel_keys, fz.ctr, scratch + OFF_INFO);
+        XD_HIP_CHECK(ctx, hipGetLastError());
+        return XDEMHIP_OK;
+    }
+    // ... on partitioned plans, behind the exchange of the pass's counters
+    int stage_median_dh_partitioned() {
+        const T* cd = static_cast<const T*>(P->cd_vals);
         // exchange 7: the pass's counters summed, the five float64 sums of every rank gathered and added in rank order -- and, in the
         // same all-reduce, the 4096-bucket histogram of this rank's dh candidates in its own row (the candidates and the bracket
         // are there once the pass is through; only the choice of the bucket needs the summed counters)
+        const int64_t words7 = 3 + 3 * (int64_t)nb + 5 * (int64_t)world;
+        uint32_t* mr_rows = reinterpret_cast<uint32_t*>(P->mr_a + words7);   // [world][DSEL_BUCKETS]
         XD_HIP_CHECK(ctx, hipMemsetAsync(mr_rows, 0, (size_t)world * DSEL_BUCKETS * 4, ctx->stream));
-        hipLaunchKernelGGL(nk_mr_counts_pack_kernel, dim3(1), dim3(256), 0, ctx->stream, cnt_d, cls_y, P->wg_sums, n_wg, nb, rank, world, P->mr_a, cls_loc);
-        hipLaunchKernelGGL((nk_dhsel_hist_kernel<T>), dim3(dsel_grid), dim3(HIST_THREADS), 0, ctx->stream, static_cast<const T*>(P->cd_vals), P->cd_cap, ctr + 1,
-                           klo_d, khi_d, mr_rows + (size_t)rank * DSEL_BUCKETS);
+        hipLaunchKernelGGL(nk_mr_counts_pack_kernel, dim3(1), dim3(256), 0, ctx->stream, fz.cnt_d, fz.cls_y, P->wg_sums, n_wg, nb, rank, world, P->mr_a,
+                           mrs.cls_loc);
+        hipLaunchKernelGGL((nk_dhsel_hist_kernel<T>), dim3(dsel_grid), dim3(HIST_THREADS), 0, ctx->stream, cd, P->cd_cap, fz.ctr + 1, fz.klo_d, fz.khi_d,
+                           mr_rows + (size_t)rank * DSEL_BUCKETS);
         XD_HIP_CHECK(ctx, hipGetLastError());
-        rc = xd_allreduce_device(ctx, P->mr_a, words7 + (int64_t)world * (DSEL_BUCKETS / 2), XDEMHIP_RED_SUM_U64);
-        if (rc) return rc;
-        hipLaunchKernelGGL(nk_mr_counts_unpack_kernel, dim3(1), dim3(256), 0, ctx->stream, P->mr_a, nb, world, cnt_d, cls_y, d_sums);
+        { const int rc_ = xd_allreduce_device(ctx, P->mr_a, words7 + (int64_t)world * (DSEL_BUCKETS / 2), XDEMHIP_RED_SUM_U64); if (rc_) return rc_; }
+        hipLaunchKernelGGL(nk_mr_counts_unpack_kernel, dim3(1), dim3(256), 0, ctx->stream, P->mr_a, nb, world, fz.cnt_d, fz.cls_y, fz.sums);
         XD_HIP_CHECK(ctx, hipGetLastError());
+        const size_t lds = dhsel_final_lds();
+        { const int rc_ = set_big_lds(ctx, nk_dhsel_final_kernel<T>, lds); if (rc_) return rc_; }
+        // (the rows of exchange 7) -> the global histogram, the bucket, this rank's offset in the bucket's key list
+        hipLaunchKernelGGL((nk_mr_dh_base_kernel<T>), dim3(1), dim3(HIST_THREADS), 0, ctx->stream, mr_rows, world, rank, fz.cnt_d, fz.klo_d, fz.khi_d, fz.dsel,
+                           fz.ctr);
+        // exchange 8: the bucket's keys of all ranks, each at its offset, + every rank's header words
+        uint64_t* slots = P->mr_b;
+        K* gk = reinterpret_cast<K*>(P->mr_b + (size_t)world * DSEL_HDR_WORDS);
+        const int64_t words8 = (int64_t)world * DSEL_HDR_WORDS + (int64_t)DSEL_CAP * (int64_t)sizeof(K) / 8;
+        XD_HIP_CHECK(ctx, hipMemsetAsync(P->mr_b, 0, (size_t)words8 * 8, ctx->stream));
+        hipLaunchKernelGGL((nk_dhsel_gather_kernel<T>), dim3(dsel_grid), dim3(HIST_THREADS), 0, ctx->stream, cd, P->cd_cap, fz.ctr + 1, fz.cnt_d, fz.klo_d,
+                           fz.khi_d, fz.dsel, gk, fz.ctr, 0);
+        hipLaunchKernelGGL(nk_mr_dh_hdr_pack_kernel, dim3(1), dim3(64), 0, ctx->stream, fz.dsel, rank, slots);
+        XD_HIP_CHECK(ctx, hipGetLastError());
+        { const int rc_ = xd_allreduce_device(ctx, P->mr_b, words8, XDEMHIP_RED_SUM_U64); if (rc_) return rc_; }
+        hipLaunchKernelGGL(nk_mr_dh_hdr_merge_kernel, dim3(1), dim3(64), 0, ctx->stream, slots, world, fz.dsel);
+        hipLaunchKernelGGL((nk_dhsel_final_kernel<T>), dim3(1), dim3(HIST_THREADS), lds, ctx->stream, P->cd_cap, fz.ctr + 1, fz.cnt_d, fz.klo_d, fz.khi_d, fz.dsel, gk,
+                           fz.ctr, scratch + OFF_INFO, 0);
+        XD_HIP_CHECK(ctx, hipGetLastError());
+        return XDEMHIP_OK;
     }
-    // 5. exact median of dh among its candidates -> vshift
-    {   // value buckets of the bracket, three launches (nk_dhsel_* above)
-        uint32_t* dsel = reinterpret_cast<uint32_t*>(fz + 24 + (11 + BINSEG_CTR_STRIDE) * nbm);
-        K* dsel_keys = reinterpret_cast<K*>(reinterpret_cast<unsigned char*>(fz) + P->fz_bytes);
-        const int grid = dsel_grid;
-        const size_t lds = (size_t)DSEL_CAP * sizeof(K) + (size_t)(BINSEL_COPIES * (SEL_RADIX + 1) + 1) * 4 + (size_t)(SEL_RADIX + 4 + 16 + 2) * 8;
-        rc = set_big_lds(ctx, nk_dhsel_final_kernel<T>, lds);
-        if (rc) return rc;
-        if (mr) {
-            // (the rows of exchange 7) -> the global histogram, the bucket, this rank's offset in the bucket's key list
-            hipLaunchKernelGGL((nk_mr_dh_base_kernel<T>), dim3(1), dim3(HIST_THREADS), 0, ctx->stream, mr_rows, world, rank, cnt_d, klo_d, khi_d, dsel, ctr);
-            // exchange 8: the bucket's keys of all ranks, each at its offset, + every rank's header words
-            uint64_t* slots = P->mr_b;
-            K* gk = reinterpret_cast<K*>(P->mr_b + (size_t)world * DSEL_HDR_WORDS);
-            const int64_t words8 = (int64_t)world * DSEL_HDR_WORDS + (int64_t)DSEL_CAP * (int64_t)sizeof(K) / 8;
-            XD_HIP_CHECK(ctx, hipMemsetAsync(P->mr_b, 0, (size_t)words8 * 8, ctx->stream));
-            hipLaunchKernelGGL((nk_dhsel_gather_kernel<T>), dim3(grid), dim3(HIST_THREADS), 0, ctx->stream, static_cast<const T*>(P->cd_vals), P->cd_cap, ctr + 1,
-                               cnt_d, klo_d, khi_d, dsel, gk, ctr, 0);
-            hipLaunchKernelGGL(nk_mr_dh_hdr_pack_kernel, dim3(1), dim3(64), 0, ctx->stream, dsel, rank, slots);
-            XD_HIP_CHECK(ctx, hipGetLastError());
-            rc = xd_allreduce_device(ctx, P->mr_b, words8, XDEMHIP_RED_SUM_U64);
-            if (rc) return rc;
-            hipLaunchKernelGGL(nk_mr_dh_hdr_merge_kernel, dim3(1), dim3(64), 0, ctx->stream, slots, world, dsel);
-            hipLaunchKernelGGL((nk_dhsel_final_kernel<T>), dim3(1), dim3(HIST_THREADS), lds, ctx->stream, P->cd_cap, ctr + 1, cnt_d, klo_d, khi_d, dsel, gk,
-                               ctr, scratch + OFF_INFO, 0);
-        } else {
-        hipLaunchKernelGGL((nk_dhsel_hist_kernel<T>), dim3(grid), dim3(HIST_THREADS), 0, ctx->stream, static_cast<const T*>(P->cd_vals), P->cd_cap, ctr + 1,
-                           klo_d, khi_d, dsel + 2 * DSEL_HDR_WORDS, P->wg_sums, n_wg, d_sums);
-        hipLaunchKernelGGL((nk_dhsel_gather_kernel<T>), dim3(grid), dim3(HIST_THREADS), 0, ctx->stream, static_cast<const T*>(P->cd_vals), P->cd_cap, ctr + 1,
-                           cnt_d, klo_d, khi_d, dsel, dsel_keys, ctr);
-        hipLaunchKernelGGL((nk_dhsel_final_kernel<T>), dim3(1), dim3(HIST_THREADS), lds, ctx->stream, P->cd_cap, ctr + 1, cnt_d, klo_d, khi_d, dsel, dsel_keys,
-                           ctr, scratch + OFF_INFO);
-        }
-        XD_HIP_CHECK(ctx, hipGetLastError());
-    }
-    // 6. the bin candidates with the exact vshift -> counts, exact medians among those inside the brackets
-    {
-        // round 5: kept values into per-bin segments (in the y raster, which this route does not use), one workgroup per bin selects
-        unsigned long long* seg_ctr = reinterpret_cast<unsigned long long*>(fz + 24 + 11 * nbm);   // [nb] x BINSEG_CTR_STRIDE words
+
+    // ---- 6. the bin candidates with the exact vshift -> counts, exact medians among those inside the brackets --------------------
+    // kept values into per-bin segments (in the y raster, which this route does not use), one workgroup per bin selects
+    void resolve_scatter() {
         const size_t lds = (size_t)nb * (3 * 8 + 2 * sizeof(K) + 3 * 4) + 16;
         hipLaunchKernelGGL((nk_resolve_scatter_kernel<T>), dim3(grid_for(ctx, n / 16 + 1, HIST_THREADS * BINSEG_U, 2)), dim3(HIST_THREADS), lds, ctx->stream,
-                           static_cast<const T*>(ws->c_vals), static_cast<const T*>(P->c_st), ws->c_bins, ws->c_cap, ctr + 5,
-                           reinterpret_cast<const T*>(scratch + OFF_INFO), nb, klo_y, khi_y, cls_y, res_y, seg_ctr, static_cast<T*>(P->y),
-                           (int64_t)P->nbuf * P->W, ctr, cls_loc);
-        const size_t lds2 = (size_t)BINSEL_KEY_BYTES + (size_t)(BINSEL_COPIES * (SEL_RADIX + 1) + 1) * 4 + (size_t)(SEL_RADIX + 8) * 8;
-        rc = set_big_lds(ctx, nk_bin_select_kernel<T>, lds2);
-        if (rc) return rc;
-        if (mr) {
-            // exchange 9: per bin the value-bucket histogram of this rank's segment, one row per rank; the resolved counters; local flags
-            const int64_t words9 = 2 + 2 * (int64_t)nb + (int64_t)world * nb * (SEL_RADIX / 2);
-            XD_HIP_CHECK(ctx, hipMemsetAsync(P->mr_a, 0, (size_t)words9 * 8, ctx->stream));
-            hipLaunchKernelGGL((nk_mr_bin_hist_kernel<T>), dim3(nb), dim3(HIST_THREADS), 0, ctx->stream, static_cast<const T*>(P->y), cls_loc, res_y, seg_ctr, nb, klo_y,
-                               khi_y, rank, world, P->mr_a, ctr);
-            XD_HIP_CHECK(ctx, hipGetLastError());
-            rc = xd_allreduce_device(ctx, P->mr_a, words9, XDEMHIP_RED_SUM_U64);
-            if (rc) return rc;
-            // exchange 10: per bin the chosen bucket's values of all ranks (+ each rank's smallest value above it)
-            const int64_t words10 = (int64_t)nb * MR_GSEG * (int64_t)sizeof(T) / 8;
-            XD_HIP_CHECK(ctx, hipMemsetAsync(P->mr_b, 0, (size_t)words10 * 8, ctx->stream));
-            hipLaunchKernelGGL((nk_mr_bin_gather_kernel<T>), dim3(nb), dim3(HIST_THREADS), 0, ctx->stream, static_cast<const T*>(P->y), cls_loc, cls_y, P->mr_a, seg_ctr, nb,
-                               klo_y, khi_y, rank, world, reinterpret_cast<T*>(P->mr_b), cls_f, res_f, segf_ctr, cnt_true, ctr);
-            XD_HIP_CHECK(ctx, hipGetLastError());
-            rc = xd_allreduce_device(ctx, P->mr_b, words10, XDEMHIP_RED_SUM_U64);
-            if (rc) return rc;
-            hipLaunchKernelGGL((nk_bin_select_kernel<T>), dim3(nb), dim3(HIST_THREADS), lds2, ctx->stream, reinterpret_cast<const T*>(P->mr_b), cls_f, res_f, segf_ctr,
-                               nb, klo_y, khi_y, rbs_y, reinterpret_cast<SelState<K>*>(scratch + OFF_STATE), reinterpret_cast<uint64_t*>(scratch + off_succ(nb)),
-                               cnt_y, ctr, (int64_t)MR_GSEG);
-        } else {
-        hipLaunchKernelGGL((nk_bin_select_kernel<T>), dim3(nb), dim3(HIST_THREADS), lds2, ctx->stream, static_cast<const T*>(P->y), cls_y, res_y, seg_ctr, nb,
-                           klo_y, khi_y, rbs_y, reinterpret_cast<SelState<K>*>(scratch + OFF_STATE), reinterpret_cast<uint64_t*>(scratch + off_succ(nb)),
-                           cnt_y, ctr);
-        }
-        XD_HIP_CHECK(ctx, hipGetLastError());
+                           static_cast<const T*>(ws->c_vals), static_cast<const T*>(P->c_st), ws->c_bins, ws->c_cap, fz.ctr + 5,
+                           reinterpret_cast<const T*>(scratch + OFF_INFO), nb, fz.klo_y, fz.khi_y, fz.cls_y, fz.res_y, fz.seg_ctr, static_cast<T*>(P->y),
+                           (int64_t)P->nbuf * P->W, fz.ctr, mrs.cls_loc);
     }
-    // 7. everything the step hands back: packed into one block on the device, one copy, one synchronisation
-    std::vector<uint64_t> cnt(3 * (size_t)nb);
-    std::vector<K> klo(nb);
-    std::vector<T> edges(nb + 1);
-    unsigned long long h_ctr[16];   // ctr[8] | rbs_d | rbs_y | cnt_d[3] (total, below, inside) | ...
-    uint64_t h_rbs = 0;
-    unsigned char info[32];
-    double sums[5];
-    T h_vhat = (T)0;
-    std::vector<SelState<K>> h_st(nb);
-    std::vector<uint64_t> h_succ(nb);
-    std::vector<uint64_t> cnt_t(mr ? 3 * (size_t)nb : 0);   // partitioned plans: (total, below, inside) of the bins' brackets (cnt holds the rewritten ones)
-    std::vector<K> khi(nb);
-    K h_kd[2] = {0, 0};   // bracket of the median of dh (the next step's prediction keeps the widths of the last sampled brackets)
-    const int n_pk = mr ? 14 : 13;
-    {
+    static size_t bin_select_lds() { return (size_t)BINSEL_KEY_BYTES + (size_t)(BINSEL_COPIES * (SEL_RADIX + 1) + 1) * 4 + (size_t)(SEL_RADIX + 8) * 8; }
+    int stage_bin_medians() {
+        resolve_scatter();
+        const size_t lds2 = bin_select_lds();
+        { const int rc_ = set_big_lds(ctx, nk_bin_select_kernel<T>, lds2); if (rc_) return rc_; }
+        hipLaunchKernelGGL((nk_bin_select_kernel<T>), dim3(nb), dim3(HIST_THREADS), lds2, ctx->stream, static_cast<const T*>(P->y), fz.cls_y, fz.res_y, fz.seg_ctr, nb,
+                           fz.klo_y, fz.khi_y, fz.rbs_y, reinterpret_cast<SelState<K>*>(scratch + OFF_STATE), reinterpret_cast<uint64_t*>(scratch + off_succ(nb)),
+                           fz.cnt_y, fz.ctr);
+        XD_HIP_CHECK(ctx, hipGetLastError());
+        return XDEMHIP_OK;
+    }
+    int stage_bin_medians_partitioned() {
+        resolve_scatter();
+        const size_t lds2 = bin_select_lds();
+        { const int rc_ = set_big_lds(ctx, nk_bin_select_kernel<T>, lds2); if (rc_) return rc_; }
+        // exchange 9: per bin the value-bucket histogram of this rank's segment, one row per rank; the resolved counters; local flags
+        const int64_t words9 = 2 + 2 * (int64_t)nb + (int64_t)world * nb * (SEL_RADIX / 2);
+        XD_HIP_CHECK(ctx, hipMemsetAsync(P->mr_a, 0, (size_t)words9 * 8, ctx->stream));
+        hipLaunchKernelGGL((nk_mr_bin_hist_kernel<T>), dim3(nb), dim3(HIST_THREADS), 0, ctx->stream, static_cast<const T*>(P->y), mrs.cls_loc, fz.res_y, fz.seg_ctr, nb,
+                           fz.klo_y, fz.khi_y, rank, world, P->mr_a, fz.ctr);
+        XD_HIP_CHECK(ctx, hipGetLastError());
+        { const int rc_ = xd_allreduce_device(ctx, P->mr_a, words9, XDEMHIP_RED_SUM_U64); if (rc_) return rc_; }
+        // exchange 10: per bin the chosen bucket's values of all ranks (+ each rank's smallest value above it)
+        const int64_t words10 = (int64_t)nb * MR_GSEG * (int64_t)sizeof(T) / 8;
+        XD_HIP_CHECK(ctx, hipMemsetAsync(P->mr_b, 0, (size_t)words10 * 8, ctx->stream));
+        hipLaunchKernelGGL((nk_mr_bin_gather_kernel<T>), dim3(nb), dim3(HIST_THREADS), 0, ctx->stream, static_cast<const T*>(P->y), mrs.cls_loc, fz.cls_y, P->mr_a,
+                           fz.seg_ctr, nb, fz.klo_y, fz.khi_y, rank, world, reinterpret_cast<T*>(P->mr_b), mrs.cls_f, mrs.res_f, mrs.segf_ctr, mrs.cnt_true, fz.ctr);
+        XD_HIP_CHECK(ctx, hipGetLastError());
+        { const int rc_ = xd_allreduce_device(ctx, P->mr_b, words10, XDEMHIP_RED_SUM_U64); if (rc_) return rc_; }
+        hipLaunchKernelGGL((nk_bin_select_kernel<T>), dim3(nb), dim3(HIST_THREADS), lds2, ctx->stream, reinterpret_cast<const T*>(P->mr_b), mrs.cls_f, mrs.res_f,
+                           mrs.segf_ctr, nb, fz.klo_y, fz.khi_y, fz.rbs_y, reinterpret_cast<SelState<K>*>(scratch + OFF_STATE),
+                           reinterpret_cast<uint64_t*>(scratch + off_succ(nb)), fz.cnt_y, fz.ctr, (int64_t)MR_GSEG);
+        XD_HIP_CHECK(ctx, hipGetLastError());
+        return XDEMHIP_OK;
+    }
+
+    // ---- 7. everything the step hands back: packed into one block on the device, one copy, one synchronisation -------------------
+    int stage_fetch() {
+        NkFetchItem t[NK_FETCH_MAX];
         FzPack pk;
-        void* dsts[14] = {cnt.data(), klo.data(), h_ctr, &h_rbs, info, sums, &h_vhat, edges.data(), h_st.data(), h_succ.data(), khi.data(), &h_kd[0], &h_kd[1],
-                          cnt_t.data()};
-        const void* srcs[14] = {cnt_y, klo_y, ctr, rbs_y, scratch + OFF_INFO, d_sums, d_vhat, d_edges, scratch + OFF_STATE, scratch + off_succ(nb), khi_y, klo_d,
-                                khi_d, cnt_true};
-        const size_t sizes[14] = {8 * 3 * (size_t)nb, sizeof(K) * nb, 128, 8, 32, 40, sizeof(T), sizeof(T) * (nb + 1), sizeof(SelState<K>) * nb, 8 * (size_t)nb,
-                                  sizeof(K) * nb, sizeof(K), sizeof(K), 8 * 3 * (size_t)nb};
-        uint32_t off = 0;
-        pk.n = n_pk;
-        for (int k = 0; k < n_pk; ++k) {
-            pk.src[k] = static_cast<const unsigned char*>(srcs[k]);
-            pk.bytes[k] = (uint32_t)sizes[k];
-            pk.off[k] = off;
-            off += (uint32_t)((sizes[k] + 15) & ~(size_t)15);
+        h.resize(nb, mr);
+        pk.n = h.table(fz, mrs, NkScratchSrc{scratch + OFF_INFO, d_edges, scratch + OFF_STATE, scratch + off_succ(nb)}, nb, mr, t);
+        const uint32_t total = (uint32_t)nk_fetch_offsets(t, pk.n, pk.off);
+        for (int k = 0; k < pk.n; ++k) {
+            pk.src[k] = static_cast<const unsigned char*>(t[k].src);
+            pk.bytes[k] = (uint32_t)t[k].bytes;
         }
-        if (off > P->fz_pack_bytes) return xd_fail(ctx, XDEMHIP_EINVAL, "one-pass step: result block too small");
-        P->fz_host.resize(off);
-        // (round 5: the block is written straight into the pinned staging buffer where there is room -- no copy behind the kernel)
-        unsigned char* pin = xd_pin_claim(ctx, P->fz_host.data(), off);
+        if (total > P->fz_pack_bytes) return xd_fail(ctx, XDEMHIP_EINVAL, "one-pass step: result block too small");
+        P->fz_host.resize(total);
+        // (the block is written straight into the pinned staging buffer where there is room -- no copy behind the kernel)
+        unsigned char* pin = xd_pin_claim(ctx, P->fz_host.data(), total);
         pk.dst = pin ? pin : P->fz_pack;
         hipLaunchKernelGGL(nk_fz_pack_kernel, dim3(1), dim3(256), 0, ctx->stream, pk);
         XD_HIP_CHECK(ctx, hipGetLastError());
-        if (!pin) { const int rc_ = xd_d2h(ctx, P->fz_host.data(), P->fz_pack, off); if (rc_) return rc_; }
+        if (!pin) { const int rc_ = xd_d2h(ctx, P->fz_host.data(), P->fz_pack, total); if (rc_) return rc_; }
         { const int rc_ = xd_sync(ctx); if (rc_) return rc_; }
-        for (int k = 0; k < n_pk; ++k) memcpy(dsts[k], P->fz_host.data() + pk.off[k], sizes[k]);
-    }
-    std::vector<SelResult<K>> hs(nb);
-    for (int k = 0; k < nb; ++k) { hs[k].st = h_st[k]; hs[k].succ = h_succ[k]; }
-    if ((h_ctr[2] != 0 || h_ctr[3] != 0) && getenv("XDEMHIP_DEBUG"))
-        fprintf(stderr, "[xdemhip] one-pass step falls through: overflow flag %llu, miss flag %llu, dh candidates %llu, bin candidates %llu\n", h_ctr[2], h_ctr[3],
-                h_ctr[1], h_ctr[5]);
-    if ((h_ctr[2] != 0 || h_ctr[3] != 0) && (predict || predict_d)) {
-        // a PREDICTED bracket missed (or overflowed): this step once more with sampled brackets, and the next one sampled too; the
-        // prediction has to earn its way back through a measured error
-        ++P->n_predict_miss;
-        P->pr_cooldown = 1;
-        P->pr_err = P->pr_err_d = 1e30;
-        return nk_step_onepass<T>(P, g, q0, n, nb, done, vshift, n_valid, y_mean, y_std, edges_out, counts, medians, false);
-    }
-    if (h_ctr[2] != 0 || h_ctr[3] != 0) {   // overflow / a bracket missed / no extreme-aspect survivor: the plain route takes the step
-        if (h_ctr[6] != 0) P->ext_ok = false;   // (no listed extreme-aspect pixel kept a finite dh: this plan reads the aspect from now on -- identical on every rank, the flag derives from reduced counts)
-        if (narrow > 0) {   // (narrowed brackets may be what missed: not that narrow again)
-            P->fz_unit_min = fmin(1.0, 1.5 * sel_narrow_unit((uint32_t)narrow));
-            P->fz_narrow = 0;
-        }
-        P->pr_have = false;
+        for (int k = 0; k < pk.n; ++k) memcpy(t[k].dst, P->fz_host.data() + pk.off[k], t[k].bytes);
         return XDEMHIP_OK;
     }
-    if (!predict) {
-        // How centred were the brackets?  |wanted rank - centre| in half widths, scaled to the full rule.  Lines of a sample that
-        // are not fully correlated (the rule's worst case) leave the ranks within a small fraction of it: the next step then takes
-        // brackets half or a quarter as wide -- fewer candidates staged, resolved and selected from (measured on C3: 1.88 -> 1.73
-        // -> 1.62 ms per step); a miss costs that step the plain route and caps the narrowing (exact either way).
-        auto off_of = [&](uint64_t tot, uint64_t lt, uint64_t in) {
-            return fabs(((double)(tot - 1) * 0.5 - (double)lt) - 0.5 * (double)in) / (0.5 * (double)in);
-        };
-        // (offsets are measured in half widths of the bracket that was used; all statistics are kept in units of the FULL rule)
-        const double unit = sel_narrow_unit((uint32_t)narrow);
-        double worst = 0.0;
-        auto take = [&](uint64_t tot, uint64_t lt, uint64_t in) {
-            if (tot < 4096 || in < 64 || in >= tot) return;
-            const double o = off_of(tot, lt, in) * unit;
-            worst = o > worst ? o : worst;
-            P->fz_off2 += o * o;
-            P->fz_offn += 1;
-        };
-        if (!predict_d) take(h_ctr[10], h_ctr[11], h_ctr[12]);   // (a predicted bracket says nothing about the centring of sample brackets)
+
+    // ---- 8. what the fetched integers say: a miss, or the step's numbers; the two policies learn from them -----------------------
+    int stage_interpret(const NkStepOut& out, NkOutcome* outcome) {
+        const unsigned long long* h_ctr = h.ctr();
+        const bool fell = h_ctr[2] != 0 || h_ctr[3] != 0;   // overflow / a bracket missed / no extreme-aspect survivor
+        if (fell && getenv("XDEMHIP_DEBUG"))
+            fprintf(stderr, "[xdemhip] one-pass step falls through: overflow flag %llu, miss flag %llu, dh candidates %llu, bin candidates %llu\n", h_ctr[2], h_ctr[3],
+                    h_ctr[1], h_ctr[5]);
+        if (fell && (br.predict || br.predict_d)) {
+            P->pred.on_miss();
+            *outcome = NK_STEP_AGAIN;
+            return XDEMHIP_OK;
+        }
+        if (fell) {
+            if (h_ctr[6] != 0) P->ext_ok = false;   // (no listed extreme-aspect pixel kept a finite dh: this plan reads the aspect from now on -- identical on every rank, the flag derives from reduced counts)
+            P->narrowing.on_miss(narrow);
+            P->pred.forget();
+            *outcome = NK_STEP_PLAIN;
+            return XDEMHIP_OK;
+        }
+        if (!br.predict) {   // (offsets are measured in half widths of the bracket that was used)
+            const double unit = sel_narrow_unit((uint32_t)narrow);
+            const std::vector<uint64_t>& c = mr ? h.cnt_t : h.cnt;
+            if (!br.predict_d) P->narrowing.observe(h.cnt_d()[0], h.cnt_d()[1], h.cnt_d()[2], unit);   // (a predicted bracket says nothing about the centring of sample brackets)
+            for (int b = 0; b < nb; ++b) P->narrowing.observe(c[b], c[nb + b], c[2 * nb + b], unit);
+            P->narrowing.choose_next(ctx->nk_narrow);
+        }
+        uint64_t total;
+        double vs;
+        memcpy(&total, h.info + 8, 8);
+        memcpy(&vs, h.info + 24, 8);
+        *out.n_valid = (int64_t)total;
+        if (total == 0) return xd_fail(ctx, XDEMHIP_EINVAL, "The subsample contains no more valid values.");
+        *out.vshift = vs;
+        const int rbs = (int)(uint32_t)h.rbs;
         for (int b = 0; b < nb; ++b) {
-            if (mr) take(cnt_t[b], cnt_t[nb + b], cnt_t[2 * nb + b]);
-            else take(cnt[b], cnt[nb + b], cnt[2 * nb + b]);
+            const uint64_t tot = h.cnt[b], lt = h.cnt[nb + b];
+            if (tot == 0) { out.counts[b] = 0; out.medians[b] = NAN; continue; }
+            SelResult<K> r;
+            r.st = h.st[b];
+            r.succ = h.succ[b];
+            r.st.count = tot;
+            r.st.n_le += lt;
+            r.st.prefix = (K)((K)(r.st.prefix >> rbs) + h.klo[b]);  // back from the rebased candidate keys
+            if (r.succ != ~(uint64_t)0) r.succ = (uint64_t)(K)((K)((K)r.succ >> rbs) + h.klo[b]);
+            out.counts[b] = (int64_t)tot;
+            out.medians[b] = median_from<T>(r);
         }
-        P->fz_worst = worst > P->fz_worst ? worst : P->fz_worst;
-        // rms offset = one standard deviation of the sample ranks in units of the full half width (independent sample elements:
-        // 1 / 17, the rule being 6 sigma of 8-element lines that are fully correlated; 0.062-0.068 measured on C3): the next brackets
-        // keep >= 4.8 sigma (a miss in 1e-4 of the steps with 73 brackets each -- it costs that step the plain route, nothing else) and
-        // >= 1.5 x the worst offset ever seen, in sixteenths of the rule.  (Rounds 4-5 halved or quartered only, at 7 sigma and 2.2 x:
-        // C3 sat at one half with 7.7 sigma of room; five sixteenths stage 38 % fewer candidates.)
-        int next = 0;
-        if (P->fz_offn >= 24) {
-            const double sigma = sqrt(P->fz_off2 / (double)P->fz_offn);
-            static const int qs[] = {4, 5, 6, 7, 8, 10, 12};
-            for (int q : qs) {
-                const double u = (double)q / 16.0;
-                if (4.8 * sigma <= u && 1.5 * P->fz_worst <= u && u >= P->fz_unit_min) { next = q == 8 ? 1 : (q == 4 ? 2 : (int)SEL_NARROW_16THS + q); break; }
-            }
-        }
-        if (ctx->nk_narrow >= 0) next = ctx->nk_narrow;   // option "nk_narrow": -1 = this rule, 0 / 1 / 2 fixed
-        if (getenv("XDEMHIP_DEBUG"))
-            fprintf(stderr, "[xdemhip] one-pass step: brackets x %.4f, offsets rms %.3f worst %.3f of the full half width (%lld brackets) -> next x %.4f\n", unit,
-                    P->fz_offn ? sqrt(P->fz_off2 / (double)P->fz_offn) : 0.0, P->fz_worst, (long long)P->fz_offn, sel_narrow_unit((uint32_t)next));
-        P->fz_narrow = next;
+        for (int k = 0; k <= nb; ++k) out.edges[k] = (double)h.edges[k];
+        // nanmean / nanstd of y from the sums of y^ and the first-order correction in (v^ - vshift)
+        const double dlt = (double)h.vhat - vs, cntd = (double)total;
+        const double s1 = h.sums[0] + dlt * h.sums[2];
+        const double s2 = h.sums[1] + 2.0 * dlt * h.sums[3] + dlt * dlt * h.sums[4];
+        const double mean = s1 / cntd, var = s2 / cntd - mean * mean;
+        *out.y_mean = mean;
+        *out.y_std = var > 0 ? sqrt(var) : 0.0;
+        std::vector<double> lo(nb), hi(nb);   // (keys are order preserving: the brackets' ends as values)
+        for (int b = 0; b < nb; ++b) { lo[b] = (double)val_of(h.klo[b]); hi[b] = (double)val_of(h.khi[b]); }
+        P->pred.record(br, g.dc, g.dr, nb, vs, out.medians, out.counts, out.edges, lo.data(), hi.data(), (double)val_of(h.kd[0]), (double)val_of(h.kd[1]), narrow);
+        *outcome = NK_STEP_DONE;
+        return XDEMHIP_OK;
     }
-    uint64_t total;
-    double vs;
-    memcpy(&total, info + 8, 8);
-    memcpy(&vs, info + 24, 8);
-    *n_valid = (int64_t)total;
-    if (total == 0) return xd_fail(ctx, XDEMHIP_EINVAL, "The subsample contains no more valid values.");
-    *vshift = vs;
-    const int rbs = (int)(uint32_t)h_rbs;
-    for (int b = 0; b < nb; ++b) {
-        const uint64_t tot = cnt[b], lt = cnt[nb + b];
-        if (tot == 0) { hs[b].st.count = 0; counts[b] = 0; medians[b] = NAN; continue; }
-        hs[b].st.count = tot;
-        hs[b].st.n_le += lt;
-        hs[b].st.prefix = (K)((K)(hs[b].st.prefix >> rbs) + klo[b]);  // back from the rebased candidate keys
-        if (hs[b].succ != ~(uint64_t)0) hs[b].succ = (uint64_t)(K)((K)((K)hs[b].succ >> rbs) + klo[b]);
-        counts[b] = (int64_t)tot;
-        medians[b] = median_from<T>(hs[b]);
+};
+
+// *done = false (nothing returned) when the route does not apply or when a bracket missed / a buffer overflowed: the caller
+// then runs the plain route, which needs nothing from here.  A PREDICTED bracket that missed sends the step round once more with
+// sampled brackets.
+template <typename T>
+int nk_step_onepass(xdemhip_nk_plan* P, const NkGeom& g, int64_t q0, int64_t n, int nb, bool* done, const NkStepOut& out) {
+    *done = false;
+    for (int trip = 0; trip < 2; ++trip) {
+        NkOnepass<T> s(P, g, q0, n, nb);
+        bool go = false;
+        { const int rc_ = s.eligible(&go); if (rc_ || !go) return rc_; }
+        { const int rc_ = s.stage_edges(); if (rc_) return rc_; }
+        // (the prediction's record holds the previous tap offsets in pixels)
+        s.br = P->pred.plan(g.dc - P->pred.sx, -(g.dr - P->pred.sy), nb, trip == 0, P->ctx->nk_predict);
+        // (the three forms are named in the order the step used to hold them: the compiler then emits their kernels in the same order,
+        //  and the device code of this file stays what it was byte for byte)
+        { const int rc_ = s.br.predict ? s.stage_brackets_predicted() : (!s.br.predict_d ? s.stage_brackets_sampled() : s.stage_brackets_dh_predicted()); if (rc_) return rc_; }
+        { const int rc_ = s.stage_pass(); if (rc_) return rc_; }
+        { const int rc_ = s.mr ? s.stage_median_dh_partitioned() : s.stage_median_dh(); if (rc_) return rc_; }
+        { const int rc_ = s.mr ? s.stage_bin_medians_partitioned() : s.stage_bin_medians(); if (rc_) return rc_; }
+        { const int rc_ = s.stage_fetch(); if (rc_) return rc_; }
+        NkOutcome outcome = NK_STEP_PLAIN;
+        { const int rc_ = s.stage_interpret(out, &outcome); if (rc_) return rc_; }
+        if (outcome != NK_STEP_AGAIN) { *done = outcome == NK_STEP_DONE; return XDEMHIP_OK; }
     }
-    for (int k = 0; k <= nb; ++k) edges_out[k] = (double)edges[k];
-    // nanmean / nanstd of y from the sums of y^ and the first-order correction in (v^ - vshift)
-    const double dlt = (double)h_vhat - vs, cntd = (double)total;
-    const double s1 = sums[0] + dlt * sums[2];
-    const double s2 = sums[1] + 2.0 * dlt * sums[3] + dlt * dlt * sums[4];
-    const double mean = s1 / cntd, var = s2 / cntd - mean * mean;
-    *y_mean = mean;
-    *y_std = var > 0 ? sqrt(var) : 0.0;
-    {
-        // Round 6: what the NEXT step's prediction rests on, and how well THIS step was (or would have been) predicted by the model
-        // "a bin median moves by -(dE sin(aspect) + dN cos(aspect))" (dE = change of the column offset of the taps, dN = minus the
-        // change of their row offset, pixels) and "the median of dh stays".  (Were the signs wrong for some layout, the measured
-        // misses would be large and no step would ever be predicted.)
-        std::vector<double> mid(nb);
-        for (int b = 0; b < nb; ++b) mid[b] = 0.5 * ((double)edges[b] + (double)edges[b + 1]);
-        if (P->pr_have && P->pr_nb == nb) {
-            double worst = 0.0;
-            for (int b = 0; b < nb; ++b) {
-                if (!P->pr_ok[b] || counts[b] == 0 || !(P->pr_w[b] > 0)) continue;
-                const double e = fabs(medians[b] - (P->pr_med[b] - (dE * sin(P->pr_mid[b]) + dN * cos(P->pr_mid[b])))) / P->pr_w[b];
-                worst = e > worst ? e : worst;
-            }
-            P->pr_err = worst;
-            P->pr_err_d = P->pr_wd > 0 ? fabs(vs - P->pr_v) / P->pr_wd : 1e30;
-            P->pr_dpx = fmax(dpx, 1e-5);   // (a repeated step measures the jitter floor: the ratio rule then stays conservative)
-            if (getenv("XDEMHIP_DEBUG"))
-                fprintf(stderr, "[xdemhip] one-pass step (%s, half widths x %.2f): shift change %.2e px, centres off by %.3f (bins) / %.3f (dh) sampled half widths\n",
-                        predict ? "PREDICTED brackets" : (predict_d ? "sampled brackets, PREDICTED bracket of the median of dh" : "sampled brackets"), pr_h, dpx, P->pr_err, P->pr_err_d);
-        } else {
-            P->pr_err = P->pr_err_d = 1e30;
-            P->pr_dpx = 1e30;
-        }
-        if (!predict || (int)P->pr_w.size() != nb) {   // the widths of SAMPLED brackets only (predicted ones are fractions of them)
-            // (kept in units of HALF the rule, the brackets the prediction's thresholds were tuned on: narrower sample brackets -- the
-            //  sixteenths above -- must not make the prediction shyer or its brackets thinner)
-            const double norm = narrow >= (int)SEL_NARROW_16THS ? 0.5 / sel_narrow_unit((uint32_t)narrow) : 1.0;
-            P->pr_w.assign(nb, 0.0);
-            for (int b = 0; b < nb; ++b)
-                if (counts[b] > 0 && khi[b] >= klo[b]) P->pr_w[b] = norm * 0.5 * ((double)val_of(khi[b]) - (double)val_of(klo[b]));
-            if (!predict_d) P->pr_wd = h_kd[1] >= h_kd[0] ? norm * 0.5 * ((double)val_of(h_kd[1]) - (double)val_of(h_kd[0])) : 0.0;
-        }
-        P->pr_med.assign(medians, medians + nb);
-        P->pr_mid = mid;
-        P->pr_ok.assign(nb, 0);
-        for (int b = 0; b < nb; ++b) P->pr_ok[b] = (counts[b] > 0 && P->pr_w[b] > 0 && std::isfinite(P->pr_w[b]) && std::isfinite(medians[b])) ? 1 : 0;
-        P->pr_v = vs;
-        P->pr_st = sums[2] > 0 ? cntd / sums[2] : 0.0;
-        P->pr_sx = g.dc;
-        P->pr_sy = g.dr;
-        P->pr_nb = nb;
-        P->pr_have = true;
-        if (predict) ++P->n_predicted;
-        if (predict_d) ++P->n_predicted_d;
-    }
-    *done = true;
-    return XDEMHIP_OK;
+    return XDEMHIP_OK;   // (not reached: the second trip predicts nothing)
 }
 
 template <typename T>
@@ -1258,7 +1165,7 @@ int nk_step_typed(xdemhip_nk_plan* P, double shift_x, double shift_y, double res
     }
     if (!fit_sums) {   // round 4: one data pass (14 B/pixel) where the plan and the step qualify; anything it cannot prove falls through
         bool done = false;
-        const int rc1 = nk_step_onepass<T>(P, g, q0, n, nb, &done, vshift, n_valid, y_mean, y_std, edges_out, counts, medians);
+        const int rc1 = nk_step_onepass<T>(P, g, q0, n, nb, &done, NkStepOut{vshift, n_valid, y_mean, y_std, edges_out, counts, medians});
         if (rc1) return rc1;
         if (done) { ++P->n_onepass; return XDEMHIP_OK; }
     }
@@ -1338,12 +1245,10 @@ int nk_step_typed(xdemhip_nk_plan* P, double shift_x, double shift_y, double res
         { const int rc_ = xd_d2h(ctx, info, base + OFF_INFO, 32); if (rc_) return rc_; }
         { const int rc_ = xd_sync(ctx); if (rc_) return rc_; }
     }
-    uint64_t total, flags;
+    uint64_t total;
     double vs;
     memcpy(&total, info + 8, 8);
-    memcpy(&flags, info + 16, 8);
     memcpy(&vs, info + 24, 8);
-    (void)flags;
     ++P->n_plain;
     *n_valid = (int64_t)total;
     if (total == 0) return xd_fail(ctx, XDEMHIP_EINVAL, "The subsample contains no more valid values.");
@@ -1536,13 +1441,12 @@ int nk_create_impl(xdemhip_ctx* ctx, const void* ref, const void* tba, const uin
     // one-pass step (large single-GPU plans with the EXT buffers): its device block and candidate buffers; without the memory the
     // plan keeps the plain route
     if (P->ref_m && P->ws.d_small && ctx->nk_fused != 0) {
-        // (... + places taken in the per-bin candidate segments: one line per bin; + header and histogram of the dh selection --
-        //  all zeroed at the start of a step; the keys of its chosen bucket sit behind, outside the zeroed part)
-        P->fz_bytes = (size_t)(24 + (11 + BINSEG_CTR_STRIDE) * P->ws.nb_max + DSEL_HDR_WORDS + DSEL_BUCKETS / 2) * 8;
+        // (the device block and the packed results: sized by what the step indexes them with -- nk_layout.h, NkStepResults::table)
         P->cd_cap = (int64_t)n / 8 + 4096;
-        P->fz_pack_bytes = (size_t)P->ws.nb_max * (8 * 3 + 8 + 16 + 64 + 8 + 8 * 3 + 16) + 1024;
+        P->fz_pack_bytes = dtype == XDEMHIP_F32 ? nk_fetch_bytes<float, uint32_t, SelState<uint32_t>>(P->ws.nb_max)
+                                                : nk_fetch_bytes<double, uint64_t, SelState<uint64_t>>(P->ws.nb_max);
         mem.optional();
-        P->fz = static_cast<uint64_t*>(mem.take(P->fz_bytes + (size_t)DSEL_CAP * 8, who));
+        P->fz = static_cast<uint64_t*>(mem.take(NkFzWords::total_bytes(P->ws.nb_max), who));
         P->cd_vals = mem.take((size_t)P->cd_cap * es, who);
         P->c_st = mem.take((size_t)P->ws.c_cap * es, who);
         P->fz_pack = mem.take<unsigned char>(P->fz_pack_bytes, who);
@@ -1563,14 +1467,40 @@ int nk_create_impl(xdemhip_ctx* ctx, const void* ref, const void* tba, const uin
             if (launched(ctx, "nk_badbits_kernel")) return fail(XDEMHIP_EHIP);
         }
     }
-    const xdemhip_allreduce_fn hook = ctx->allreduce;
-    if (!global_count) ctx->allreduce = nullptr;  // whole-raster plan: local pass; xdemhip_nk_set_rows re-partitions with the hook
-    int rc = dtype == XDEMHIP_F32 ? nk_aux_typed<float>(P) : nk_aux_typed<double>(P);
-    ctx->allreduce = hook;
+    int rc;
+    {
+        std::optional<XdLocalSelection> local;   // whole-raster plan: local pass; xdemhip_nk_set_rows re-partitions with the hook
+        if (!global_count) local.emplace(ctx);
+        rc = dtype == XDEMHIP_F32 ? nk_aux_typed<float>(P) : nk_aux_typed<double>(P);
+    }
     if (rc != XDEMHIP_OK) return fail(rc);
     if (n_valid) *n_valid = P->n_valid0;
     *out_plan = P;
     return XDEMHIP_OK;
+}
+
+// What the three step entry points share.  The message texts and the order in which each entry point checks its arguments are part
+// of the interface.
+static int nk_check_bins(xdemhip_nk_plan* P, int n_bins) {
+    if (n_bins < 1 || n_bins > P->max_bins) return xd_fail(P->ctx, XDEMHIP_EINVAL, "n_bins out of range (1..1024)");
+    // explicit edges fix the number of bins: the caller's output arrays are sized by ITS n_bins, so the two must agree
+    if (!P->custom_edges.empty() && n_bins != (int)P->custom_edges.size() - 1)
+        return xd_fail(P->ctx, XDEMHIP_EINVAL, "n_bins must equal the number of explicit bin edges - 1 (xdemhip_nk_set_bin_edges)");
+    return XDEMHIP_OK;
+}
+static int nk_check_resolution(xdemhip_ctx* ctx, double res_x, double res_y) {
+    if (!(res_x > 0) || !(res_y > 0)) return xd_fail(ctx, XDEMHIP_EINVAL, "resolution must be > 0");
+    return XDEMHIP_OK;
+}
+// the step itself between the context's two timing events; `typed(tag)` runs it for the sample type of `tag`
+template <typename F> static int nk_timed_step(xdemhip_nk_plan* P, F&& typed) {
+    xdemhip_ctx* ctx = P->ctx;
+    XD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    XD_HIP_CHECK(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
+    const int rc = P->dtype == XDEMHIP_F32 ? typed(float()) : typed(double());
+    (void)hipEventRecord(ctx->ev_stop, ctx->stream);
+    ctx->timed = (rc == XDEMHIP_OK);
+    return rc;
 }
 
 }  // namespace
@@ -1610,7 +1540,7 @@ int xdemhip_nk_set_rows(xdemhip_nk_plan* P, int64_t row_begin, int64_t row_end, 
     P->row0 = row_begin;
     P->row1 = row_end;
     P->bcache_force = true;  // other own rows: their bins were never cached
-    P->pr_have = false;      // ... and their medians are not the previous step's
+    P->pred.forget();        // ... and their medians are not the previous step's
     // valid mask / aux rasters outside the range are never read by this rank; recount the global number of valid pixels
     int rc = P->dtype == XDEMHIP_F32 ? nk_aux_typed<float>(P) : nk_aux_typed<double>(P);
     if (rc) return rc;
@@ -1641,8 +1571,8 @@ int xdemhip_nk_subsample(xdemhip_nk_plan* P, const int64_t* ranks, int64_t k, in
     P->inlier = P->sub_inlier;   // (an owned copy of the mask the plan was created with stays with the owner)
     // (as after xdemhip_nk_set_rows: other valid pixels -- no cached bins, no previous medians, no measured sample offsets)
     P->bcache_force = true;
-    P->pr_have = false;
-    P->fz_narrow = 0; P->fz_unit_min = 0.25; P->fz_worst = 0.0; P->fz_off2 = 0.0; P->fz_offn = 0;
+    P->pred.forget();
+    P->narrowing.reset();
     const int rc = P->dtype == XDEMHIP_F32 ? nk_aux_typed<float>(P) : nk_aux_typed<double>(P);
     if (rc) return rc;
     if (n_valid) *n_valid = P->n_valid0;
@@ -1651,9 +1581,9 @@ int xdemhip_nk_subsample(xdemhip_nk_plan* P, const int64_t* ranks, int64_t k, in
 
 int xdemhip_nk_predict_counts(xdemhip_nk_plan* P, int64_t* predicted, int64_t* predicted_dh_only, int64_t* missed) {
     if (!P) return XDEMHIP_EINVAL;
-    if (predicted) *predicted = P->n_predicted;
-    if (predicted_dh_only) *predicted_dh_only = P->n_predicted_d;
-    if (missed) *missed = P->n_predict_miss;
+    if (predicted) *predicted = P->pred.n_predicted;
+    if (predicted_dh_only) *predicted_dh_only = P->pred.n_predicted_d;
+    if (missed) *missed = P->pred.n_predict_miss;
     return XDEMHIP_OK;
 }
 
@@ -1689,19 +1619,11 @@ int xdemhip_nk_step(xdemhip_nk_plan* P, double shift_x, double shift_y, double r
     if (!P) return XDEMHIP_EINVAL;
     xdemhip_ctx* ctx = P->ctx;
     if (!vshift || !n_valid || !y_mean || !y_std || !edges || !counts || !medians) return xd_fail(ctx, XDEMHIP_EINVAL, "null output");
-    if (n_bins < 1 || n_bins > P->max_bins) return xd_fail(ctx, XDEMHIP_EINVAL, "n_bins out of range (1..1024)");
-    // explicit edges fix the number of bins: the caller's output arrays are sized by ITS n_bins, so the two must agree
-    if (!P->custom_edges.empty() && n_bins != (int)P->custom_edges.size() - 1)
-        return xd_fail(ctx, XDEMHIP_EINVAL, "n_bins must equal the number of explicit bin edges - 1 (xdemhip_nk_set_bin_edges)");
-    if (!(res_x > 0) || !(res_y > 0)) return xd_fail(ctx, XDEMHIP_EINVAL, "resolution must be > 0");
-    XD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    XD_HIP_CHECK(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
-    int rc = P->dtype == XDEMHIP_F32
-                 ? nk_step_typed<float>(P, shift_x, shift_y, res_x, res_y, n_bins, vshift, n_valid, y_mean, y_std, edges, counts, medians, nullptr)
-                 : nk_step_typed<double>(P, shift_x, shift_y, res_x, res_y, n_bins, vshift, n_valid, y_mean, y_std, edges, counts, medians, nullptr);
-    (void)hipEventRecord(ctx->ev_stop, ctx->stream);
-    ctx->timed = (rc == XDEMHIP_OK);
-    return rc;
+    { const int rc_ = nk_check_bins(P, n_bins); if (rc_) return rc_; }
+    { const int rc_ = nk_check_resolution(ctx, res_x, res_y); if (rc_) return rc_; }
+    return nk_timed_step(P, [&](auto tag) {
+        return nk_step_typed<decltype(tag)>(P, shift_x, shift_y, res_x, res_y, n_bins, vshift, n_valid, y_mean, y_std, edges, counts, medians, nullptr);
+    });
 }
 
 int xdemhip_nk_step_fit(xdemhip_nk_plan* P, double shift_x, double shift_y, double res_x, double res_y, double* vshift, int64_t* n_valid,
@@ -1710,15 +1632,10 @@ int xdemhip_nk_step_fit(xdemhip_nk_plan* P, double shift_x, double shift_y, doub
     if (!P) return XDEMHIP_EINVAL;
     xdemhip_ctx* ctx = P->ctx;
     if (!vshift || !n_valid || !y_mean || !y_std || !sums) return xd_fail(ctx, XDEMHIP_EINVAL, "null output");
-    if (!(res_x > 0) || !(res_y > 0)) return xd_fail(ctx, XDEMHIP_EINVAL, "resolution must be > 0");
-    XD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    XD_HIP_CHECK(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
-    int rc = P->dtype == XDEMHIP_F32
-                 ? nk_step_typed<float>(P, shift_x, shift_y, res_x, res_y, 72, vshift, n_valid, y_mean, y_std, nullptr, nullptr, nullptr, sums)
-                 : nk_step_typed<double>(P, shift_x, shift_y, res_x, res_y, 72, vshift, n_valid, y_mean, y_std, nullptr, nullptr, nullptr, sums);
-    (void)hipEventRecord(ctx->ev_stop, ctx->stream);
-    ctx->timed = (rc == XDEMHIP_OK);
-    return rc;
+    { const int rc_ = nk_check_resolution(ctx, res_x, res_y); if (rc_) return rc_; }
+    return nk_timed_step(P, [&](auto tag) {
+        return nk_step_typed<decltype(tag)>(P, shift_x, shift_y, res_x, res_y, 72, vshift, n_valid, y_mean, y_std, nullptr, nullptr, nullptr, sums);
+    });
 }
 
 int xdemhip_nk_step_values(xdemhip_nk_plan* P, double shift_x, double shift_y, double res_x, double res_y, int n_bins, double* vshift,
@@ -1727,25 +1644,18 @@ int xdemhip_nk_step_values(xdemhip_nk_plan* P, double shift_x, double shift_y, d
     if (!P) return XDEMHIP_EINVAL;
     xdemhip_ctx* ctx = P->ctx;
     if (!vshift || !n_valid || !y_mean || !y_std || !edges || !y_out || !bins_out) return xd_fail(ctx, XDEMHIP_EINVAL, "null output");
-    if (!(res_x > 0) || !(res_y > 0)) return xd_fail(ctx, XDEMHIP_EINVAL, "resolution must be > 0");
+    { const int rc_ = nk_check_resolution(ctx, res_x, res_y); if (rc_) return rc_; }
     if (memspace != XDEMHIP_HOST && memspace != XDEMHIP_DEVICE) return xd_fail(ctx, XDEMHIP_EINVAL, "memspace must be XDEMHIP_HOST or XDEMHIP_DEVICE");
-    if (n_bins < 1 || n_bins > P->max_bins) return xd_fail(ctx, XDEMHIP_EINVAL, "n_bins out of range (1..1024)");
-    if (!P->custom_edges.empty() && n_bins != (int)P->custom_edges.size() - 1)
-        return xd_fail(ctx, XDEMHIP_EINVAL, "n_bins must equal the number of explicit bin edges - 1 (xdemhip_nk_set_bin_edges)");
-    XD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    XD_HIP_CHECK(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
-    const int rc = P->dtype == XDEMHIP_F32
-                       ? nk_step_values<float>(P, shift_x, shift_y, res_x, res_y, n_bins, vshift, n_valid, y_mean, y_std, edges, y_out, bins_out, memspace)
-                       : nk_step_values<double>(P, shift_x, shift_y, res_x, res_y, n_bins, vshift, n_valid, y_mean, y_std, edges, y_out, bins_out, memspace);
-    (void)hipEventRecord(ctx->ev_stop, ctx->stream);
-    ctx->timed = (rc == XDEMHIP_OK);
-    return rc;
+    { const int rc_ = nk_check_bins(P, n_bins); if (rc_) return rc_; }
+    return nk_timed_step(P, [&](auto tag) {
+        return nk_step_values<decltype(tag)>(P, shift_x, shift_y, res_x, res_y, n_bins, vshift, n_valid, y_mean, y_std, edges, y_out, bins_out, memspace);
+    });
 }
 
 int xdemhip_nk_set_bin_edges(xdemhip_nk_plan* P, const double* edges, int n_edges, int decimal) {
     if (!P) return XDEMHIP_EINVAL;
     P->bcache_force = true;
-    P->pr_have = false;
+    P->pred.forget();
     if (n_edges == 0) { P->custom_edges.clear(); return XDEMHIP_OK; }
     if (!edges || n_edges < 2 || n_edges - 1 > MAX_BINS_PER_SWEEP) return xd_fail(P->ctx, XDEMHIP_EINVAL, "bin edges: 2 .. 129 increasing values");
     for (int k = 1; k < n_edges; ++k)
