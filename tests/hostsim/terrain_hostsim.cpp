@@ -75,7 +75,7 @@ static int go(const void* dem, int64_t H, int64_t W, int64_t ht, int64_t hb, int
         else run<0, false, true, Spec<MASK_SAH_WIN, 0, 1, 0, 1>, TIN, TOUT>(d, H, W, ht, hb, TH, P, out);
         return 0;
     }
-    // the small first-derivative sets of terrain_tile.h's XD_SMALL (lean tail, compile-time masks), every fit
+    // the small first-derivative sets of terrain_tile.h's small_kernel (lean tail, compile-time masks), every fit
     if (g_tail == 2 && !win && !curv && P.degrees && P.hs_zf2 == 1.0 && sizeof(TIN) == 4 && sizeof(TOUT) == 4) {
 #define SMALL(M)                                                                                                   \
     do {                                                                                                           \

@@ -527,21 +527,32 @@ def test_library_allocated_planes(terrain, backing):
         ctx.device_tensor((1 << 40,), "float32")   # 4 TiB
 
 
-@pytest.mark.parametrize("fit,attrs", [("Florinsky", "FULL"), ("ZevenbergThorne", "FULL"), ("Horn", "SAH_WIN")])
+# the small sets and the directional full set: one kernel family each, at the smallest raster that streams (8 x 8 interior tiles)
+# and one column narrower, where the plan falls back to tiles
+STREAM_SMALL = {"FULL_DIR": FULL, "SLOPE": ["slope"], "SLOPE_ASPECT": ["slope", "aspect"], "HILLSHADE": ["hillshade"],
+                "SAH": ["slope", "aspect", "hillshade"]}
+
+
+@pytest.mark.parametrize("fit,attrs", [("Florinsky", "FULL"), ("ZevenbergThorne", "FULL"), ("Horn", "SAH_WIN"),
+                                       ("Florinsky", "FULL_DIR"), ("ZevenbergThorne", "FULL_DIR"), ("Horn", "SLOPE"),
+                                       ("ZevenbergThorne", "SLOPE_ASPECT"), ("Florinsky", "HILLSHADE"), ("Florinsky", "SAH")])
 def test_streaming_strips_equal_tile_kernel_and_oracle(terrain, fit, attrs):
     """The streaming route of the specialised kernels (raster interior by wave-autonomous 64-column strips fed by LDS-DMA,
     frame of edge tiles by the tile kernel; context option "terrain_stream") runs the very same per-pixel code as the tile
     kernel: planes must be BIT-IDENTICAL with the route switched off, for every band height, with NaN / Inf holes straddling
     strip, band and ring-block boundaries, for row blocks with halo rows (the multi-GPU call) and for shapes whose last band
-    and frame are ragged; and equal to the oracle like every other configuration."""
+    and frame are ragged; and equal to the oracle like every other configuration.  Every kernel family that has strips is
+    here: the full sets with either curvature method, Horn's five planes and the four small sets."""
     import torch
 
     from xdem_amd import _lib
 
-    attrs = FULL if attrs == "FULL" else SAH_WIN
+    kw = dict(resolution=10.0, surface_fit=fit, curv_method="directional" if attrs == "FULL_DIR" else "geometric")
+    shapes = ((9 * 32 + 2, 9 * 256 + 4), (9 * 32 + 2, 9 * 256 + 3)) if attrs in STREAM_SMALL else ((1400, 2600), (2309, 1801), (1153, 4100))
+    attrs = STREAM_SMALL.get(attrs) or (FULL if attrs == "FULL" else SAH_WIN)
     ctx = _lib.default_context()
     rng = np.random.default_rng(7)
-    for shape in ((1400, 2600), (2309, 1801), (1153, 4100)):
+    for shape in shapes:
         dem = _dem(shape, seed=shape[0])
         # holes: single pixels, a block across a 64-column strip border and a 128-row band border, +-Inf, a whole row piece
         for _ in range(40):
@@ -549,14 +560,14 @@ def test_streaming_strips_equal_tile_kernel_and_oracle(terrain, fit, attrs):
         dem[30:36, 310:330] = np.nan
         dem[158:163, 572:580] = np.nan
         dem[287:290, 255:258] = np.inf
-        dem[600, 700:900] = np.nan
+        dem[min(600, shape[0] - 90), 700:900] = np.nan
         dem[shape[0] - 40, shape[1] - 300] = -np.inf
         d = torch.from_numpy(dem).cuda()
         ref_planes = None
         try:
             for stream in (0, 1, 128, 256, 512):
                 ctx.set_option("terrain_stream", stream)
-                out = terrain.terrain_attributes_device(d, attrs, resolution=10.0, surface_fit=fit)
+                out = terrain.terrain_attributes_device(d, attrs, **kw)
                 torch.cuda.synchronize()
                 got = out.cpu().numpy()
                 if stream == 0:
@@ -571,7 +582,7 @@ def test_streaming_strips_equal_tile_kernel_and_oracle(terrain, fit, attrs):
                 try:
                     ctx.set_option("terrain_order", order)
                     ctx.set_option("terrain_ring_wait", wait)
-                    got = terrain.terrain_attributes_device(d, attrs, resolution=10.0, surface_fit=fit)
+                    got = terrain.terrain_attributes_device(d, attrs, **kw)
                     torch.cuda.synchronize()
                     got = got.cpu().numpy()
                 finally:
@@ -581,17 +592,17 @@ def test_streaming_strips_equal_tile_kernel_and_oracle(terrain, fit, attrs):
                     assert np.array_equal(got[i], ref_planes[i], equal_nan=True), (shape, "order", order, "wait", wait, a)
             # row block with halo rows: rows [r0, r1) of the raster from a buffer holding depth rows either side
             r0, r1, depth = 96, shape[0] - 70, 2
-            blk = terrain.terrain_attributes_device(d[r0 - depth:r1 + depth], attrs, resolution=10.0, surface_fit=fit,
+            blk = terrain.terrain_attributes_device(d[r0 - depth:r1 + depth], attrs, **kw,
                                                     halo_top=depth, halo_bottom=depth)
-            top = terrain.terrain_attributes_device(d[:r1 + depth], attrs, resolution=10.0, surface_fit=fit, halo_bottom=depth)
+            top = terrain.terrain_attributes_device(d[:r1 + depth], attrs, **kw, halo_bottom=depth)
             torch.cuda.synchronize()
             for i, a in enumerate(attrs):
                 assert np.array_equal(blk[i].cpu().numpy(), ref_planes[i][r0:r1], equal_nan=True), (shape, "block", a)
                 assert np.array_equal(top[i].cpu().numpy(), ref_planes[i][:r1], equal_nan=True), (shape, "top block", a)
         finally:
             ctx.set_option("terrain_stream", 1)
-        if shape == (1400, 2600):
-            ref = to.terrain_attributes(dem, attrs, resolution=10.0, surface_fit=fit)
+        if shape == shapes[0]:
+            ref = to.terrain_attributes(dem, attrs, **kw)
             for a, g, r in zip(attrs, ref_planes, ref):
                 check_attribute(g, r, a, dem, 10.0, f"{fit}/{a}")
 

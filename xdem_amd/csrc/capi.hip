@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "common.h"
+#include "terrain_route.h"
 
 #define XDEMHIP_VERSION_NUM 100
 
@@ -416,233 +417,36 @@ int xdemhip_fractal_constants(int window_size, int max_q, int* q, double* log_q,
     return n;
 }
 
-static int popcount32(uint32_t v) { return __builtin_popcount(v); }
-
+// Validate, describe the call, then the device route (one launch on the caller's arrays) or the host route (terrain_host.hip)
 int xdemhip_terrain(xdemhip_ctx* ctx, const void* dem, int dem_dtype, int64_t H, int64_t W, int64_t row_stride,
                     int64_t halo_top, int64_t halo_bottom, double resolution, int surface_fit, int curv_method,
                     uint32_t attr_mask, int tri_method, int window_size, double hs_alt, double hs_az, double hs_z,
                     int degrees, int out_dtype, void* const* out_planes, int memspace) {
     if (!ctx) return XDEMHIP_EINVAL;
-    if (!dem || !out_planes) return xd_fail(ctx, XDEMHIP_EINVAL, "null buffer");
-    if (H <= 0 || W <= 0 || row_stride < W || halo_top < 0 || halo_bottom < 0)
-        return xd_fail(ctx, XDEMHIP_EINVAL, "bad raster geometry");
-    if ((dem_dtype != XDEMHIP_F32 && dem_dtype != XDEMHIP_F64) || (out_dtype != XDEMHIP_F32 && out_dtype != XDEMHIP_F64))
-        return xd_fail(ctx, XDEMHIP_EINVAL, "dtype must be XDEMHIP_F32 or XDEMHIP_F64");
-    if (surface_fit < 0 || surface_fit > 2) return xd_fail(ctx, XDEMHIP_EINVAL, "unknown surface_fit");
-    if (curv_method < 0 || curv_method > 1) return xd_fail(ctx, XDEMHIP_EINVAL, "unknown curv_method");
-    if (tri_method < 0 || tri_method > 1) return xd_fail(ctx, XDEMHIP_EINVAL, "unknown tri_method");
-    if (attr_mask == 0 || (attr_mask >> XDEMHIP_ATTR_COUNT)) return xd_fail(ctx, XDEMHIP_EINVAL, "bad attr_mask");
-    const uint32_t curv_bits = attr_mask & 0x3f8u;
-    if (surface_fit == XDEMHIP_FIT_HORN && curv_bits)
-        return xd_fail(ctx, XDEMHIP_EINVAL, "'Horn' surface fit cannot be used to calculate curvatures");
-    if ((attr_mask & 0x5c00u) && (window_size < 3 || (window_size & 1) == 0 || window_size > 1023))
-        return xd_fail(ctx, XDEMHIP_EINVAL, "window_size must be odd and >= 3");
-    const uint32_t needs_res = 0x3ffu | XDEMHIP_ATTR_RUGOSITY;  // surface fit + rugosity (terrain.py:352-367)
-    if ((attr_mask & needs_res) && !(resolution > 0.0) ) return xd_fail(ctx, XDEMHIP_EINVAL, "resolution must be > 0");
-    if (memspace != XDEMHIP_HOST && memspace != XDEMHIP_DEVICE) return xd_fail(ctx, XDEMHIP_EINVAL, "bad memspace");
-
+    const xd::TerrainCheck check = xd::terrain_validate(dem, out_planes, dem_dtype, H, W, row_stride, halo_top, halo_bottom, resolution,
+                                                        surface_fit, curv_method, attr_mask, tri_method, window_size, out_dtype, memspace);
+    if (check.code != XDEMHIP_OK) return xd_fail(ctx, check.code, check.msg);
     XD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    const int n_planes = popcount32(attr_mask);
-    for (int i = 0; i < n_planes; ++i)
+    for (int i = 0; i < __builtin_popcount(attr_mask); ++i)
         if (!out_planes[i]) return xd_fail(ctx, XDEMHIP_EINVAL, "null output plane");
 
     xd::TerrainLaunch L;
     memset(&L, 0, sizeof L);
     L.dem_dtype = dem_dtype; L.out_dtype = out_dtype;
     L.H = H; L.W = W; L.row_stride = row_stride; L.halo_top = halo_top; L.halo_bottom = halo_bottom;
-    L.resolution = (attr_mask & needs_res) ? resolution : 1.0;
+    L.resolution = (attr_mask & xd::ATTRS_NEED_RESOLUTION) ? resolution : 1.0;
     L.surface_fit = surface_fit; L.curv_method = curv_method; L.tri_method = tri_method;
     L.window_size = window_size; L.degrees = degrees & 1; L.hs_unclipped = (degrees >> 1) & 1; L.attr_mask = attr_mask;
     L.hs_alt = hs_alt; L.hs_az = hs_az; L.hs_z = hs_z;
+    if (memspace == XDEMHIP_HOST) return xd::terrain_host(ctx, L, dem, out_planes);
 
-    const size_t in_es = dem_dtype == XDEMHIP_F32 ? 4 : 8, out_es = out_dtype == XDEMHIP_F32 ? 4 : 8;
-
-    if (memspace == XDEMHIP_DEVICE) {
-        L.dem = dem;
-        for (int bit = 0, i = 0; bit < XDEMHIP_ATTR_COUNT; ++bit)
-            if (attr_mask & (1u << bit)) L.planes[bit] = out_planes[i++];
-        XD_HIP_CHECK(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
-        int rc = xd::launch_terrain(ctx, L);
-        XD_HIP_CHECK(ctx, hipEventRecord(ctx->ev_stop, ctx->stream));
-        ctx->timed = (rc == XDEMHIP_OK);
-        return rc;
-    }
-
-    // Host buffers: the raster streams through the device in ROW CHUNKS with the overlap the requested attributes need (the GPU
-    // analogue of the reference's map_overlap tiles, xdem/terrain/terrain.py:412-466): device memory stays bounded however
-    // large the host raster is, and a chunk is computed exactly as the same rows of the whole raster (halo_top / halo_bottom
-    // of the kernels).  Round 3: a double-buffered pipeline over PINNED staging buffers owned by the context --
-    //   copy threads: caller's rows -> pinned in[k & 1]      |  H2D (copy stream 0)  |  kernels (context stream)
-    //   D2H (copy stream 1) -> pinned out[k & 1]             |  copy threads: pinned out -> caller's planes
-    // with chunk k's transfers and kernels running while the threads move chunk k - 1's planes into the caller's (pageable,
-    // often never-touched) arrays: the PCIe link stays busy in both directions instead of idling behind a pageable copy.
-    int depth = 0;  // overlap rows per side
-    if (attr_mask & 0x3ffu) depth = surface_fit == XDEMHIP_FIT_FLORINSKY ? 2 : 1;
-    if ((attr_mask & 0x5c00u) && window_size / 2 > depth) depth = window_size / 2;
-    if ((attr_mask & XDEMHIP_ATTR_RUGOSITY) && depth < 1) depth = 1;
-    // chunk size: ~256 MiB of output planes per chunk by default (deep enough to hide latencies, small enough to pipeline),
-    // capped by option "host_chunk_mb" (the device / pinned budget of one chunk, input + planes)
-    const size_t row_bytes = (size_t)W * (in_es + out_es * (size_t)n_planes);
-    const size_t budget = (size_t)(ctx->host_chunk_mb > 0 ? ctx->host_chunk_mb : 288) << 20;
-    int64_t chunk = (int64_t)(budget / (row_bytes ? row_bytes : 1)) - 2 * depth;
-    // the caller's tile size (mp_config.chunk_size of the reference's tiled call) can only SHRINK the chunks: a tile of the whole raster's
-    // height -- or a moderate one on a very wide raster -- would otherwise put input + all planes of the raster on the device and
-    // fail with ENOMEM where the untiled call streams
-    if (ctx->host_chunk_rows > 0 && ctx->host_chunk_rows < chunk) chunk = ctx->host_chunk_rows;
-    if (chunk < 64) chunk = 64;  // (a few rows of a very wide raster may exceed the budget; still correct)
-    if (chunk > H) chunk = H;
-    size_t in_bytes = 0, plane_bytes = 0, out_bytes = 0;
-    auto size_chunk = [&]() {
-        in_bytes = (size_t)(chunk + 2 * depth) * (size_t)W * in_es;
-        plane_bytes = (size_t)chunk * (size_t)W * out_es;
-        out_bytes = plane_bytes * (size_t)n_planes;
-    };
-    size_chunk();
-    void* d_in[2] = {nullptr, nullptr};
-    void* d_out[2] = {nullptr, nullptr};
-    hipEvent_t ev_in[2] = {nullptr, nullptr}, ev_comp[2] = {nullptr, nullptr}, ev_out[2] = {nullptr, nullptr};
-    int rc = XDEMHIP_OK;
-    auto cleanup = [&]() {
-        for (int q = 0; q < 2; ++q) {
-            if (d_in[q]) (void)hipFree(d_in[q]);
-            if (d_out[q]) (void)hipFree(d_out[q]);
-            if (ev_in[q]) (void)hipEventDestroy(ev_in[q]);
-            if (ev_comp[q]) (void)hipEventDestroy(ev_comp[q]);
-            if (ev_out[q]) (void)hipEventDestroy(ev_out[q]);
-        }
-    };
-    // pinned staging, kept by the context between calls (pinning hundreds of MiB costs more than moving them).  The budget sizes
-    // 2 x (input + planes) of pinned host memory AND the same of device memory; where the host cannot pin that much the chunk is
-    // halved until it can (down to 64 rows) instead of failing the call.  Option "host_release" frees the staging buffers.
-    if (ctx->stage_in_bytes < in_bytes || ctx->stage_out_bytes < out_bytes) {
-        auto drop_staging = [&]() {
-            for (int q = 0; q < 2; ++q) {
-                if (ctx->stage_in[q]) (void)hipHostFree(ctx->stage_in[q]);
-                if (ctx->stage_out[q]) (void)hipHostFree(ctx->stage_out[q]);
-                ctx->stage_in[q] = ctx->stage_out[q] = nullptr;
-            }
-            ctx->stage_in_bytes = ctx->stage_out_bytes = 0;
-        };
-        for (;;) {
-            drop_staging();
-            bool ok = true;
-            for (int q = 0; q < 2 && ok; ++q)
-                ok = hipHostMalloc(&ctx->stage_in[q], in_bytes, hipHostMallocDefault) == hipSuccess &&
-                     hipHostMalloc(&ctx->stage_out[q], out_bytes, hipHostMallocDefault) == hipSuccess;
-            if (ok) break;
-            (void)hipGetLastError();
-            drop_staging();
-            if (chunk <= 64) return xd_fail(ctx, XDEMHIP_ENOMEM, "hipHostMalloc(staging) failed even for 64-row chunks");
-            chunk = chunk / 2 < 64 ? 64 : chunk / 2;
-            size_chunk();
-        }
-        ctx->stage_in_bytes = in_bytes;
-        ctx->stage_out_bytes = out_bytes;
-    }
-    for (int q = 0; q < 2; ++q) {
-        if (hipMalloc(&d_in[q], in_bytes) != hipSuccess || hipMalloc(&d_out[q], out_bytes) != hipSuccess ||
-            hipEventCreateWithFlags(&ev_in[q], hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&ev_comp[q], hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&ev_out[q], hipEventDisableTiming) != hipSuccess) {
-            cleanup();
-            return xd_fail(ctx, XDEMHIP_ENOMEM, "hipMalloc / hipEventCreate (host path) failed");
-        }
-    }
-    L.row_stride = W;
-    const int nthreads = ctx->host_copy_threads;
-    hipStream_t s_h2d = ctx->copy_streams[0], s_d2h = ctx->copy_streams[1];
-    // `nthreads` threads, each copying its share of the byte ranges handed to it (caller's memory is pageable; fresh output
-    // pages fault on first touch: both want many threads)
-    struct Span { char* dst; const char* src; size_t bytes; };
-    auto parallel_copy = [&](const std::vector<Span>& spans) {
-        size_t total = 0;
-        for (const Span& sp : spans) total += sp.bytes;
-        if (total < ((size_t)4 << 20) || nthreads <= 1) {
-            for (const Span& sp : spans) memcpy(sp.dst, sp.src, sp.bytes);
-            return;
-        }
-        std::vector<std::thread> workers;
-        const size_t per = (total + (size_t)nthreads - 1) / (size_t)nthreads;
-        for (int t = 0; t < nthreads; ++t)
-            workers.emplace_back([&, t]() {
-                size_t lo = per * (size_t)t, hi = lo + per < total ? lo + per : total, pos = 0;
-                for (const Span& sp : spans) {
-                    const size_t a = pos > lo ? pos : lo, b = pos + sp.bytes < hi ? pos + sp.bytes : hi;
-                    if (b > a) memcpy(sp.dst + (a - pos), sp.src + (a - pos), b - a);
-                    pos += sp.bytes;
-                    if (pos >= hi) break;
-                }
-            });
-        for (auto& w : workers) w.join();
-    };
-    struct ChunkGeom { int64_t r0, r1, top, bot; };
-    std::vector<ChunkGeom> chunks;
-    for (int64_t r0 = 0; r0 < H; r0 += chunk) {
-        ChunkGeom g;
-        g.r0 = r0; g.r1 = (r0 + chunk < H) ? r0 + chunk : H;
-        // rows of the caller's buffer (which itself may carry halo rows) available above / below this chunk
-        g.top = (r0 + halo_top < depth) ? r0 + halo_top : depth;
-        g.bot = (H + halo_bottom - g.r1 < depth) ? H + halo_bottom - g.r1 : depth;
-        chunks.push_back(g);
-    }
-    const int nchunks = (int)chunks.size();
-    auto drain = [&](int k) -> int {   // chunk k's planes: pinned staging -> caller's arrays (after its D2H has landed)
-        const ChunkGeom& g = chunks[k];
-        const int q = k & 1;
-        if (hipEventSynchronize(ev_out[q]) != hipSuccess) return xd_fail(ctx, XDEMHIP_EHIP, "D2H copy failed");
-        std::vector<Span> spans;
-        const size_t nb = (size_t)(g.r1 - g.r0) * (size_t)W * out_es;
-        for (int i = 0; i < n_planes; ++i)
-            spans.push_back({static_cast<char*>(out_planes[i]) + (size_t)g.r0 * (size_t)W * out_es,
-                             static_cast<const char*>(ctx->stage_out[q]) + (size_t)i * plane_bytes, nb});
-        parallel_copy(spans);
-        return XDEMHIP_OK;
-    };
-    for (int k = 0; k < nchunks && rc == XDEMHIP_OK; ++k) {
-        const ChunkGeom& g = chunks[k];
-        const int q = k & 1;
-        const int64_t in_rows = g.top + (g.r1 - g.r0) + g.bot;
-        // (buffers q are free: chunk k - 2 was drained two iterations ago, which followed its kernels and copies)
-        {   // caller's rows -> pinned in[q] (row stride squeezed out), then H2D
-            const char* src = static_cast<const char*>(dem) + (size_t)(g.r0 + halo_top - g.top) * (size_t)row_stride * in_es;
-            std::vector<Span> spans;
-            if (row_stride == W) spans.push_back({static_cast<char*>(ctx->stage_in[q]), src, (size_t)in_rows * (size_t)W * in_es});
-            else
-                for (int64_t r = 0; r < in_rows; ++r)
-                    spans.push_back({static_cast<char*>(ctx->stage_in[q]) + (size_t)r * (size_t)W * in_es,
-                                     src + (size_t)r * (size_t)row_stride * in_es, (size_t)W * in_es});
-            parallel_copy(spans);
-        }
-        if (hipMemcpyAsync(d_in[q], ctx->stage_in[q], (size_t)in_rows * (size_t)W * in_es, hipMemcpyHostToDevice, s_h2d) != hipSuccess ||
-            hipEventRecord(ev_in[q], s_h2d) != hipSuccess || hipStreamWaitEvent(ctx->stream, ev_in[q], 0) != hipSuccess) {
-            rc = xd_fail(ctx, XDEMHIP_EHIP, "H2D copy failed");
-            break;
-        }
-        L.dem = d_in[q];
-        for (int bit = 0, i = 0; bit < XDEMHIP_ATTR_COUNT; ++bit)
-            if (attr_mask & (1u << bit)) L.planes[bit] = static_cast<char*>(d_out[q]) + (size_t)(i++) * plane_bytes;
-        L.H = g.r1 - g.r0; L.halo_top = g.top; L.halo_bottom = g.bot;
-        if (k == 0) (void)hipEventRecord(ctx->ev_start, ctx->stream);
-        rc = xd::launch_terrain(ctx, L);
-        if (rc != XDEMHIP_OK) break;
-        if (k == nchunks - 1) (void)hipEventRecord(ctx->ev_stop, ctx->stream);
-        const size_t nb = (size_t)(g.r1 - g.r0) * (size_t)W * out_es;
-        hipError_t e = hipEventRecord(ev_comp[q], ctx->stream);
-        if (e == hipSuccess) e = hipStreamWaitEvent(s_d2h, ev_comp[q], 0);
-        for (int i = 0; i < n_planes && e == hipSuccess; ++i)   // (a short last chunk leaves gaps between its planes: one copy per plane)
-            e = hipMemcpyAsync(static_cast<char*>(ctx->stage_out[q]) + (size_t)i * plane_bytes,
-                               static_cast<const char*>(d_out[q]) + (size_t)i * plane_bytes, nb, hipMemcpyDeviceToHost, s_d2h);
-        if (e == hipSuccess) e = hipEventRecord(ev_out[q], s_d2h);
-        if (e != hipSuccess) { rc = xd_fail(ctx, XDEMHIP_EHIP, "D2H copy failed"); break; }
-        // while the device works on chunk k, move chunk k - 1's planes into the caller's arrays
-        if (k > 0) rc = drain(k - 1);
-    }
-    if (rc == XDEMHIP_OK) rc = drain(nchunks - 1);
-    if (rc != XDEMHIP_OK) { (void)hipStreamSynchronize(s_h2d); (void)hipStreamSynchronize(s_d2h); }
+    L.dem = dem;
+    for (int bit = 0, i = 0; bit < XDEMHIP_ATTR_COUNT; ++bit)
+        if (attr_mask & (1u << bit)) L.planes[bit] = out_planes[i++];
+    XD_HIP_CHECK(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
+    int rc = xd::launch_terrain(ctx, L);
+    XD_HIP_CHECK(ctx, hipEventRecord(ctx->ev_stop, ctx->stream));
     ctx->timed = (rc == XDEMHIP_OK);
-    hipError_t e2 = hipStreamSynchronize(ctx->stream);
-    if (e2 != hipSuccess && rc == XDEMHIP_OK) rc = xd_fail(ctx, XDEMHIP_EHIP, std::string("kernel failed: ") + hipGetErrorString(e2));
-    cleanup();
     return rc;
 }
 

@@ -383,6 +383,7 @@ struct TerrainLaunch {
     void* planes[XDEMHIP_ATTR_COUNT];  // device pointers by attribute bit (null when not requested)
 };
 int launch_terrain(xdemhip_ctx* ctx, const TerrainLaunch& L);
+int terrain_host(xdemhip_ctx* ctx, const TerrainLaunch& L, const void* dem, void* const* out_planes);  // terrain_host.hip: host buffers, in row chunks
 int launch_terrain_nonfinite(xdemhip_ctx* ctx, const TerrainLaunch& L);  // terrain_nonfinite.hip
 // rugosity / fractal roughness (window_extra.hip); plane indexes of the two attributes
 constexpr int P_RUGOSITY_IDX = 13, P_FRACTAL_IDX = 14;

@@ -1,6 +1,7 @@
 // terrain.hip -- dtype dispatch of the fused terrain-attribute kernel (kernel templates: terrain_tile.h).
 #include "common.h"
 #include "terrain_math.h"
+#include "terrain_route.h"
 
 namespace xd {
 
@@ -24,7 +25,7 @@ int launch_terrain(xdemhip_ctx* ctx, const TerrainLaunch& L) {
         C.attr_mask = core;
         int rc = launch_core(ctx, C);
         if (rc != XDEMHIP_OK) return rc;
-        if (ctx->terrain_nonfinite && (core & 0x3ffu)) {  // the Numba engine's +-Inf rule on top of the fused kernels' planes
+        if (ctx->terrain_nonfinite && (core & ATTRS_SURFACE)) {  // the Numba engine's +-Inf rule on top of the fused kernels' planes
             rc = launch_terrain_nonfinite(ctx, C);
             if (rc != XDEMHIP_OK) return rc;
         }

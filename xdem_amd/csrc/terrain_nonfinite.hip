@@ -18,6 +18,7 @@
 // dtype (xdem/terrain/terrain.py:586-596).  Everything about it is cold: a raster without +-Inf pays one streaming read.
 #include "common.h"
 #include "terrain_nonfinite.h"
+#include "terrain_route.h"
 
 namespace xd {
 
@@ -59,7 +60,7 @@ static int nf_launch(xdemhip_ctx* ctx, const TerrainLaunch& L, const NfParams& P
 }
 
 int launch_terrain_nonfinite(xdemhip_ctx* ctx, const TerrainLaunch& L) {
-    const uint32_t surf = L.attr_mask & 0x3ffu;
+    const uint32_t surf = L.attr_mask & ATTRS_SURFACE;
     if (!surf) return XDEMHIP_OK;
     if (!ctx->nf_flag) XD_HIP_CHECK(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->nf_flag), sizeof(int)));
     NfParams P;

@@ -1,6 +1,7 @@
 // terrain_tile.h -- fused terrain-attribute kernel for gfx950 (MI355X): kernel templates and launchers, instantiated per
 // (DEM dtype, output dtype) pair by terrain_ff.hip / terrain_dd.hip / terrain_fd.hip / terrain_df.hip (four translation
-// units so that they compile in parallel); terrain.hip holds the dtype dispatch.
+// units so that they compile in parallel); terrain.hip holds the dtype dispatch, terrain_route.h (plain C++) every decision the
+// launchers act on: which kernel, which part of the raster the strips take, which window kernel on which grid.
 //
 // One pass over the DEM produces every requested attribute (slope, aspect, hillshade, the curvatures,
 // TPI, TRI): 4 B read + 4 B written per attribute per pixel -- an HBM-bound job, no MFMA (no dense
@@ -23,11 +24,11 @@
 
 #include "common.h"
 #include "terrain_math.h"
+#include "terrain_route.h"
 
 namespace xd {
 
-constexpr int TILE_W = 256;
-constexpr int XPAD = 4;
+constexpr int XPAD = 4;   // (TILE_W: terrain_route.h)
 constexpr int PITCH = TILE_W + 2 * XPAD;
 
 template <typename TIN, typename TOUT> struct TileArgs {
@@ -286,8 +287,7 @@ __global__ __launch_bounds__(256, MINW) void terrain_strip_kernel(const StripArg
 //    difference / fused-multiply-add / min / max chains).  Windows whose patch exceeds WIN_LDS_BYTES (w > ~90) and
 //    option "terrain_window_lds" = 0 take
 //  * window_generic_kernel: one thread per pixel, taps through L1 / L2 (the form of rounds 1-3; the check of the other).
-constexpr int WIN_TW = 64, WIN_TH = 16;
-constexpr size_t WIN_LDS_BYTES = 64 * 1024;
+// (WIN_TW x WIN_TH, WIN_LDS_BYTES and the choice between the two forms: terrain_route.h, plan_window)
 
 template <typename TIN, typename TOUT, bool DO_TPI, bool DO_TRI, bool DO_ROUGH>
 __device__ __forceinline__ void window_accumulate(const TIN* win /* top-left tap */, int pitch, int w, double c, int tri_wilson,
@@ -388,10 +388,10 @@ static int launch_window(xdemhip_ctx* ctx, const TerrainLaunch& L, uint32_t win)
     TOUT* tri = (win & A_TRI) ? static_cast<TOUT*>(L.planes[P_TRI]) : nullptr;
     TOUT* rough = (win & A_ROUGH) ? static_cast<TOUT*>(L.planes[P_ROUGH]) : nullptr;
     const int w = L.window_size, wilson = (int)(L.tri_method == XDEMHIP_TRI_WILSON);
-    const size_t lds = (size_t)(WIN_TH + w - 1) * (size_t)(WIN_TW + w - 1) * sizeof(TIN);
-    const int64_t gy_lds = (L.H + WIN_TH - 1) / WIN_TH, gy_gen = (L.H + 3) / 4;
-    if (ctx->terrain_window_lds != 0 && lds <= WIN_LDS_BYTES && gy_lds <= 65535) {
-        const dim3 grid((unsigned)((L.W + WIN_TW - 1) / WIN_TW), (unsigned)gy_lds);
+    const WindowPlan plan = plan_window(L.H, L.W, w, sizeof(TIN), ctx->terrain_window_lds);
+    const dim3 grid(plan.grid_x, plan.grid_y);
+    if (plan.lds) {
+        const size_t lds = plan.lds_bytes;
         const int which = (tpi ? 1 : 0) | (tri ? 2 : 0) | (rough ? 4 : 0);
 #define XD_WIN(T, R, O)                                                                                                       \
     do {                                                                                                                      \
@@ -413,8 +413,7 @@ static int launch_window(xdemhip_ctx* ctx, const TerrainLaunch& L, uint32_t win)
         XD_HIP_CHECK(ctx, hipGetLastError());
         return XDEMHIP_OK;
     }
-    if (gy_gen > 65535) return xd_fail(ctx, XDEMHIP_EUNSUPPORTED, "raster too tall for one launch of the window kernel");
-    dim3 grid((unsigned)((L.W + 63) / 64), (unsigned)gy_gen);
+    if (plan.too_tall) return xd_fail(ctx, XDEMHIP_EUNSUPPORTED, "raster too tall for one launch of the window kernel");
     hipLaunchKernelGGL((window_generic_kernel<TIN, TOUT>), grid, dim3(256), 0, ctx->stream, dem, L.H, L.W, L.row_stride, L.halo_top,
                        L.halo_bottom, w, wilson, tpi, tri, rough);
     XD_HIP_CHECK(ctx, hipGetLastError());
@@ -444,8 +443,6 @@ static void fill_params(const TerrainLaunch& L, TerrainParams& P) {
     P.degrees = L.degrees;
     P.hs_clip = L.hs_unclipped ? 0 : 1;
 }
-
-struct FrameRect { int tx0 = 0, tx1 = 0, ty0 = 0, ty1 = 0; };  // interior tile rectangle left out in frame mode (empty: all tiles)
 
 template <int FIT, bool CURV, bool WIN, class SP, typename TIN, typename TOUT, int TH>
 static int launch_tiles(xdemhip_ctx* ctx, const TerrainLaunch& L, uint32_t mask, FrameRect fr = FrameRect()) {
@@ -483,48 +480,24 @@ static int launch_shaped(xdemhip_ctx* ctx, const TerrainLaunch& L, uint32_t mask
 }
 
 // Streaming route for float32 in / float32 out and the specialised attribute sets: the interior by terrain_strip_kernel, the
-// frame of edge tiles by the tile kernel.  Returns 1 if it took the launch, 0 if the raster does not qualify (caller falls
-// back to the tile kernel for everything), < 0 on error.  Option "terrain_stream": 0 off, 1 on (default), 128 / 256 / 512 =
-// band height (measurement).
+// frame of edge tiles by the tile kernel, both as plan_strips (terrain_route.h) cuts the raster.  Returns 1 if it took the launch,
+// 0 if the raster does not qualify (caller falls back to the tile kernel for everything), < 0 on error.
 template <int FIT, bool CURV, bool WIN, class SP>
 static int launch_stream(xdemhip_ctx* ctx, const TerrainLaunch& L, uint32_t mask) {
-    constexpr int HALO = Halo<FIT>::v;
-    constexpr int TH = 32;
-    if (ctx->terrain_stream == 0) return 0;
-    if ((reinterpret_cast<uintptr_t>(L.dem) & 15) || (L.row_stride & 3)) return 0;   // 16-byte quads of the LDS-DMA
-    if (L.row_stride >= ((int64_t)1 << 24) - 64) return 0;                               // 24-bit row offsets inside a block
-    FrameRect fr;
-    fr.tx0 = 1;
-    fr.tx1 = (int)((L.W - 4) / TILE_W);
-    fr.ty0 = L.halo_top >= HALO ? 0 : 1;
-    const int64_t ylim = (L.H + L.halo_bottom - HALO) < L.H ? (L.H + L.halo_bottom - HALO) : L.H;
-    fr.ty1 = (int)(ylim / TH);
-    if (fr.tx1 - fr.tx0 < 1 || fr.ty1 - fr.ty0 < 2) return 0;
-    if ((int64_t)(fr.tx1 - fr.tx0) * (fr.ty1 - fr.ty0) < 64) return 0;   // small rasters: one launch of the tile kernel
+    const RasterGeom geom = {L.H, L.W, L.row_stride, L.halo_top, L.halo_bottom};
+    const StripPlan plan = plan_strips(geom, (reinterpret_cast<uintptr_t>(L.dem) & 15) == 0, Halo<FIT>::v, ctx->terrain_stream);
+    if (!plan.ok) return 0;
     StripArgs a;
     a.dem = static_cast<const float*>(L.dem);
     a.H = L.H; a.W = L.W; a.stride = L.row_stride; a.halo_top = L.halo_top;
-    a.xi0 = (int64_t)fr.tx0 * TILE_W; a.yi0 = (int64_t)fr.ty0 * TH; a.yi1 = (int64_t)fr.ty1 * TH;
-    a.groups_x = fr.tx1 - fr.tx0;
+    a.xi0 = plan.xi0; a.yi0 = plan.yi0; a.yi1 = plan.yi1;
+    a.groups_x = plan.groups_x; a.ngroups = plan.ngroups; a.grid8 = plan.grid8; a.nbands = plan.nbands;
+    a.perm_mul = plan.perm_mul;
     a.order = ctx->terrain_order;
+    a.safe_wait = ctx->terrain_ring_wait;
     fill_params(L, a.P);
     a.P.mask = mask;
     for (int k = 0; k < N_ATTR; ++k) a.out.p[k] = static_cast<float*>(L.planes[k]);
-    const int bh = ctx->terrain_stream >= 64 ? ctx->terrain_stream : 128;
-    const bool dbg_no_strips = ctx->terrain_stream == 3, dbg_no_frame = ctx->terrain_stream == 2;  // (debug: one of the two launches only)
-    const int64_t bands = (a.yi1 - a.yi0 + bh - 1) / bh;
-    if (bands * a.groups_x > (int64_t)0xfffff0) return 0;
-    a.ngroups = (int)(bands * a.groups_x);
-    a.grid8 = (a.ngroups + 7) / 8;
-    a.nbands = (int)bands;
-    a.safe_wait = ctx->terrain_ring_wait;
-    {   // multiplier of order 2: near the golden section of the grid, coprime to it
-        const uint32_t n = (uint32_t)a.grid8 * 8u;
-        uint32_t m = (uint32_t)(0.6180339887 * (double)n) | 1u;
-        auto gcd = [](uint32_t x, uint32_t y) { while (y) { const uint32_t t = x % y; x = y; y = t; } return x; };
-        while (m > 1 && gcd(m, n) != 1) m += 2;
-        a.perm_mul = m;
-    }
     const dim3 grid(a.grid8 * 8), block(256);
     // four waves per SIMD for every streaming kernel (four workgroups of 36 KB LDS per CU): the Florinsky sets with curvatures get
     // there since round 6 (forward-accumulated stencil sums + the TPI / TRI window re-read from LDS: 164 -> 127 VGPRs, no scratch:
@@ -532,125 +505,109 @@ static int launch_stream(xdemhip_ctx* ctx, const TerrainLaunch& L, uint32_t mask
     constexpr int MINW = (FIT == 2 && CURV && SP::F64TAIL != 2) ? 1 : 4;   // (the mixed tail of option terrain_math = 0 would spill two registers)
     // ring blocks: the sets of up to five planes march a row in a few hundred cycles and need their refills further ahead (RowsRing)
     constexpr int RBLK = ring_block(__builtin_popcount(SP::CMASK));
-    if (dbg_no_strips) {}
+    const int bh = plan.band_height;
+    if (!plan.strips) {}
     else if (bh == 128) hipLaunchKernelGGL((terrain_strip_kernel<FIT, CURV, WIN, SP, 128, MINW, RBLK>), grid, block, 0, ctx->stream, a);
     else if (bh == 256) hipLaunchKernelGGL((terrain_strip_kernel<FIT, CURV, WIN, SP, 256, MINW, RBLK>), grid, block, 0, ctx->stream, a);
     else if (bh == 512) hipLaunchKernelGGL((terrain_strip_kernel<FIT, CURV, WIN, SP, 512, MINW, RBLK>), grid, block, 0, ctx->stream, a);
     else return xd_fail(ctx, XDEMHIP_EINVAL, "terrain_stream: 0, 1, 128, 256 or 512");
     XD_HIP_CHECK(ctx, hipGetLastError());
-    const int rc = dbg_no_frame ? XDEMHIP_OK : launch_tiles<FIT, CURV, WIN, SP, float, float, TH>(ctx, L, mask, fr);
+    const int rc = plan.frame ? launch_tiles<FIT, CURV, WIN, SP, float, float, STRIP_TILE_H>(ctx, L, mask, plan.fr) : XDEMHIP_OK;
     return rc == XDEMHIP_OK ? 1 : rc;
 }
 
+// ---- from a TerrainRoute to the kernel's template arguments -----------------------------------------------------------------------
+// for_kernel hands `f` a Kernel<...> tag for the route: the one place that spells the template arguments of a family, read by the
+// streaming attempt and the tile launch alike.  Only the kernels a dtype pair has are named for it (if constexpr): the strips, both
+// tails, the small sets, the directional full set and the float64 tail exist for float32 -> float32 alone.
+template <int FIT_, bool CURV_, bool WIN_, class SP_> struct Kernel {
+    static constexpr int FIT = FIT_;
+    static constexpr bool CURV = CURV_, WIN = WIN_;
+    typedef SP_ SP;
+};
+// compile-time attribute set with the reference's defaults: degrees, Riley TRI, z_factor 1
+template <uint32_t M, int DIR, int LV> using SpecSet = Spec<M, DIR, 1, 0, 1, LV>;
+static_assert(MASK_FULL11 == ATTRS_FULL11 && MASK_SAH_WIN == ATTRS_SAH_WIN && A_ANY_WIN == ATTRS_FUSED_WINDOW && A_ANY_CURV == ATTRS_CURVATURE,
+              "terrain_route.h and terrain_math.h name the same attribute sets");
+
+constexpr int NO_KERNEL = 1;   // "not one of mine" of the helpers below (no status code: those are <= 0)
+
+// the eleven planes with either curvature method and Horn's five, at tail LV (the float64 tail has the Florinsky full set only)
+template <int LV, bool FF, class F> static int set_kernel(const TerrainRoute& r, F& f) {
+    const bool fl = r.fit == XDEMHIP_FIT_FLORINSKY;
+    if (r.family == TF_FULL11_GEO) {
+        if (fl) return f(Kernel<2, true, true, SpecSet<MASK_FULL11, 0, LV>>());
+        if constexpr (LV != 1) return f(Kernel<1, true, true, SpecSet<MASK_FULL11, 0, LV>>());
+    }
+    if constexpr (LV != 1) {
+        if (r.family == TF_SAH_WIN) return f(Kernel<0, false, true, SpecSet<MASK_SAH_WIN, 0, LV>>());
+        if constexpr (FF) {
+            if (r.family == TF_FULL11_DIR) return fl ? f(Kernel<2, true, true, SpecSet<MASK_FULL11, 1, LV>>()) : f(Kernel<1, true, true, SpecSet<MASK_FULL11, 1, LV>>());
+        }
+    }
+    return NO_KERNEL;
+}
+template <uint32_t M, class F> static int small_kernel(const TerrainRoute& r, F& f) {   // a small set: every fit, lean tail
+    if (r.fit == XDEMHIP_FIT_HORN) return f(Kernel<0, false, false, SpecSet<M, 0, 2>>());
+    if (r.fit == XDEMHIP_FIT_ZEVENBERGTHORNE) return f(Kernel<1, false, false, SpecSet<M, 0, 2>>());
+    return f(Kernel<2, false, false, SpecSet<M, 0, 2>>());
+}
+template <int FIT, bool CURV, bool WIN, bool FF, class F> static int runtime_tail(const TerrainRoute& r, F& f) {
+    if constexpr (FF) {
+        if (r.family == TF_RUNTIME_F64) return f(Kernel<FIT, CURV, WIN, SpecRuntimeF64>());
+    }
+    return f(Kernel<FIT, CURV, WIN, SpecRuntime>());
+}
+template <bool FF, class F> static int runtime_kernel(const TerrainRoute& r, F& f) {
+    if (r.fit == XDEMHIP_FIT_HORN) return r.fuse_win ? runtime_tail<0, false, true, FF>(r, f) : runtime_tail<0, false, false, FF>(r, f);
+    if (r.fit == XDEMHIP_FIT_ZEVENBERGTHORNE) {
+        if (r.curv) return r.fuse_win ? runtime_tail<1, true, true, FF>(r, f) : runtime_tail<1, true, false, FF>(r, f);
+        return r.fuse_win ? runtime_tail<1, false, true, FF>(r, f) : runtime_tail<1, false, false, FF>(r, f);
+    }
+    if (r.curv) return r.fuse_win ? runtime_tail<2, true, true, FF>(r, f) : runtime_tail<2, true, false, FF>(r, f);
+    return r.fuse_win ? runtime_tail<2, false, true, FF>(r, f) : runtime_tail<2, false, false, FF>(r, f);
+}
+
+template <typename TIN, typename TOUT, class F>
+static int for_kernel(xdemhip_ctx* ctx, const TerrainRoute& r, F f) {
+    constexpr bool FF = SameT<TIN, float>::v && SameT<TOUT, float>::v;
+    int rc = NO_KERNEL;
+    if constexpr (FF) {
+        if (r.tail == 2) rc = set_kernel<2, FF>(r, f);
+    }
+    if (rc == NO_KERNEL && r.tail == 0) rc = set_kernel<0, FF>(r, f);
+    if constexpr (FF) {
+        if (r.family == TF_SLOPE) rc = small_kernel<A_SLOPE>(r, f);
+        if (r.family == TF_SLOPE_ASPECT) rc = small_kernel<A_SLOPE | A_ASPECT>(r, f);
+        if (r.family == TF_HILLSHADE) rc = small_kernel<A_HILLSHADE>(r, f);
+        if (r.family == TF_SAH) rc = small_kernel<A_SLOPE | A_ASPECT | A_HILLSHADE>(r, f);
+        if (rc == NO_KERNEL && r.tail == 1) rc = set_kernel<1, FF>(r, f);
+    }
+    if (rc == NO_KERNEL && (r.family == TF_RUNTIME || (FF && r.family == TF_RUNTIME_F64))) rc = runtime_kernel<FF>(r, f);
+    return rc == NO_KERNEL ? xd_fail(ctx, XDEMHIP_EINVAL, "terrain route: no kernel of this family for the dtype pair") : rc;
+}
+
+// One call: the route, the fused launch for it (strips + frame where the route and the raster allow, else tiles), then the launch
+// of the windowed indexes of another window size if the route has one.
 template <typename TIN, typename TOUT>
 static int launch_typed(xdemhip_ctx* ctx, const TerrainLaunch& L) {
-    const uint32_t surf = L.attr_mask & ~A_ANY_WIN;
-    const uint32_t win = L.attr_mask & A_ANY_WIN;
-    const bool fuse_win = win && L.window_size == 3;
-    const uint32_t mask = surf | (fuse_win ? win : 0u);
-    const bool curv = (surf & A_ANY_CURV) != 0;
-    int rc = XDEMHIP_OK;
-    if (mask) {
-        const int fit = surf ? L.surface_fit : XDEMHIP_FIT_ZEVENBERGTHORNE;  // window-only: cheapest 3x3 march
-        // Compile-time specialised kernels for the headline configurations (reference defaults: geometric
-        // curvatures, degrees, Riley TRI, z_factor 1): all attribute branches fold away -> one schedulable basic block.
-        // (an unclipped hillshade -- the engine-boundary call -- is known to the float64 tail of the runtime-mask kernels only)
-        const bool defaults_dir = L.degrees && L.tri_method == XDEMHIP_TRI_RILEY && L.hs_z == 1.0 && !L.hs_unclipped;  // ... with either curvature method
-        const bool defaults = L.curv_method == XDEMHIP_CURV_GEOMETRIC && defaults_dir;
-        // option "terrain_math" = 1: float64 attribute math for float32 rasters too (other dtype pairs always use it);
-        // 2 (default) / 0: lean / mixed tail of the specialised float32 kernels (the runtime-mask kernels keep the mixed tail)
-        constexpr bool FF = SameT<TIN, float>::v && SameT<TOUT, float>::v;
-        const bool f64tail = FF && (ctx->terrain_math == 1 || L.hs_unclipped);
-        if constexpr (FF) {
-            // float32 in / float32 out, specialised sets: lean tail (option "terrain_math" = 2, the default) or the mixed tail of
-            // round 2 (0); the streaming route (interior by wave-autonomous strips + frame by tiles) where the raster qualifies
-            const bool fl = defaults && mask == MASK_FULL11 && fit == XDEMHIP_FIT_FLORINSKY;
-            const bool zt = defaults && mask == MASK_FULL11 && fit == XDEMHIP_FIT_ZEVENBERGTHORNE;
-            const bool hn = defaults && mask == MASK_SAH_WIN && fit == XDEMHIP_FIT_HORN;
-            // round 5: the same eleven planes with curv_method="directional" (the other value users pass: terrain.py:694-747) were
-            // the runtime-mask tile kernel's (0.60 of the roofline); they now have the full set's route
-            const bool dirc = defaults_dir && L.curv_method == XDEMHIP_CURV_DIRECTIONAL && mask == MASK_FULL11;
-            const bool fld = dirc && fit == XDEMHIP_FIT_FLORINSKY, ztd = dirc && fit == XDEMHIP_FIT_ZEVENBERGTHORNE;
-#define XD_SPECIALISED(LV)                                                                                                   \
-    do {                                                                                                                     \
-        int took = 0;                                                                                                        \
-        if (fl) took = launch_stream<2, true, true, Spec<MASK_FULL11, 0, 1, 0, 1, LV>>(ctx, L, mask);                        \
-        else if (zt) took = launch_stream<1, true, true, Spec<MASK_FULL11, 0, 1, 0, 1, LV>>(ctx, L, mask);                   \
-        else if (hn) took = launch_stream<0, false, true, Spec<MASK_SAH_WIN, 0, 1, 0, 1, LV>>(ctx, L, mask);                 \
-        else if (fld) took = launch_stream<2, true, true, Spec<MASK_FULL11, 1, 1, 0, 1, LV>>(ctx, L, mask);                  \
-        else if (ztd) took = launch_stream<1, true, true, Spec<MASK_FULL11, 1, 1, 0, 1, LV>>(ctx, L, mask);                  \
-        if (took != 0) return took < 0 ? took : XDEMHIP_OK;                                                                  \
-        if (fl) return launch_shaped<2, true, true, Spec<MASK_FULL11, 0, 1, 0, 1, LV>, TIN, TOUT>(ctx, L, mask);             \
-        if (zt) return launch_shaped<1, true, true, Spec<MASK_FULL11, 0, 1, 0, 1, LV>, TIN, TOUT>(ctx, L, mask);             \
-        if (hn) return launch_shaped<0, false, true, Spec<MASK_SAH_WIN, 0, 1, 0, 1, LV>, TIN, TOUT>(ctx, L, mask);           \
-        if (fld) return launch_shaped<2, true, true, Spec<MASK_FULL11, 1, 1, 0, 1, LV>, TIN, TOUT>(ctx, L, mask);            \
-        if (ztd) return launch_shaped<1, true, true, Spec<MASK_FULL11, 1, 1, 0, 1, LV>, TIN, TOUT>(ctx, L, mask);            \
-    } while (0)
-            if (ctx->terrain_math == 2) XD_SPECIALISED(2);
-            else if (ctx->terrain_math == 0) XD_SPECIALISED(0);
-#undef XD_SPECIALISED
-            // Round 4: the SMALL surface sets -- DEM.slope(), slope + aspect, a hillshade, the three together -- for every fit, with
-            // reference defaults (degrees, z_factor 1): compile-time masks + lean tail + the streaming route, like the full set.
-            // With 8-16 bytes per pixel instead of 48 these launches are bound by instruction issue, so the folded attribute
-            // branches and the float32 scale factors matter more here than for the eleven planes.
-            // (win == 0: a windowed index of another window size still has its own launch below -- these macros return)
-            if (win == 0 && ctx->terrain_math == 2 && L.degrees && !L.hs_unclipped && L.hs_z == 1.0 && (mask & ~(A_SLOPE | A_ASPECT | A_HILLSHADE)) == 0) {
-#define XD_SMALL(F, M)                                                                                                       \
-    do {                                                                                                                     \
-        const int took = launch_stream<F, false, false, Spec<M, 0, 1, 0, 1, 2>>(ctx, L, mask);                              \
-        if (took != 0) return took < 0 ? took : XDEMHIP_OK;                                                                  \
-        return launch_shaped<F, false, false, Spec<M, 0, 1, 0, 1, 2>, TIN, TOUT>(ctx, L, mask);                             \
-    } while (0)
-#define XD_SMALL_FITS(M)                                                                                                     \
-    do {                                                                                                                     \
-        if (fit == XDEMHIP_FIT_HORN) XD_SMALL(0, M);                                                                         \
-        else if (fit == XDEMHIP_FIT_ZEVENBERGTHORNE) XD_SMALL(1, M);                                                         \
-        else XD_SMALL(2, M);                                                                                                 \
-    } while (0)
-                if (mask == A_SLOPE) XD_SMALL_FITS(A_SLOPE);
-                else if (mask == (A_SLOPE | A_ASPECT)) XD_SMALL_FITS(A_SLOPE | A_ASPECT);
-                else if (mask == A_HILLSHADE) XD_SMALL_FITS(A_HILLSHADE);
-                else if (mask == (A_SLOPE | A_ASPECT | A_HILLSHADE)) XD_SMALL_FITS(A_SLOPE | A_ASPECT | A_HILLSHADE);
-#undef XD_SMALL_FITS
-#undef XD_SMALL
+    const TerrainCall call = {L.dem_dtype, L.out_dtype, L.attr_mask, L.surface_fit, L.curv_method, L.tri_method, L.degrees, L.hs_z,
+                              L.hs_unclipped, L.window_size};
+    const TerrainRoute r = terrain_route(call, TerrainOptions{ctx->terrain_math, ctx->terrain_stream});
+    if (r.family != TF_NONE) {
+        const int rc = for_kernel<TIN, TOUT>(ctx, r, [&](auto k) -> int {
+            typedef decltype(k) K;
+            typedef typename K::SP SP;
+            // strips exist for float32 -> float32, compile-time attribute sets, lean and mixed tail
+            if constexpr (SameT<TIN, float>::v && SameT<TOUT, float>::v && SP::CMASK != 0 && SP::F64TAIL != 1) {
+                const int took = r.try_stream ? launch_stream<K::FIT, K::CURV, K::WIN, SP>(ctx, L, r.mask) : 0;
+                if (took != 0) return took < 0 ? took : XDEMHIP_OK;
             }
-        } else if (!f64tail) {
-            if (defaults && mask == MASK_FULL11 && fit == XDEMHIP_FIT_FLORINSKY)
-                return launch_shaped<2, true, true, Spec<MASK_FULL11, 0, 1, 0, 1>, TIN, TOUT>(ctx, L, mask);
-            if (defaults && mask == MASK_FULL11 && fit == XDEMHIP_FIT_ZEVENBERGTHORNE)
-                return launch_shaped<1, true, true, Spec<MASK_FULL11, 0, 1, 0, 1>, TIN, TOUT>(ctx, L, mask);
-            if (defaults && mask == MASK_SAH_WIN && fit == XDEMHIP_FIT_HORN)
-                return launch_shaped<0, false, true, Spec<MASK_SAH_WIN, 0, 1, 0, 1>, TIN, TOUT>(ctx, L, mask);
-        }
-        if constexpr (FF) {
-            if (f64tail && defaults && mask == MASK_FULL11 && fit == XDEMHIP_FIT_FLORINSKY)
-                return launch_shaped<2, true, true, Spec<MASK_FULL11, 0, 1, 0, 1, 1>, TIN, TOUT>(ctx, L, mask);
-        }
-#define XD_GO(F, C, Wn)                                                                             \
-    do {                                                                                            \
-        if constexpr (FF) {                                                                         \
-            rc = f64tail ? launch_shaped<F, C, Wn, SpecRuntimeF64, TIN, TOUT>(ctx, L, mask)         \
-                         : launch_shaped<F, C, Wn, SpecRuntime, TIN, TOUT>(ctx, L, mask);           \
-        } else {                                                                                    \
-            rc = launch_shaped<F, C, Wn, SpecRuntime, TIN, TOUT>(ctx, L, mask);                     \
-        }                                                                                           \
-    } while (0)
-        if (fit == XDEMHIP_FIT_HORN) { if (fuse_win) XD_GO(0, false, true); else XD_GO(0, false, false); }
-        else if (fit == XDEMHIP_FIT_ZEVENBERGTHORNE) {
-            if (curv) { if (fuse_win) XD_GO(1, true, true); else XD_GO(1, true, false); }
-            else { if (fuse_win) XD_GO(1, false, true); else XD_GO(1, false, false); }
-        } else {
-            if (curv) { if (fuse_win) XD_GO(2, true, true); else XD_GO(2, true, false); }
-            else { if (fuse_win) XD_GO(2, false, true); else XD_GO(2, false, false); }
-        }
-#undef XD_GO
+            return launch_shaped<K::FIT, K::CURV, K::WIN, SP, TIN, TOUT>(ctx, L, r.mask);
+        });
         if (rc != XDEMHIP_OK) return rc;
     }
-    if (win && !fuse_win) {
-        rc = launch_window<TIN, TOUT>(ctx, L, win);
-        if (rc != XDEMHIP_OK) return rc;
-    }
-    return XDEMHIP_OK;
+    return r.window_mask ? launch_window<TIN, TOUT>(ctx, L, r.window_mask) : XDEMHIP_OK;
 }
 
 }  // namespace xd
