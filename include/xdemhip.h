@@ -666,6 +666,25 @@ int xdemhip_perbin_lookup(xdemhip_ctx* ctx, const void* const* vars, const int* 
 int xdemhip_shift_bilinear(xdemhip_ctx* ctx, const void* src, int dtype, int64_t H, int64_t W, double shift_row_px,
                            double shift_col_px, double dz, void* out, int memspace);
 
+/* ---- geoutils' Raster.reproject, same CRS: a raster resampled onto another north-up grid ----------------------------------------
+ * What the reference's entry points do first to put two rasters on one grid (xdem/coreg/base.py:146-156, demcollection.py:128,
+ * dem.py:724, ddem.py:198).  The reference runs GDAL's warper through rasterio; the rule here is written down in DESIGN.md
+ * ("Regridding") and restated in NumPy by tests/reproject_oracle.py, whose bits every route returns -- parity with GDAL is unpinned.
+ * src: H x W, float32 / float64 (uint8 with XDEMHIP_REGRID_NEAREST only, then dst is uint8 too); dst: h x w, float32 / float64 in any
+ * combination with src.  map4 = (rx, tx, ry, ty): the centre of destination pixel (row o_y, column o_x) lies at
+ * (u_y, u_x) = ((o_y + 0.5) ry + ty, (o_x + 0.5) rx + tx) in source pixel units (pixel i covers [i, i + 1)); rx, ry > 0, i.e.
+ * r = a_d / a_s and t = (c_d - c_s) / a_s per axis of two north-up transforms.  Kernels: bilinear (radius 1), cubic (Catmull-Rom,
+ * radius 2), cubic spline (B-spline, radius 2), stretched by max(1, r) when downsampling; taps outside the source and non-finite taps
+ * are dropped and the rest renormalised; a pixel whose centre lies outside the source, or whose remaining weight is <= 1e-5, is NaN.
+ * Nearest copies source pixel floor(u + 1e-10) per axis, NaN (uint8: 0) outside.  float64 arithmetic throughout, in one fixed order.
+ * *valid_count = destination pixels that are not NaN (uint8: pixels taken from inside the source), counted in the same pass.
+ * Nothing outlives the call: it returns synchronised in both memory spaces.  XDEMHIP_EUNSUPPORTED: a downsampling that needs more
+ * than 2^24 taps per destination pixel. */
+enum { XDEMHIP_U8 = 2 };
+enum { XDEMHIP_REGRID_NEAREST = 0, XDEMHIP_REGRID_BILINEAR = 1, XDEMHIP_REGRID_CUBIC = 2, XDEMHIP_REGRID_CUBIC_SPLINE = 3 };
+int xdemhip_regrid(xdemhip_ctx* ctx, const void* src, int src_dtype, int64_t H, int64_t W, void* dst, int dst_dtype, int64_t h, int64_t w,
+                   const double* map4, int kernel, int memspace, int64_t* valid_count);
+
 /* ---- xdem.coreg.BlockwiseCoreg (xdem/coreg/blockwise.py): one Nuth-Kaab fit per tile of a tiling, all tiles together --------------
  * A plan copies the two rasters into tile-major buffers (tiles4: row0, row1, col0, col1 of each of the n_tiles <= 65535 tiles, every tile
  * inside the raster, at least 2 x 2 and fewer than 2^31 pixels); every tile is then an independent raster: np.gradient is one-sided

@@ -22,7 +22,10 @@
  *   "vec_seg_lds"        0 (default: 4096) the longest crossing segment that one workgroup sorts in LDS; a longer one is sorted in place in
  *                        global memory (1 .. 4096; with "vec_seg_reg" = 1 the value 1 sends every segment down the global route).
  *   "vec_stage_times"    0 (default) / 1: xdemhip_rasterize records an event where each of its five stages starts and
- *                        xdemhip_rasterize_stage_ms returns the device time between them (a measurement form: the same planes). */
+ *                        xdemhip_rasterize_stage_ms returns the device time between them (a measurement form: the same planes).
+ *   "regrid_route"       0 (default) xdemhip_regrid takes the LDS-tiled route while a workgroup's source footprint fits its LDS budget and
+ *                        the per-pixel route that reads its taps from global memory beyond it; 1 = the tiled route wherever the footprint
+ *                        fits (today the automatic choice, pinned against a later change of policy); 2 = the per-pixel route always. */
 #pragma once
 #include "xdemhip.h"
 #ifdef __cplusplus
@@ -35,6 +38,10 @@ int xdemhip_rasterize_stage_ms(xdemhip_ctx* ctx, float* ms);
 /* Device bytes that the plans of this context hold between calls: what their creates and steps asked for and have not yet freed
  * (0 once every plan is destroyed; the memory tests read it). */
 int xdemhip_plan_bytes(xdemhip_ctx* ctx, int64_t* bytes);
+/* The route xdemhip_regrid takes for a map4 / kernel / source dtype under a value of "regrid_route" (host only, no context):
+ * *route = XDEMHIP_REGRID_ROUTE_*, *lds_bytes = what a workgroup of the tiled route would ask for, *lds_budget = the most it may. */
+enum { XDEMHIP_REGRID_ROUTE_NEAREST = 0, XDEMHIP_REGRID_ROUTE_TILE = 1, XDEMHIP_REGRID_ROUTE_DIRECT = 2 };
+int xdemhip_regrid_route(const double* map4, int kernel, int src_dtype, int route_switch, int* route, int64_t* lds_bytes, int64_t* lds_budget);
 #ifdef __cplusplus
 }
 #endif

@@ -219,8 +219,10 @@ __global__ __launch_bounds__(256) void nk_y_kernel(const T* __restrict__ dh, con
                                                    const T* __restrict__ aspect, int64_t n, T vshift,
                                                    const T* __restrict__ edges, int nb, T* __restrict__ y,
                                                    uint16_t* __restrict__ bins, double* sums /* [sum, sumsq] */,
-                                                   int last_decimal = NK_AUTO_EDGES) {
+                                                   int last_decimal = NK_AUTO_EDGES,
+                                                   double* part = nullptr /* [workgroups][2]: the sums leave per workgroup, for nk_y_sums_kernel */) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    __shared__ double wave_part[2][4];
     T* e = reinterpret_cast<T*>(smem);
     for (int k = threadIdx.x; k <= nb; k += blockDim.x) e[k] = edges[k];
     __syncthreads();
@@ -242,7 +244,36 @@ __global__ __launch_bounds__(256) void nk_y_kernel(const T* __restrict__ dh, con
         bins[p] = b;
     }
     for (int off = 32; off > 0; off >>= 1) { s1 += __shfl_down(s1, off); s2 += __shfl_down(s2, off); }
-    if ((threadIdx.x & 63) == 0) { atomicAdd(&sums[0], s1); atomicAdd(&sums[1], s2); }
+    if (!part) {
+        if ((threadIdx.x & 63) == 0) { atomicAdd(&sums[0], s1); atomicAdd(&sums[1], s2); }
+        return;
+    }
+    // a fixed order instead of atomics, whose order of arrival changes the last bits from launch to launch: the four waves in order
+    // here, the workgroups in order in nk_y_sums_kernel
+    if ((threadIdx.x & 63) == 0) { wave_part[0][threadIdx.x >> 6] = s1; wave_part[1][threadIdx.x >> 6] = s2; }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        const double* w = wave_part[threadIdx.x];
+        part[2 * (size_t)blockIdx.x + threadIdx.x] = ((w[0] + w[1]) + w[2]) + w[3];
+    }
+}
+
+// sums[t] = the workgroups' partials of nk_y_kernel added in a fixed order: lane l takes the partials l, l + 256, ... in order, then a
+// halving tree over the 256 lanes.  One workgroup.
+__global__ __launch_bounds__(256) void nk_y_sums_kernel(const double* __restrict__ part, int n_wg, double* __restrict__ sums) {
+    __shared__ double red[256];
+    for (int t = 0; t < 2; ++t) {
+        double s = 0.0;
+        for (int b = threadIdx.x; b < n_wg; b += 256) s += part[2 * (size_t)b + t];
+        red[threadIdx.x] = s;
+        __syncthreads();
+        for (int half = 128; half > 0; half >>= 1) {
+            if ((int)threadIdx.x < half) red[threadIdx.x] += red[threadIdx.x + half];
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) sums[t] = red[0];
+        __syncthreads();
+    }
 }
 
 // The same y / bin id computed on the fly for the bracketed selection (select_run.h): its sample and counting passes read
@@ -1257,8 +1288,17 @@ int nk_step_typed(xdemhip_nk_plan* P, double shift_x, double shift_y, double res
         // small grids, plain mode, a missed bracket: y and bin-id arrays + plain digit passes
         XD_HIP_CHECK(ctx, hipMemsetAsync(d_sums, 0, 16, ctx->stream));
         if (n > 0) {
-            hipLaunchKernelGGL((nk_y_kernel<T>), dim3(grid_for(ctx, n, 256, 16)), dim3(256), sizeof(T) * (nb + 1), ctx->stream, dh, st, asp, n,
-                               (T)vs, d_edges, nb, y, bins, d_sums, P->custom_edges.empty() ? NK_AUTO_EDGES : P->custom_decimal);
+            // (the two sums seed curve_fit: added in a fixed order, so that a fit repeats its bits -- per-workgroup partials in the slots
+            //  of the one-pass step, which this route never runs beside)
+            const int n_wg = grid_for(ctx, n, 256, 16);
+            const size_t slots = ((size_t)n_wg * 2 + 4) / 5;   // (the capacity counts rows of five doubles)
+            if (slots > P->wg_sums_cap) {
+                P->wg_sums_cap = P->mem.regrow(P->wg_sums, slots * 5 * sizeof(double), "per-workgroup sums of the y pass") ? slots : 0;
+                { const int rc_ = P->mem.status(); if (rc_) return rc_; }
+            }
+            hipLaunchKernelGGL((nk_y_kernel<T>), dim3(n_wg), dim3(256), sizeof(T) * (nb + 1), ctx->stream, dh, st, asp, n,
+                               (T)vs, d_edges, nb, y, bins, d_sums, P->custom_edges.empty() ? NK_AUTO_EDGES : P->custom_decimal, P->wg_sums);
+            hipLaunchKernelGGL(nk_y_sums_kernel, dim3(1), dim3(256), 0, ctx->stream, P->wg_sums, n_wg, d_sums);
             XD_HIP_CHECK(ctx, hipGetLastError());
         }
         rc = run_select_core<T>(ctx, y, bins, n, nb, base, hs, SEL_MEDIAN, nullptr);

@@ -1,7 +1,8 @@
 """Minimal georeferenced DEM container whose terrain / co-registration methods run on the GPU.
 
-In the reference ``xdem.DEM`` subclasses ``geoutils.Raster`` (I/O, CRS, reprojection -- all out of scope here) and
-only *forwards* to the hot paths (``xdem/dem.py:429-665``).  This class mirrors exactly that forwarding layer so that
+In the reference ``xdem.DEM`` subclasses ``geoutils.Raster`` (I/O, CRS, reprojection between CRSs -- all out of scope here) and
+only *forwards* to the hot paths (``xdem/dem.py:429-665``).  Of ``Raster.reproject`` the same-CRS case is here: ``DEM.reproject``
+regrids onto another north-up grid on the GPU (``xdem_amd.reproject``).  This class mirrors exactly that forwarding layer so that
 ``DEM.slope()``, ``DEM.get_terrain_attribute()`` and ``DEM.coregister_3d()`` keep their signatures; for real I/O keep
 using geoutils / rasterio and either pass their Raster objects straight to ``xdem_amd.terrain`` functions (any object
 with ``.data``, ``.res``, ``.transform``, ``.crs`` and a ``from_array`` classmethod is accepted) or wrap arrays with
@@ -64,6 +65,20 @@ class DEM:
 
     def copy(self) -> "DEM":
         return DEM(self.data.copy(), self.transform, self.crs, self.nodata)
+
+    # ---- regridding (geoutils' Raster.reproject, same CRS) ------------------------------------------------------------
+    def reproject(self, ref=None, crs=None, res=None, grid_size=None, bounds=None, nodata=None, dtype=None, resampling="bilinear",
+                  force_source_nodata=None, silent: bool = False, n_threads: int = 0, memory_limit: int = 64) -> "DEM":
+        """This DEM on another north-up grid of its own CRS, resampled on the GPU (``geoutils.Raster.reproject``'s signature).  The grid:
+        ``ref`` (a DEM, or anything with ``.shape`` and ``.transform``), or ``res`` / ``grid_size`` / ``bounds`` as
+        ``xdem_amd.reproject.target_grid`` reads them.  ``resampling``: "nearest", "bilinear", "cubic", "cubic_spline" (or rasterio's
+        enum).  Returns a new DEM with this CRS and ``nodata`` (the argument, else this DEM's); voids and pixels outside this DEM are
+        NaN.  A target grid equal to this one returns ``self`` with a warning (``silent=True``: none).  ``force_source_nodata`` masks
+        that value first; ``n_threads`` and ``memory_limit`` are accepted and ignored; a ``crs`` other than this DEM's raises."""
+        from .reproject import reproject_dem
+
+        return reproject_dem(self, ref=ref, crs=crs, res=res, grid_size=grid_size, bounds=bounds, nodata=nodata, dtype=dtype,
+                             resampling=resampling, force_source_nodata=force_source_nodata, silent=silent)
 
     # ---- terrain forwarders (xdem/dem.py:429-619) -------------------------------------------------------------
     def _surface_fit(self, method, surface_fit):
@@ -166,7 +181,8 @@ class DEM:
             out, out_transform = method.apply(self.data, resample=resample, transform=self.transform)
             return DEM(out, out_transform, self.crs, self.nodata)
         if reference_elev.shape != self.shape or reference_elev.transform != self.transform:
-            raise NotImplementedError("reference and to-be-aligned DEM must share one grid (reprojection is geoutils' job).")
+            raise NotImplementedError("reference and to-be-aligned DEM must share one grid (reprojection is geoutils' job); "
+                                      "call DEM.reproject(reference_elev) first to regrid within one CRS.")
         mask = None if inlier_mask is None else np.asarray(getattr(inlier_mask, "data", inlier_mask), dtype=bool)
         # (a step that rotates works about a centroid in the grid's coordinates: it gets the transform; the others read the resolution)
         steps = getattr(method, "pipeline", [method])
@@ -201,7 +217,8 @@ class DEM:
         if not isinstance(other_elev, DEM):
             raise TypeError("Other elevation should be a DEM or elevation point cloud object.")
         if other_elev.shape != self.shape or other_elev.transform != self.transform:
-            raise NotImplementedError("both DEMs must share one grid (reprojection is geoutils' job).")
+            raise NotImplementedError("both DEMs must share one grid (reprojection is geoutils' job); "
+                                      "call DEM.reproject(other_elev) first to regrid within one CRS.")
         dh = other_elev.data - self.data
         if precision_of_other == "same":
             dh = dh / np.sqrt(2)

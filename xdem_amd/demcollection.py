@@ -10,8 +10,9 @@ filled plane has the bits ``volume.hypsometric_interpolation`` gives for it.
 
 Outlines are ``xdem_amd.Vector`` tables, as upstream takes them, or boolean arrays on the DEMs' grid (or a dict of either by
 timestamp).  A Vector is burnt into the grid on the GPU when a mask is first asked for and the mask is kept per (vector, filter, grid);
-the union of a start and an end outline is one call (``xdemhip_rasterize_union``).  DEMs on different grids are refused (reprojection
-is geoutils' job).  A stack of mixed dtypes is float64 throughout.
+the union of a start and an end outline is one call (``xdemhip_rasterize_union``).  DEMs on different grids are refused by the
+constructor's route (reprojection is geoutils' job); ``DEMCollection.on_reference_grid`` regrids them onto the reference's grid first
+(same CRS, ``xdem_amd.reproject``).  A stack of mixed dtypes is float64 throughout.
 
 One quirk of upstream is reproduced on purpose: the constructor sorts ``dems`` by time but leaves ``timestamps`` in the caller's order
 (demcollection.py:70-78), so ``reference_timestamp`` and the intervals of the dDEMs index the UNSORTED stamps with SORTED positions.
@@ -245,6 +246,26 @@ class DEMCollection:
         self._fused = None         # (mask keys, figures) of the last batched fill
         self._burnt: dict = {}     # masks made from Vector outlines, by (vectors, filter, grid, memspace)
 
+    @classmethod
+    def on_reference_grid(cls, dems, timestamps=None, outlines=None, reference_dem=0, resampling="cubic_spline") -> "DEMCollection":
+        """The collection of `dems` with every DEM that is not on the reference's grid regridded onto it first (``DEM.reproject``, same
+        CRS; a ``datetime`` attribute is carried over).  Upstream's ``subtract_dems`` calls ``dem.reproject(resampling=...)`` with no
+        target for this; the reference's grid is the evident intent.  ``subtract_dems()`` of the result is the batched pass."""
+        dems = list(dems)
+        ref = dems[reference_dem] if isinstance(reference_dem, (int, np.integer)) else reference_dem
+        ref_grid = (tuple(ref.shape), tuple(float(v) for v in ref.transform))
+        on_grid = []
+        for dem in dems:
+            if dem is not ref and (tuple(dem.shape), tuple(float(v) for v in dem.transform)) != ref_grid:
+                if not isinstance(dem, DEM):
+                    dem = DEM.from_array(dem.data, dem.transform, dem.crs, dem.nodata)
+                moved = dem.reproject(ref, resampling=resampling, silent=True)
+                if hasattr(dem, "datetime"):
+                    moved.datetime = dem.datetime
+                dem = moved
+            on_grid.append(dem)
+        return cls(on_grid, timestamps=timestamps, outlines=outlines, reference_dem=reference_dem)
+
     @property
     def reference_dem(self) -> DEM:
         return self.dems[self.reference_index]
@@ -262,7 +283,8 @@ class DEMCollection:
         shape = tuple(ref.data.shape)
         for dem in self.dems:
             if tuple(dem.data.shape) != shape or dem.transform != ref.transform:
-                raise NotImplementedError("all DEMs of a collection must share one grid (reprojection is geoutils' job).")
+                raise NotImplementedError("all DEMs of a collection must share one grid (reprojection is geoutils' job); "
+                                          "DEMCollection.on_reference_grid(...) regrids them within one CRS first.")
         can_equal = [dem.nodata == ref.nodata or (dem.nodata is None and ref.nodata is None) for dem in self.dems]
         if self._plan is not None:
             self._plan.close()
