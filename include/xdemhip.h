@@ -966,6 +966,31 @@ int xdemhip_rasterize_union(xdemhip_ctx* ctx, const double* xy_a, int64_t V_a, c
                             unsigned char* out, int memspace, int64_t* n_burnt);
 int xdemhip_rasterize_launches(xdemhip_ctx* ctx, int64_t* n_launches);
 
+/* ---- exact Euclidean distance transform (edt.hip; geoutils' Raster.proximity) ---------------------------------------
+ * xdemhip_edt: for every pixel of an H x W plane the distance to the nearest target (targets[y * W + x] != 0) under the sampling
+ * (sy of rows, sx of columns; finite, > 0).  THE RULE, float64, every fl one rounding (the file is built without contraction):
+ *   d(y, x) = sqrt( min over targets (ty, tx) of  fl( fl(fl((y - ty) sy)^2) + fl(fl((x - tx) sx)^2) ) )
+ * the true float64 minimum of that expression over all targets (SciPy's expression, axis 0 first).  No target: +inf everywhere,
+ * indices -1.  `dist` (may be null): H * W of dist_dtype (XDEMHIP_F32: the float64 result rounded once).  `idx` (may be null):
+ * int32 [2][H][W], row and column of the target that attains the minimum; among targets of equal cost the smaller |x - tx| wins,
+ * then the smaller tx, then within that column the nearer row, the upper row on a tie.  `keep` (may be null): H * W bytes, the
+ * distance is 0 wherever (keep != 0) != (keep_polarity != 0) (indices are not touched).  n_targets (may be null; a host word):
+ * the targets counted.  Planes in `memspace`; the call returns synchronised and holds no memory afterwards.  Sides 1 .. 2^31 - 1.
+ * Only sums, products and comparisons of the costs above decide which target wins (no divisions, no parabola intersections): the
+ * column pass keeps the nearest target of each column as an integer row offset, the row pass scans outward from each pixel and
+ * stops at the first column distance whose own cost reaches the best so far, skipping blocks of columns whose lower bound does.
+ * (Test switch "edt_route"; xdemhip_edt_plan of include/xdemhip_test.h has the tile constants.)
+ * xdemhip_edt_targets: out[i] = 1 where src[i] is a target, else 0: with n_values = 0 finite and != 0, else equal to one of
+ * values[0 .. n_values) (at most 64, host doubles; NaN never is a target).  src of XDEMHIP_F32 / _F64 / _U8 / _I32, n >= 1 elements.
+ * xdemhip_mask_boundary: out = 1 on the inner boundary of a byte mask: a mask pixel with a 4-neighbour INSIDE the raster that is not
+ * in the mask (the raster's edge makes no boundary), else 0. */
+enum { XDEMHIP_I32 = 3 };
+int xdemhip_edt(xdemhip_ctx* ctx, const unsigned char* targets, int64_t H, int64_t W, double sy, double sx, void* dist, int dist_dtype,
+                int32_t* idx, const unsigned char* keep, int keep_polarity, int memspace, int64_t* n_targets);
+int xdemhip_edt_targets(xdemhip_ctx* ctx, const void* src, int src_dtype, int64_t n, const double* values, int n_values,
+                        unsigned char* out, int memspace);
+int xdemhip_mask_boundary(xdemhip_ctx* ctx, const unsigned char* mask, int64_t H, int64_t W, unsigned char* out, int memspace);
+
 #ifdef __cplusplus
 }
 #endif

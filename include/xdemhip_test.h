@@ -25,7 +25,10 @@
  *                        xdemhip_rasterize_stage_ms returns the device time between them (a measurement form: the same planes).
  *   "regrid_route"       0 (default) xdemhip_regrid takes the LDS-tiled route while a workgroup's source footprint fits its LDS budget and
  *                        the per-pixel route that reads its taps from global memory beyond it; 1 = the tiled route wherever the footprint
- *                        fits (today the automatic choice, pinned against a later change of policy); 2 = the per-pixel route always. */
+ *                        fits (today the automatic choice, pinned against a later change of policy); 2 = the per-pixel route always.
+ *   "edt_route"          0 (default) the row pass of xdemhip_edt scans a window of column offsets staged in LDS and goes on block by block
+ *                        in global memory beyond its halo; 1 = no window: every pixel takes the block search in global memory; 2 = band
+ *                        height, tile, halo and block shrunk to their minima, so that small planes cross bands, tiles and blocks. */
 #pragma once
 #include "xdemhip.h"
 #ifdef __cplusplus
@@ -42,6 +45,12 @@ int xdemhip_plan_bytes(xdemhip_ctx* ctx, int64_t* bytes);
  * *route = XDEMHIP_REGRID_ROUTE_*, *lds_bytes = what a workgroup of the tiled route would ask for, *lds_budget = the most it may. */
 enum { XDEMHIP_REGRID_ROUTE_NEAREST = 0, XDEMHIP_REGRID_ROUTE_TILE = 1, XDEMHIP_REGRID_ROUTE_DIRECT = 2 };
 int xdemhip_regrid_route(const double* map4, int kernel, int src_dtype, int route_switch, int* route, int64_t* lds_bytes, int64_t* lds_budget);
+/* ms[4]: device time of the four passes (down, carry, up, row) of the last xdemhip_edt call on this context. */
+int xdemhip_edt_stage_ms(xdemhip_ctx* ctx, float* ms);
+/* The constants xdemhip_edt works with on an H x W plane under a value of "edt_route" (host only, no context): rows of a band of the
+ * column pass, columns of a tile of the row pass, its halo on either side (0: no window), columns of a block of the block minima,
+ * bytes of a stored row offset (2 while H <= 32767, else 4).  Any output may be null. */
+int xdemhip_edt_plan(int64_t H, int64_t W, int route_switch, int* band_rows, int* tile_cols, int* halo, int* block_cols, int* offset_bytes);
 #ifdef __cplusplus
 }
 #endif

@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "csrc", "libxdemhip.so")
 
 OK = 0
-F32, F64, U8 = 0, 1, 2
+F32, F64, U8, I32 = 0, 1, 2, 3
 HOST, DEVICE = 0, 1
 
 _lib = None
@@ -297,6 +297,13 @@ def lib() -> ctypes.CDLL:
         L.xdemhip_regrid.argtypes = [c_ctx, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int,
                                      ctypes.c_int64, ctypes.c_int64, c_dp, ctypes.c_int, ctypes.c_int, c_i64p]
         L.xdemhip_regrid_route.argtypes = [c_dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_ip, c_i64p, c_i64p]
+        c_u8p = ctypes.c_void_p
+        L.xdemhip_edt.argtypes = [c_ctx, c_u8p, ctypes.c_int64, ctypes.c_int64, ctypes.c_double, ctypes.c_double, ctypes.c_void_p, ctypes.c_int,
+                                  ctypes.c_void_p, c_u8p, ctypes.c_int, ctypes.c_int, c_i64p]
+        L.xdemhip_edt_targets.argtypes = [c_ctx, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, c_dp, ctypes.c_int, c_u8p, ctypes.c_int]
+        L.xdemhip_mask_boundary.argtypes = [c_ctx, c_u8p, ctypes.c_int64, ctypes.c_int64, c_u8p, ctypes.c_int]
+        L.xdemhip_edt_plan.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int, c_ip, c_ip, c_ip, c_ip, c_ip]
+        L.xdemhip_edt_stage_ms.argtypes = [c_ctx, ctypes.POINTER(ctypes.c_float)]
         _lib = L
         return L
 
@@ -563,7 +570,7 @@ class Context:
             self._L.xdemhip_device_free(self.handle, ctypes.c_void_p(p))
 
     TEST_SWITCHES = frozenset(("terrain_stream", "terrain_order", "terrain_ring_wait", "terrain_window_lds", "nk_narrow",
-                               "vario_grid", "vario_runs", "vario_sort", "hypso_seg_lds", "pts_tile_order", "bw_seg_lds", "vec_seg_reg", "vec_seg_lds", "vec_stage_times", "regrid_route"))
+                               "vario_grid", "vario_runs", "vario_sort", "hypso_seg_lds", "pts_tile_order", "bw_seg_lds", "vec_seg_reg", "vec_seg_lds", "vec_stage_times", "regrid_route", "edt_route"))
 
     def set_option(self, name: str, value: int) -> None:
         """Option of the library (``xdemhip_set_option``: the names listed in include/xdemhip.h), e.g. ``("selection", 1)`` -- or,

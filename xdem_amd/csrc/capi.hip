@@ -327,6 +327,7 @@ const XdOpt kTestSwitches[] = {
     {"vec_stage_times", 0, 1, &xdemhip_ctx::vec_stage_times, "vec_stage_times: 0 or 1"},
     {"vec_seg_lds", 0, 4096, &xdemhip_ctx::vec_seg_lds, "vec_seg_lds: 0 (default: 4096) or 1 to 4096 crossings"},
     {"regrid_route", 0, 2, &xdemhip_ctx::regrid_route, "regrid_route: 0 automatic, 1 tiled where it fits, 2 per-pixel"},
+    {"edt_route", 0, 2, &xdemhip_ctx::edt_route, "edt_route: 0 automatic, 1 global block search only, 2 minimal band, tile, halo and block"},
 };
 int xd_set_from(xdemhip_ctx* ctx, const XdOpt* tab, size_t n, const char* name, int value, bool* found) {
     *found = false;

@@ -80,6 +80,17 @@ class DEM:
         return reproject_dem(self, ref=ref, crs=crs, res=res, grid_size=grid_size, bounds=bounds, nodata=nodata, dtype=dtype,
                              resampling=resampling, force_source_nodata=force_source_nodata, silent=silent)
 
+    # ---- proximity (geoutils' Raster.proximity) --------------------------------------------------------------------------
+    def proximity(self, vector=None, target_values=None, geometry_type="boundary", in_or_out="both", distance_unit="georeferenced",
+                  dtype=np.float32) -> "DEM":
+        """The distance of every pixel to the nearest target on the GPU (``geoutils.Raster.proximity``'s signature): a DEM on this
+        grid and CRS without nodata.  Targets: this DEM's non-zero finite pixels, those equal to one of ``target_values``, or the
+        outlines of ``vector`` (an ``xdem_amd.Vector``: ``geometry_type`` "boundary" / "polygon", ``in_or_out`` "in" / "out" /
+        "both").  ``distance_unit``: "pixel" or "georeferenced".  See ``xdem_amd.proximity.proximity``."""
+        from .proximity import proximity
+
+        return proximity(self, vector, target_values, geometry_type, in_or_out, distance_unit, dtype)
+
     # ---- terrain forwarders (xdem/dem.py:429-619) -------------------------------------------------------------
     def _surface_fit(self, method, surface_fit):
         if method is not None:

@@ -10,8 +10,8 @@ pixel centre that lies EXACTLY on an edge may differ from the half-open rule use
 Geometries are taken by duck typing (shapely and geopandas are never imported): an ``(N, 2)`` array (one exterior ring), ``(exterior,
 [holes...])``, a list of those (a multipolygon), a GeoJSON-like mapping (``Polygon``, ``MultiPolygon``, ``Feature``; a
 ``FeatureCollection`` as the whole argument, its properties becoming the table), or any object that answers shapely's calls
-(``.geom_type``, ``.exterior.coords``, ``.interiors``, ``.geoms``).  Out of scope: lines and points, ``all_touched=True``, buffering,
-reprojection of a vector, file formats other than GeoJSON.
+(``.geom_type``, ``.exterior.coords``, ``.interiors``, ``.geoms``).  Out of scope: lines and points, ``all_touched=True``, buffering a
+geometry (``create_mask(buffer=)`` buffers the burnt mask), reprojection of a vector, file formats other than GeoJSON.
 """
 from __future__ import annotations
 
@@ -226,6 +226,14 @@ class DeviceRasterizer:
         return int(n.value)
 
 
+class _SizedGrid:
+    """A grid without data: what ``Vector.proximity(raster=None)`` hands on (``.data`` is only asked for its shape)."""
+
+    def __init__(self, shape, transform, crs):
+        self.shape, self.transform, self.crs = shape, transform, crs
+        self.data = np.broadcast_to(np.uint8(0), shape)
+
+
 _RASTERIZER: Any = DeviceRasterizer()   # (a test puts its oracle here)
 
 
@@ -345,12 +353,15 @@ class Vector:
         shape = (max(1, int(np.ceil((b.top - b.bottom) / ry))), max(1, int(np.ceil((b.right - b.left) / rx))))
         return shape, (rx, 0.0, float(b.left), 0.0, -ry, float(b.top))
 
-    def create_mask(self, raster=None, res=None, bounds=None, as_array: bool = True, device: bool = False):
+    def create_mask(self, raster=None, res=None, bounds=None, as_array: bool = True, device: bool = False, buffer: float = 0):
         """True where a pixel's centre is inside a polygon of the table.  `raster`: a DEM, a dDEM or ``(shape, transform)``.  With `res`
         alone the grid runs from ``(left, top)`` of `bounds` (default: the vector's) with ``ceil(extent / res)`` pixels each way, at
         least one -- UNPINNED: geoutils' own choice of that grid cannot be read offline.  Returns a NumPy bool array, with `device` a
         torch bool tensor on the GPU (nothing is fetched), with ``as_array=False`` a DEM around either.  The mask is kept per grid and
-        memspace and returned again by the next call (the host array is read-only)."""
+        memspace and returned again by the next call (the host array is read-only).  `buffer` (upstream's keyword, georeferenced units
+        between pixel centres): > 0 adds the pixels whose distance to the nearest mask pixel is <= buffer, < 0 keeps the mask pixels
+        whose distance to the nearest pixel outside the mask is > |buffer| (``xdem_amd.proximity``; UNPINNED: geoutils buffers the
+        geometry with shapely before burning it)."""
         shape, t6 = self._grid(raster, res, bounds)
         key = ("mask", shape, t6, bool(device))
         if key not in self._cache:
@@ -359,11 +370,42 @@ class Vector:
                 mask.setflags(write=False)   # (kept per (shape, transform, memspace) and handed out again: copy it to change it)
             self._cache[key] = mask
         mask = self._cache[key]
+        if buffer != 0:
+            from . import proximity as _prox
+
+            bkey = key + (float(buffer),)
+            if bkey not in self._cache:
+                grown = _prox.buffered_mask(mask, (abs(t6[4]), abs(t6[0])), buffer)
+                if isinstance(grown, np.ndarray):
+                    grown.setflags(write=False)
+                self._cache[bkey] = grown
+            mask = self._cache[bkey]
         if as_array:
             return mask
         from .ddem import raster_of
 
         return raster_of(mask, t6, self.crs, None)
+
+    def proximity(self, raster=None, size=(1000, 1000), geometry_type="boundary", in_or_out="both", distance_unit="georeferenced",
+                  dtype=np.float32):
+        """``geoutils.Vector.proximity``: the distance of every pixel of `raster`'s grid to this vector's outlines
+        (``xdem_amd.proximity.proximity``; a DEM on that grid, a device plane when `raster`'s data is one).  With ``raster=None`` the
+        grid has `size` = (columns, rows) pixels over the vector's bounds and the plane is a host array."""
+        from . import proximity as _prox
+
+        if raster is None:
+            raster = _SizedGrid(*self.size_grid(size), self.crs)
+        return _prox.proximity(raster, self, None, geometry_type, in_or_out, distance_unit, dtype)
+
+    def size_grid(self, size) -> tuple:
+        """``((rows, columns), transform6)`` of a grid of `size` = (columns, rows) pixels over the vector's bounds."""
+        w, h = (int(v) for v in size)
+        if w < 1 or h < 1:
+            raise ValueError("size must be at least (1, 1)")
+        b = self.bounds
+        if not all(np.isfinite(v) for v in b) or not (b.right > b.left and b.top > b.bottom):
+            raise ValueError("a grid from `size` needs bounds with an extent: the vector has none")
+        return (h, w), ((b.right - b.left) / w, 0.0, float(b.left), 0.0, -(b.top - b.bottom) / h, float(b.top))
 
     def rasterize(self, raster, in_value=None, out_value=0, device: bool = False):
         """An int32 plane on the grid of `raster`: `in_value` of the polygon that holds the pixel's centre, the LATER polygon of the
