@@ -991,6 +991,37 @@ int xdemhip_edt_targets(xdemhip_ctx* ctx, const void* src, int src_dtype, int64_
                         unsigned char* out, int memspace);
 int xdemhip_mask_boundary(xdemhip_ctx* ctx, const unsigned char* mask, int64_t H, int64_t W, unsigned char* out, int memspace);
 
+/* ---- sampling a raster at points, a raster as points (spline.hip; geoutils' Raster.interp_points / to_pointcloud) -----
+ * THE RULE, float64, every operation one rounding (the file is built without contraction); transform6 = (a, b, c, d, e, f), b = d = 0:
+ *   r = (y - f) / e - 0.5, cc = (x - c) / a - 0.5 (without the 0.5 when shift != 0); a point with r outside [0, H - 1] or cc outside
+ *   [0, W - 1], or a non-finite coordinate, gives NaN.
+ *   spread = the non-finite pixels grown by `dist` in city-block distance; a point is NaN if one of its four bilinear corner pixels
+ *   with non-zero weight (w0 = 1 - t, w1 = 1 - w0) is in it.  A raster without a finite pixel gives NaN everywhere.
+ *   order 0: the pixel floor(r + 0.5), floor(cc + 0.5).  order 1: the four taps of the raster itself.  orders 3 and 5: the
+ *   (order + 1)^2 B-spline taps (SciPy's weight polynomials, mirror index mapping) of the coefficient plane: the mirror spline
+ *   prefilter (per axis a gain, per pole a causal and an anticausal recursion; columns first) of the raster whose non-finite pixels
+ *   took the value of their nearest finite pixel (xdemhip_edt's winner on unit sampling).  value = sum of ((c wr) wc) from 0.0, rows
+ *   outer and columns inner, rounded once to the raster's dtype.
+ * xdemhip_spline_prepare: makes the plan of an H x W raster (sides >= 2; XDEMHIP_F32 / _F64; host or device memory) for an order
+ *   (0, 1, 3, 5) and a spreading distance: the spread plane and, for orders 3 and 5, the coefficients, in device memory the plan
+ *   owns.  For orders 0 and 1 the plan reads the raster at every gather: a device raster must outlive the plan (a host raster is
+ *   copied).  *n_nonfinite = the number of non-finite pixels.  Returns synchronised.  (Test switch "spline_route".)
+ * xdemhip_spline_gather: out[i] = the value at (x[i], y[i]), i < n (float64 columns; host or device memory, the result where the
+ *   points are) in out_dtype: the raster's dtype, or XDEMHIP_F64 for the value before its one rounding; *n_valid = the number of
+ *   results that are not NaN.  Returns synchronised.
+ * xdemhip_raster_points: the pixels of a raster in row-major order as x = c + (col + 0.5) a, y = f + (row + 0.5) e (float64) and z
+ *   (the raster's dtype); skip_nodata != 0 keeps the finite pixels only (per-row counts, an exclusive scan, a write in column order).
+ *   *count = the number of points; with x = y = z = null only the count is made, else `capacity` (elements) must hold it.
+ *   Returns synchronised. */
+typedef struct xdemhip_spline xdemhip_spline;
+int xdemhip_spline_prepare(xdemhip_ctx* ctx, const void* raster, int dtype, int64_t H, int64_t W, int order, int dist, int memspace,
+                           xdemhip_spline** out, int64_t* n_nonfinite);
+int xdemhip_spline_gather(xdemhip_spline* plan, const double* x, const double* y, int64_t n, const double* transform6, int shift, void* out,
+                          int out_dtype, int memspace, int64_t* n_valid);
+void xdemhip_spline_destroy(xdemhip_spline* plan);
+int xdemhip_raster_points(xdemhip_ctx* ctx, const void* raster, int dtype, int64_t H, int64_t W, const double* transform6, int skip_nodata,
+                          double* x, double* y, void* z, int64_t capacity, int memspace, int64_t* count);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,7 +28,10 @@
  *                        fits (today the automatic choice, pinned against a later change of policy); 2 = the per-pixel route always.
  *   "edt_route"          0 (default) the row pass of xdemhip_edt scans a window of column offsets staged in LDS and goes on block by block
  *                        in global memory beyond its halo; 1 = no window: every pixel takes the block search in global memory; 2 = band
- *                        height, tile, halo and block shrunk to their minima, so that small planes cross bands, tiles and blocks. */
+ *                        height, tile, halo and block shrunk to their minima, so that small planes cross bands, tiles and blocks.
+ *   "spline_route"       0 (default) the prefilter of xdemhip_spline_prepare runs its column passes in bands of rows and its row passes
+ *                        out of LDS tiles where a row is longer than its two warm-up halos, else one thread per row; 1 = one band per
+ *                        column (no warm-up halo along rows); 2 = the one-thread-per-row route always; 3 = the LDS tiles always. */
 #pragma once
 #include "xdemhip.h"
 #ifdef __cplusplus
@@ -51,6 +54,18 @@ int xdemhip_edt_stage_ms(xdemhip_ctx* ctx, float* ms);
  * column pass, columns of a tile of the row pass, its halo on either side (0: no window), columns of a block of the block minima,
  * bytes of a stored row offset (2 while H <= 32767, else 4).  Any output may be null. */
 int xdemhip_edt_plan(int64_t H, int64_t W, int route_switch, int* band_rows, int* tile_cols, int* halo, int* block_cols, int* offset_bytes);
+/* The constants the prefilter of xdemhip_spline_prepare works with on an H x W raster (sides >= 2) for an order (0, 1, 3, 5) under a
+ * value of "spline_route" (host only, no context): rows of a band of the column passes, rows and columns of a tile of the row passes
+ * (1 x W: the one-thread-per-row route), the warm-up halo in samples, LDS bytes of a workgroup of the row passes.  Any output may be null. */
+int xdemhip_spline_plan(int64_t H, int64_t W, int order, int route_switch, int* band_rows, int* tile_rows, int* tile_cols, int* halo, int* lds_bytes);
+/* One line of the prefilter on the CPU through the functions the kernels run (host only, no context): every pole of the order (3, 5)
+ * over in[0 .. n), n >= 2, cut into bands of `band` samples; two_phase != 0: each band walked as the LDS row route walks a segment. */
+int xdemhip_spline_host_line(const double* in, int64_t n, int order, int64_t band, int two_phase, double* out);
+/* ms[4]: device time of the stages of the prepare that made this plan: mask and fill, dilation, column passes, row passes. */
+int xdemhip_spline_stage_ms(xdemhip_spline* plan, float* ms);
+/* The planes a plan holds, copied out (either may be null; asking for one the plan does not hold is XDEMHIP_EINVAL): the uint8 spread
+ * plane (held while the raster has some but not only non-finite pixels) and the float64 coefficients (orders 3 and 5). */
+int xdemhip_spline_planes(xdemhip_spline* plan, unsigned char* spread, double* coef, int memspace);
 #ifdef __cplusplus
 }
 #endif

@@ -304,6 +304,18 @@ def lib() -> ctypes.CDLL:
         L.xdemhip_mask_boundary.argtypes = [c_ctx, c_u8p, ctypes.c_int64, ctypes.c_int64, c_u8p, ctypes.c_int]
         L.xdemhip_edt_plan.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int, c_ip, c_ip, c_ip, c_ip, c_ip]
         L.xdemhip_edt_stage_ms.argtypes = [c_ctx, ctypes.POINTER(ctypes.c_float)]
+        L.xdemhip_spline_plan.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int, c_ip, c_ip, c_ip, c_ip, c_ip]
+        L.xdemhip_spline_prepare.argtypes = [c_ctx, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                             ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), c_i64p]
+        L.xdemhip_spline_gather.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, c_dp, ctypes.c_int, ctypes.c_void_p,
+                                            ctypes.c_int, ctypes.c_int, c_i64p]
+        L.xdemhip_spline_planes.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+        L.xdemhip_spline_stage_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
+        L.xdemhip_spline_host_line.argtypes = [c_dp, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int, c_dp]
+        L.xdemhip_spline_destroy.argtypes = [ctypes.c_void_p]
+        L.xdemhip_spline_destroy.restype = None
+        L.xdemhip_raster_points.argtypes = [c_ctx, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, c_dp, ctypes.c_int, ctypes.c_void_p,
+                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, c_i64p]
         _lib = L
         return L
 
@@ -570,7 +582,7 @@ class Context:
             self._L.xdemhip_device_free(self.handle, ctypes.c_void_p(p))
 
     TEST_SWITCHES = frozenset(("terrain_stream", "terrain_order", "terrain_ring_wait", "terrain_window_lds", "nk_narrow",
-                               "vario_grid", "vario_runs", "vario_sort", "hypso_seg_lds", "pts_tile_order", "bw_seg_lds", "vec_seg_reg", "vec_seg_lds", "vec_stage_times", "regrid_route", "edt_route"))
+                               "vario_grid", "vario_runs", "vario_sort", "hypso_seg_lds", "pts_tile_order", "bw_seg_lds", "vec_seg_reg", "vec_seg_lds", "vec_stage_times", "regrid_route", "edt_route", "spline_route"))
 
     def set_option(self, name: str, value: int) -> None:
         """Option of the library (``xdemhip_set_option``: the names listed in include/xdemhip.h), e.g. ``("selection", 1)`` -- or,

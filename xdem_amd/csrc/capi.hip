@@ -328,6 +328,7 @@ const XdOpt kTestSwitches[] = {
     {"vec_seg_lds", 0, 4096, &xdemhip_ctx::vec_seg_lds, "vec_seg_lds: 0 (default: 4096) or 1 to 4096 crossings"},
     {"regrid_route", 0, 2, &xdemhip_ctx::regrid_route, "regrid_route: 0 automatic, 1 tiled where it fits, 2 per-pixel"},
     {"edt_route", 0, 2, &xdemhip_ctx::edt_route, "edt_route: 0 automatic, 1 global block search only, 2 minimal band, tile, halo and block"},
+    {"spline_route", 0, 3, &xdemhip_ctx::spline_route, "spline_route: 0 automatic, 1 one band per column, 2 plain row route, 3 LDS row route"},
 };
 int xd_set_from(xdemhip_ctx* ctx, const XdOpt* tab, size_t n, const char* name, int value, bool* found) {
     *found = false;

@@ -57,6 +57,7 @@ struct xdemhip_ctx {
     int vec_stage_times = 0; // test switch "vec_stage_times": 1 xdemhip_rasterize records an event at every stage's start (measurement: xdemhip_rasterize_stage_ms)
     int regrid_route = 0;    // test switch "regrid_route": 0 xdemhip_regrid picks its route by the LDS budget, 1 the tiled route wherever the footprint fits, 2 the per-pixel route always
     int edt_route = 0;       // test switch "edt_route": 0 the row pass of xdemhip_edt scans an LDS window first, 1 global block search only, 2 minimal band / tile / halo / block
+    int spline_route = 0;    // test switch "spline_route": prefilter of xdemhip_spline_prepare: 0 banded columns and LDS rows where a row is longer than its halos, 1 one band per column, 2 plain rows always, 3 LDS rows always
     float edt_stage_ms[4] = {0, 0, 0, 0};      // device time of the four passes (down, carry, up, row) of the last xdemhip_edt call
     float vec_stage_ms[5] = {0, 0, 0, 0, 0};   // device time of the five stages of the last xdemhip_rasterize call made under that switch
     int64_t vec_launches = 0;   // kernels launched by the last xdemhip_rasterize / xdemhip_rasterize_union call (xdemhip_rasterize_launches)

@@ -91,6 +91,27 @@ class DEM:
 
         return proximity(self, vector, target_values, geometry_type, in_or_out, distance_unit, dtype)
 
+    # ---- points (geoutils' Raster.interp_points / Raster.to_pointcloud) --------------------------------------------------------
+    def interp_points(self, points, method="linear", dist_nodata_spread="half_order_up", band: int = 1, input_latlon: bool = False,
+                      shift_area_or_point: bool = False, force_scipy_function=None):
+        """The elevations at ``points`` = ``(x, y)`` (arrays or device tensors) or an ``EPC``-like cloud, sampled on the GPU
+        (``geoutils.Raster.interp_points``'s signature): "nearest", "linear", "cubic" or "quintic", NaN outside the hull of the
+        pixel centres and within ``dist_nodata_spread`` of a void.  ``band`` other than 1 and ``input_latlon=True`` raise.  The
+        values where the points live.  See ``xdem_amd.interp.interp_points``; an iterative caller keeps an ``interp.InterpPlan``."""
+        from .interp import dem_interp_points
+
+        return dem_interp_points(self, points, method, dist_nodata_spread, band, input_latlon, shift_area_or_point, force_scipy_function)
+
+    def to_pointcloud(self, data_column_name="b1", data_band: int = 1, auxiliary_data_bands=None, auxiliary_column_names=None, subsample=1,
+                      skip_nodata: bool = True, as_array: bool = False, random_state=None, force_pixel_offset="center"):
+        """This DEM as an ``EPC`` of its pixel centres in row-major order (``geoutils.Raster.to_pointcloud``'s signature), the valid
+        pixels only with ``skip_nodata``; ``as_array``: an ``(N, 3)`` float64 array of x, y, z.  ``subsample`` other than 1, auxiliary
+        bands and a ``force_pixel_offset`` other than "center" raise ``NotImplementedError``."""
+        from .interp import dem_to_pointcloud
+
+        return dem_to_pointcloud(self, data_column_name, data_band, auxiliary_data_bands, auxiliary_column_names, subsample, skip_nodata,
+                                 as_array, random_state, force_pixel_offset)
+
     # ---- terrain forwarders (xdem/dem.py:429-619) -------------------------------------------------------------
     def _surface_fit(self, method, surface_fit):
         if method is not None:
