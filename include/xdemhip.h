@@ -1022,6 +1022,52 @@ void xdemhip_spline_destroy(xdemhip_spline* plan);
 int xdemhip_raster_points(xdemhip_ctx* ctx, const void* raster, int dtype, int64_t H, int64_t W, const double* transform6, int skip_nodata,
                           double* x, double* y, void* z, int64_t capacity, int memspace, int64_t* count);
 
+/* ---- connected components and outline rings (ccl.hip; scipy.ndimage.label, geoutils' Raster.polygonize) -------------------
+ * THE RULE of xdemhip_label.  `classes`: an H x W plane of XDEMHIP_U8 or XDEMHIP_I32, 0 = background; H * W < 2^31 (else XDEMHIP_EINVAL).
+ *   Two pixels are joined iff they are neighbours under `connectivity` (4: sharing an edge; 8: or a corner) and hold the same non-zero
+ *   class; a component is a class of the transitive closure.  `labels` (int32, H x W): 0 on background; the components are numbered
+ *   1 .. K in raster order of their first pixel, the one with the smallest row * W + col.  On a 0/1 plane that is scipy.ndimage.label's
+ *   numbering with generate_binary_structure(2, 1) for 4 and (2, 2) for 8.  *K (a host word): the number of components.
+ *   `table` (may be null): K x 7 int64, COLUMN by column (table[col * K + l - 1] for label l): class, pixel count, row_min, row_max,
+ *   col_min, col_max (inclusive), linear index of the first pixel.  It is written when `capacity` (components) holds K; a smaller
+ *   capacity returns XDEMHIP_EINVAL with the labels and *K written, so a caller without a bound passes table = null, reads K and calls
+ *   xdemhip_label_table on the label plane it has (the way xdemhip_raster_points is called twice).
+ *   Union-find on a parent plane whose roots are the smallest linear index of their set, split over launches at every inter-workgroup
+ *   hand-off (no flags, no spin-waiting); counts, minima and maxima are integer atomics: the same bits every run.
+ *   (Test switch "ccl_route"; xdemhip_label_plan of include/xdemhip_test.h has the tile.)
+ * xdemhip_label_table: the same table from a label plane and the class plane it was made of (labels outside 1 .. K are skipped).
+ * THE RULE of xdemhip_outlines.  `labels`: an int32 H x W plane, 0 = background, a component = the pixels of one value in 1 .. K (any
+ *   other value: XDEMHIP_EINVAL), as xdemhip_label makes them under either connectivity.  Vertices are pixel corners (i, j), i in [0, H],
+ *   j in [0, W].  A component owns one unit EDGE for each side of each of its pixels whose neighbour across that side is not in the
+ *   component (another component, background, or outside the raster).  Sides: 0 top, 1 left, 2 bottom, 3 right; edge number =
+ *   4 * (row * W + col) + side.  An edge is directed with its pixel on the left in map coordinates (x east, y north): the top side
+ *   runs west, the left side south, the bottom side east, the right side north.  The SUCCESSOR of an edge is the edge of the same
+ *   component that starts at its end vertex; with `ahead` the pixel across the end vertex on the edge's own side and `across` the one on
+ *   the other side: if `across` is in the component the ring turns right onto its previous side (so at a PINCH vertex, where two
+ *   diagonally opposite pixels belong to the component and two edges start, the ring keeps hugging the non-member pixel on its right);
+ *   else if `ahead` is in the component it goes straight on along the same side of `ahead`; else it turns left onto the next side of
+ *   its own pixel.  The successor is a permutation of the edges; its cycles are the RINGS.  Every component has exactly one ring of
+ *   positive signed area, its exterior, counter-clockwise in map coordinates, and any number of rings of negative area, its holes,
+ *   clockwise; the signed areas of a component's rings add up to its pixel count.  Under connectivity 4 no ring visits a vertex twice;
+ *   under connectivity 8 a ring may touch itself at a pinch vertex (inherent; GDAL's polygonize does the same).
+ *   Only CORNER edges, those whose successor turns, give a vertex: their end vertex.  A ring starts at the end vertex of its
+ *   lowest-numbered corner edge and follows the successors.  The lowest edge of a component is the top side of its first pixel, a corner
+ *   edge of its exterior, so with the rings of a component in increasing number of that edge the exterior comes first; components
+ *   follow in label order.  x = c + a * j, y = f + e * i in float64, one multiply and one add each (built without contraction), for the
+ *   north-up transform6 (a, 0, c, 0, e, f), a > 0 > e (else XDEMHIP_EINVAL).
+ *   Outputs, the table layout xdemhip_rasterize reads: xy = the V abscissae, then the V ordinates, packed for the V the call returns;
+ *   ring_off (R + 1 int64), poly_of_ring (R int32: label - 1), ring_area (may be null; R int64: the signed area in pixels).  *V and *R
+ *   are host words.  With xy = ring_off = poly_of_ring = null only the counting pass runs: *V is exact and *R is the bound V / 4 (a
+ *   ring has at least four corners); the full call needs v_capacity >= V and r_capacity >= V / 4 (ring_off one more) and returns the
+ *   exact *R.  V must stay below 2^31.  The number of kernel launches depends on H and W only.
+ * All planes and arrays in `memspace`; every call returns synchronised and holds no memory afterwards. */
+int xdemhip_label(xdemhip_ctx* ctx, const void* classes, int dtype, int64_t H, int64_t W, int connectivity, int32_t* labels, int64_t* table,
+                  int64_t capacity, int memspace, int64_t* K);
+int xdemhip_label_table(xdemhip_ctx* ctx, const void* classes, int dtype, const int32_t* labels, int64_t H, int64_t W, int64_t K, int64_t* table,
+                        int memspace);
+int xdemhip_outlines(xdemhip_ctx* ctx, const int32_t* labels, int64_t H, int64_t W, int64_t K, const double* transform6, double* xy, int64_t v_capacity,
+                     int64_t* ring_off, int32_t* poly_of_ring, int64_t* ring_area, int64_t r_capacity, int memspace, int64_t* V, int64_t* R);
+
 #ifdef __cplusplus
 }
 #endif

@@ -31,7 +31,9 @@
  *                        height, tile, halo and block shrunk to their minima, so that small planes cross bands, tiles and blocks.
  *   "spline_route"       0 (default) the prefilter of xdemhip_spline_prepare runs its column passes in bands of rows and its row passes
  *                        out of LDS tiles where a row is longer than its two warm-up halos, else one thread per row; 1 = one band per
- *                        column (no warm-up halo along rows); 2 = the one-thread-per-row route always; 3 = the LDS tiles always. */
+ *                        column (no warm-up halo along rows); 2 = the one-thread-per-row route always; 3 = the LDS tiles always.
+ *   "ccl_route"          0 (default) xdemhip_label labels tiles of 64 x 64 pixels in LDS before the border unions; 2 = minimal tiles of 2 x 2
+ *                        pixels, so that small planes cross tile borders and four-tile corners everywhere (no value 1). */
 #pragma once
 #include "xdemhip.h"
 #ifdef __cplusplus
@@ -66,6 +68,14 @@ int xdemhip_spline_stage_ms(xdemhip_spline* plan, float* ms);
 /* The planes a plan holds, copied out (either may be null; asking for one the plan does not hold is XDEMHIP_EINVAL): the uint8 spread
  * plane (held while the raster has some but not only non-finite pixels) and the float64 coefficients (orders 3 and 5). */
 int xdemhip_spline_planes(xdemhip_spline* plan, unsigned char* spread, double* coef, int memspace);
+/* The tile xdemhip_label works with on an H x W plane (H * W < 2^31) under a value of "ccl_route" (host only, no context): rows and
+ * columns of a tile, the tiles down and across, the LDS bytes of a workgroup and the budget they must stay within.  Any output may be null. */
+int xdemhip_label_plan(int64_t H, int64_t W, int route_switch, int* tile_rows, int* tile_cols, int64_t* tiles_r, int64_t* tiles_c, int* lds_bytes,
+                       int* lds_budget);
+/* ms[11]: device time of the stages of the last xdemhip_label call on this context (tile, border, flatten, number, table; the table
+ * stage also after xdemhip_label_table) and of the last full xdemhip_outlines call (corners, walk, leader, rank, rings with their fetch
+ * and host ordering, gather).  launches (may be null) [2]: the kernels those two calls launched. */
+int xdemhip_ccl_stage_ms(xdemhip_ctx* ctx, float* ms, int64_t* launches);
 #ifdef __cplusplus
 }
 #endif

@@ -316,6 +316,14 @@ def lib() -> ctypes.CDLL:
         L.xdemhip_spline_destroy.restype = None
         L.xdemhip_raster_points.argtypes = [c_ctx, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, c_dp, ctypes.c_int, ctypes.c_void_p,
                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, c_i64p]
+        L.xdemhip_label.argtypes = [c_ctx, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                    ctypes.c_int64, ctypes.c_int, c_i64p]
+        L.xdemhip_label_table.argtypes = [c_ctx, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                          ctypes.c_void_p, ctypes.c_int]
+        L.xdemhip_outlines.argtypes = [c_ctx, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, c_dp, ctypes.c_void_p, ctypes.c_int64,
+                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, c_i64p, c_i64p]
+        L.xdemhip_label_plan.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int, c_ip, c_ip, c_i64p, c_i64p, c_ip, c_ip]
+        L.xdemhip_ccl_stage_ms.argtypes = [c_ctx, ctypes.POINTER(ctypes.c_float), c_i64p]
         _lib = L
         return L
 
@@ -582,7 +590,7 @@ class Context:
             self._L.xdemhip_device_free(self.handle, ctypes.c_void_p(p))
 
     TEST_SWITCHES = frozenset(("terrain_stream", "terrain_order", "terrain_ring_wait", "terrain_window_lds", "nk_narrow",
-                               "vario_grid", "vario_runs", "vario_sort", "hypso_seg_lds", "pts_tile_order", "bw_seg_lds", "vec_seg_reg", "vec_seg_lds", "vec_stage_times", "regrid_route", "edt_route", "spline_route"))
+                               "vario_grid", "vario_runs", "vario_sort", "hypso_seg_lds", "pts_tile_order", "bw_seg_lds", "vec_seg_reg", "vec_seg_lds", "vec_stage_times", "regrid_route", "edt_route", "spline_route", "ccl_route"))
 
     def set_option(self, name: str, value: int) -> None:
         """Option of the library (``xdemhip_set_option``: the names listed in include/xdemhip.h), e.g. ``("selection", 1)`` -- or,

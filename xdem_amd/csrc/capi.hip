@@ -329,6 +329,7 @@ const XdOpt kTestSwitches[] = {
     {"regrid_route", 0, 2, &xdemhip_ctx::regrid_route, "regrid_route: 0 automatic, 1 tiled where it fits, 2 per-pixel"},
     {"edt_route", 0, 2, &xdemhip_ctx::edt_route, "edt_route: 0 automatic, 1 global block search only, 2 minimal band, tile, halo and block"},
     {"spline_route", 0, 3, &xdemhip_ctx::spline_route, "spline_route: 0 automatic, 1 one band per column, 2 plain row route, 3 LDS row route"},
+    {"ccl_route", 0, 2, &xdemhip_ctx::ccl_route, "ccl_route: 0 automatic tiles or 2 minimal tiles"},
 };
 int xd_set_from(xdemhip_ctx* ctx, const XdOpt* tab, size_t n, const char* name, int value, bool* found) {
     *found = false;
@@ -377,6 +378,7 @@ int xdemhip_set_test_switch(xdemhip_ctx* ctx, const char* name, int value) {
     if (!ctx || !name) return XDEMHIP_EINVAL;
     if (strcmp(name, "terrain_stream") == 0 && !(value == 0 || value == 1 || value == 2 || value == 3 || value == 128 || value == 256 || value == 512))
         return xd_fail(ctx, XDEMHIP_EINVAL, "terrain_stream: 0, 1, 2, 3, 128, 256 or 512");
+    if (strcmp(name, "ccl_route") == 0 && value == 1) return xd_fail(ctx, XDEMHIP_EINVAL, "ccl_route: 0 automatic tiles or 2 minimal tiles");
     bool found = false;
     const int rc = xd_set_from(ctx, kTestSwitches, sizeof kTestSwitches / sizeof kTestSwitches[0], name, value, &found);
     if (found) return rc;

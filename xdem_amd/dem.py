@@ -91,6 +91,15 @@ class DEM:
 
         return proximity(self, vector, target_values, geometry_type, in_or_out, distance_unit, dtype)
 
+    # ---- polygonize (geoutils' Raster.polygonize) -------------------------------------------------------------------------
+    def polygonize(self, target_values="all", data_column_name="id", connectivity=4, by_value=False) -> Vector:
+        """The target pixels of this DEM as a ``Vector`` of outline polygons, one per connected component, labelled and traced on the
+        GPU (``geoutils.Raster.polygonize``'s signature; ``connectivity`` and ``by_value`` are this project's).  ``target_values``: a
+        number, a ``(min, max)`` tuple, a list, or "all" (finite and not nodata).  See ``xdem_amd.polygonize.polygonize``."""
+        from .polygonize import polygonize
+
+        return polygonize(self, target_values, data_column_name, connectivity, by_value)
+
     # ---- points (geoutils' Raster.interp_points / Raster.to_pointcloud) --------------------------------------------------------
     def interp_points(self, points, method="linear", dist_nodata_spread="half_order_up", band: int = 1, input_latlon: bool = False,
                       shift_area_or_point: bool = False, force_scipy_function=None):

@@ -291,6 +291,20 @@ class Vector:
             obj = {"type": "FeatureCollection", "features": [obj]}
         return cls(obj, crs=crs)
 
+    @classmethod
+    def from_mask(cls, mask, raster, connectivity=4, crs=None) -> "Vector":
+        """The outlines of a boolean mask on the grid of `raster` (a DEM, a dDEM or ``(shape, transform)``): one polygon per connected
+        component, labelled and traced on the GPU (``xdem_amd.polygonize``); the column ``id`` numbers them ``0..K-1``."""
+        from .ddem import raster_of
+        from .polygonize import polygonize
+
+        shape, t6 = grid_of(raster)
+        m = mask if hasattr(mask, "is_cuda") else np.asarray(mask)
+        if tuple(m.shape) != shape or str(m.dtype).split(".")[-1] != "bool":
+            raise ValueError(f"from_mask takes a boolean mask of the grid's shape {shape}")
+        grid = raster_of(m, t6, crs if crs is not None else getattr(raster, "crs", None), None)
+        return polygonize(grid, 1, "id", connectivity)
+
     # ---- the table -------------------------------------------------------------------------------------------------------------------
     def __len__(self) -> int:
         return len(self.ds)
