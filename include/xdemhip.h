@@ -1068,6 +1068,36 @@ int xdemhip_label_table(xdemhip_ctx* ctx, const void* classes, int dtype, const 
 int xdemhip_outlines(xdemhip_ctx* ctx, const int32_t* labels, int64_t H, int64_t W, int64_t K, const double* transform6, double* xy, int64_t v_capacity,
                      int64_t* ring_off, int32_t* poly_of_ring, int64_t* ring_area, int64_t r_capacity, int memspace, int64_t* V, int64_t* R);
 
+/* ---- raster filters (filter.hip; scipy.ndimage.gaussian_filter / generic_filter, xDEM's old xdem/filters.py) -----------
+ * xdemhip_filter: out = the filter `kind` of the H x W plane `in` (XDEMHIP_F32 / _F64, row-major; sides 1 .. 2^31 - 1), in the same
+ * dtype and memspace.  NaN = missing; +-Inf are ordinary values.  tests/filters_oracle.py restates every rule in NumPy and every route
+ * returns its bits (the file is built without contraction).  `out` must not overlap `in` (XDEMHIP_EINVAL).
+ *   XDEMHIP_FILTER_GAUSSIAN  scipy.ndimage.gaussian_filter(mode="reflect"): `radius` = lw = int(truncate * sigma + 0.5) and `weights` =
+ *     the 2 lw + 1 normalised float64 weights, both made by the caller on the host (the library has no exp; it checks sigma > 0,
+ *     truncate > 0 and that radius is that lw).  Axis 0 first, then axis 1; one pass, float64, in SciPy's order:
+ *     tmp = c w[lw]; for i = -lw .. -1: tmp += (x[i] + x[-i]) w[i + lw]; x mirrored about the raster's edges (d c b a | a b c d | d c b a,
+ *     repeated when lw exceeds the side); the axis-0 result is rounded to the dtype before the axis-1 pass, the axis-1 result after it.
+ *     `normalise` 0: that, NaN spreading as in SciPy.  1: g = G(in with NaN -> 0), n = G(1 where not NaN else 0, in the dtype),
+ *     out = g / n in the dtype (IEEE division), NaN where in is NaN.  2: 1 if the plane holds a NaN (one counting pass), else 0.
+ *   XDEMHIP_FILTER_MEDIAN / _MIN / _MAX  the window size x size (odd, >= 3) about the pixel, clipped at the raster's edge: the median /
+ *     minimum / maximum of its non-NaN values, NaN if it has none, whether or not the centre is NaN.  An even count gives (a + b) / 2
+ *     of the two middle values in float64, rounded once.  Values are compared as order-preserving unsigned keys: -0.0 < +0.0.
+ *   XDEMHIP_FILTER_MEAN  footprint = the square size x size (size odd >= 3, radius = 0) or the disk dy^2 + dx^2 <= radius^2 (size = 0,
+ *     radius >= 0), clipped at the edge: the float64 sum of its non-NaN values from +0.0, dy outer and dx inner, both ascending, divided
+ *     by their count and rounded once; NaN for an empty window.
+ *   XDEMHIP_FILTER_DISTANCE  out = in, but NaN where |in - m| > threshold, m the unrounded float64 disk mean (radius; the centre
+ *     included), the comparison in float64 (false for a NaN on either side).  One pass; no mean plane is stored.
+ * A workgroup stages its tile and halo in LDS once, the edge rule applied while staging, and filters from there; halos beyond the LDS
+ * budget read their taps from global memory (the Gaussian in two launches through a plane of the call's own): no upper limit on sigma,
+ * size or radius but XDEMHIP_EUNSUPPORTED above lw = 2^20 and above radius 16383 / size 32767 (int32 window counts).
+ * Returns synchronised whenever the call held a buffer of its own (host memory, a Gaussian's weights, a disk's table); a square
+ * window on device memory is queued on the context's stream.  The call holds no memory afterwards.
+ * (Test switch "filter_route"; xdemhip_filter_plan of include/xdemhip_test.h has the tile.) */
+enum { XDEMHIP_FILTER_GAUSSIAN = 0, XDEMHIP_FILTER_MEDIAN = 1, XDEMHIP_FILTER_MEAN = 2, XDEMHIP_FILTER_MIN = 3, XDEMHIP_FILTER_MAX = 4,
+       XDEMHIP_FILTER_DISTANCE = 5 };
+int xdemhip_filter(xdemhip_ctx* ctx, const void* in, int dtype, int64_t H, int64_t W, int kind, int size, int radius, double sigma,
+                   double truncate, const double* weights, int normalise, double threshold, void* out, int memspace);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,7 +33,11 @@
  *                        out of LDS tiles where a row is longer than its two warm-up halos, else one thread per row; 1 = one band per
  *                        column (no warm-up halo along rows); 2 = the one-thread-per-row route always; 3 = the LDS tiles always.
  *   "ccl_route"          0 (default) xdemhip_label labels tiles of 64 x 64 pixels in LDS before the border unions; 2 = minimal tiles of 2 x 2
- *                        pixels, so that small planes cross tile borders and four-tile corners everywhere (no value 1). */
+ *                        pixels, so that small planes cross tile borders and four-tile corners everywhere (no value 1).
+ *   "filter_route"       0 (default) xdemhip_filter takes the LDS-tiled route while tile and halo fit its LDS budget and reads its taps from
+ *                        global memory beyond it; 1 = the tiled route wherever the halo fits (today the automatic choice, pinned against a
+ *                        later change of policy); 2 = the global route always; 3 = tiles shrunk to their minimum (4 x 8 pixels), so that
+ *                        small planes cross tile borders and corners everywhere. */
 #pragma once
 #include "xdemhip.h"
 #ifdef __cplusplus
@@ -76,6 +80,13 @@ int xdemhip_label_plan(int64_t H, int64_t W, int route_switch, int* tile_rows, i
  * stage also after xdemhip_label_table) and of the last full xdemhip_outlines call (corners, walk, leader, rank, rings with their fetch
  * and host ordering, gather).  launches (may be null) [2]: the kernels those two calls launched. */
 int xdemhip_ccl_stage_ms(xdemhip_ctx* ctx, float* ms, int64_t* launches);
+/* The frame xdemhip_filter works with on an H x W plane for a kind (XDEMHIP_FILTER_*), a halo `radius` (the Gaussian's lw, size / 2
+ * of a window, the radius of a disk) and a dtype under a value of "filter_route" (host only, no context): rows and columns of a tile,
+ * its halo on every side, the LDS bytes of a workgroup of the tiled route (the Gaussian's counted with its normalising planes), the
+ * budget they must stay within, and *route = XDEMHIP_FILTER_ROUTE_*.  Any output may be null. */
+enum { XDEMHIP_FILTER_ROUTE_TILE = 1, XDEMHIP_FILTER_ROUTE_GLOBAL = 2 };
+int xdemhip_filter_plan(int64_t H, int64_t W, int kind, int radius, int dtype, int route_switch, int* tile_rows, int* tile_cols, int* halo,
+                        int64_t* lds_bytes, int64_t* lds_budget, int* route);
 #ifdef __cplusplus
 }
 #endif

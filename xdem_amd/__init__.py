@@ -14,6 +14,7 @@ from . import terrain  # noqa: F401
 from . import coreg, spatialstats  # noqa: F401
 from . import proximity  # noqa: F401  (distance_transform_edt, proximity: geoutils' Raster.proximity)
 from . import polygonize  # noqa: F401  (label, outlines, polygonize: scipy.ndimage.label and geoutils' Raster.polygonize)
+from . import filters  # noqa: F401  (gaussian, median, mean, min, max and distance filters: geoutils' Raster.filter)
 from . import interp  # noqa: F401  (interp_points, InterpPlan, raster_points: geoutils' Raster.interp_points / to_pointcloud)
 from . import stats  # noqa: F401  (get_stats, percentile, linear_error: the raster statistics geoutils gives xdem's DEM)
 from . import freq, surfit, window  # noqa: F401  (the reference's engine-boundary modules: xdem.terrain.surfit / .window / .freq)

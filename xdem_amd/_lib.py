@@ -324,6 +324,10 @@ def lib() -> ctypes.CDLL:
                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, c_i64p, c_i64p]
         L.xdemhip_label_plan.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int, c_ip, c_ip, c_i64p, c_i64p, c_ip, c_ip]
         L.xdemhip_ccl_stage_ms.argtypes = [c_ctx, ctypes.POINTER(ctypes.c_float), c_i64p]
+        L.xdemhip_filter.argtypes = [c_ctx, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                     ctypes.c_double, ctypes.c_double, c_dp, ctypes.c_int, ctypes.c_double, ctypes.c_void_p, ctypes.c_int]
+        L.xdemhip_filter_plan.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_ip, c_ip, c_ip,
+                                          c_i64p, c_i64p, c_ip]
         _lib = L
         return L
 
@@ -590,7 +594,7 @@ class Context:
             self._L.xdemhip_device_free(self.handle, ctypes.c_void_p(p))
 
     TEST_SWITCHES = frozenset(("terrain_stream", "terrain_order", "terrain_ring_wait", "terrain_window_lds", "nk_narrow",
-                               "vario_grid", "vario_runs", "vario_sort", "hypso_seg_lds", "pts_tile_order", "bw_seg_lds", "vec_seg_reg", "vec_seg_lds", "vec_stage_times", "regrid_route", "edt_route", "spline_route", "ccl_route"))
+                               "vario_grid", "vario_runs", "vario_sort", "hypso_seg_lds", "pts_tile_order", "bw_seg_lds", "vec_seg_reg", "vec_seg_lds", "vec_stage_times", "regrid_route", "edt_route", "spline_route", "ccl_route", "filter_route"))
 
     def set_option(self, name: str, value: int) -> None:
         """Option of the library (``xdemhip_set_option``: the names listed in include/xdemhip.h), e.g. ``("selection", 1)`` -- or,

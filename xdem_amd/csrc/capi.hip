@@ -330,6 +330,7 @@ const XdOpt kTestSwitches[] = {
     {"edt_route", 0, 2, &xdemhip_ctx::edt_route, "edt_route: 0 automatic, 1 global block search only, 2 minimal band, tile, halo and block"},
     {"spline_route", 0, 3, &xdemhip_ctx::spline_route, "spline_route: 0 automatic, 1 one band per column, 2 plain row route, 3 LDS row route"},
     {"ccl_route", 0, 2, &xdemhip_ctx::ccl_route, "ccl_route: 0 automatic tiles or 2 minimal tiles"},
+    {"filter_route", 0, 3, &xdemhip_ctx::filter_route, "filter_route: 0 automatic, 1 tiled where the halo fits, 2 global taps, 3 minimal tiles"},
 };
 int xd_set_from(xdemhip_ctx* ctx, const XdOpt* tab, size_t n, const char* name, int value, bool* found) {
     *found = false;

@@ -59,7 +59,8 @@ struct xdemhip_ctx {
     int edt_route = 0;       // test switch "edt_route": 0 the row pass of xdemhip_edt scans an LDS window first, 1 global block search only, 2 minimal band / tile / halo / block
     int spline_route = 0;    // test switch "spline_route": prefilter of xdemhip_spline_prepare: 0 banded columns and LDS rows where a row is longer than its halos, 1 one band per column, 2 plain rows always, 3 LDS rows always
     int ccl_route = 0;       // test switch "ccl_route": tiles of xdemhip_label: 0 automatic (64 x 64), 2 minimal (2 x 2): small planes cross every tile border
-    float ccl_stage_ms[11] = {};               // device time of the stages of the last xdemhip_label (5) and xdemhip_outlines (6) calls (xdemhip_ccl_stage_ms)
+    int filter_route = 0;    // test switch "filter_route": xdemhip_filter: 0 tiled while tile and halo fit the LDS budget, 1 the same pinned, 2 taps from global memory always, 3 minimal tiles (4 x 8)
+    float ccl_stage_ms[11] = {};              // device time of the stages of the last xdemhip_label (5) and xdemhip_outlines (6) calls (xdemhip_ccl_stage_ms)
     int64_t ccl_launches = 0, ccl_stage_launches[2] = {0, 0};   // kernels launched by the call at hand; by the last xdemhip_label / xdemhip_outlines call
     float edt_stage_ms[4] = {0, 0, 0, 0};      // device time of the four passes (down, carry, up, row) of the last xdemhip_edt call
     float vec_stage_ms[5] = {0, 0, 0, 0, 0};   // device time of the five stages of the last xdemhip_rasterize call made under that switch

@@ -100,6 +100,17 @@ class DEM:
 
         return polygonize(self, target_values, data_column_name, connectivity, by_value)
 
+    # ---- filters (geoutils' Raster.filter) ---------------------------------------------------------------------------------------
+    def filter(self, method, inplace: bool = False, **kwargs):
+        """This DEM through a raster filter on the GPU: a new DEM on this grid, CRS and nodata, or with ``inplace=True`` this DEM changed
+        and None returned.  ``method``: "gaussian" (``sigma``, ``truncate=4.0``, ``normalise="auto"``), "median" / "min" / "max"
+        (``size``, odd), "mean" (``size`` or ``radius``), "distance" (``radius``, ``outlier_threshold``), or a callable that takes and
+        returns an array.  Voids (NaN, this DEM's nodata) are missing values: ignored by every window, kept by the Gaussian and the
+        distance filter, filled by the others where the window holds a value.  ``radius`` is in PIXELS.  See ``xdem_amd.filters``."""
+        from .filters import filter_dem
+
+        return filter_dem(self, method, inplace, **kwargs)
+
     # ---- points (geoutils' Raster.interp_points / Raster.to_pointcloud) --------------------------------------------------------
     def interp_points(self, points, method="linear", dist_nodata_spread="half_order_up", band: int = 1, input_latlon: bool = False,
                       shift_area_or_point: bool = False, force_scipy_function=None):
